@@ -3,7 +3,10 @@
 MI355X, next to the numpy-CPU baseline, with the roofline of the dominant
 kernel and a parity check of exactly what was timed.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+
+--dump-outputs writes what the last timed step computed (DIR/<output name>.npy; the inputs depend on the
+arguments alone), so that two builds can be compared output for output.
 
 N>1 runs one rank per GPU: `python -m planer_amd.launch --nproc N bench.py --gpus N ...`
 (the product's own torch-free spawner) or, as the driver does, `python -m
@@ -44,6 +47,7 @@ PEAK_HBM_GBS = 8000.0
 PER_GPU_BATCH = 32                 # BASELINE.json configs[2] / configs[3]: 32 images per GPU
 PROF_REPEAT = 10                   # launches of a step between its two stream markers in the per-layer passes
 PROFILE_TAG = "r06"
+DUMP_LIMIT_BYTES = 64 * 10**6      # --dump-outputs: all files together, headers included
 
 
 def cdiv(a, b):
@@ -145,6 +149,21 @@ def sample_sclk(ctx, step, sync, samples=5):
         return sorted(seen)[len(seen) // 2] if seen else None
     except Exception:
         return None
+
+
+def dump_outputs(path, names, arrays):
+    """--dump-outputs: one DIR/<name>.npy per graph output, float32 (float64 for other dtypes, which it holds exactly).  Past
+    DUMP_LIMIT_BYTES in all, every output keeps the same share of its elements, picked by a fixed seed and kept in flat
+    index order: the sample depends on the shapes alone, so two builds run with the same arguments write comparable files."""
+    os.makedirs(path, exist_ok=True)
+    arrays = [np.ascontiguousarray(a if a.dtype == np.float32 else a.astype(np.float64)) for a in arrays]
+    room = DUMP_LIMIT_BYTES - 4096 * len(arrays)                   # .npy headers
+    total = sum(a.nbytes for a in arrays)
+    for name, a in zip(names, arrays):
+        if total > room:
+            keep = a.size * room // total
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(path, re.sub(r"[^A-Za-z0-9_.-]", "_", name) + ".npy"), a)
 
 
 def oracle_net(g, b):
@@ -376,6 +395,9 @@ def main():
     ap.add_argument("--settle-ms", type=float, default=300.0,
                     help="run the step loop untimed for this long before the W warm-up steps, so the timed region sees "
                          "steady-state clocks (DVFS ramps over ~100 ms; the K timed steps last ~15-35 ms)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the outputs of the last timed step (rank 0's shard) to DIR/<output name>.npy, at most "
+                         "%d MB in all (a seeded sample of the elements beyond that)" % (DUMP_LIMIT_BYTES // 10**6))
     args = ap.parse_args()
 
     import planer_amd
@@ -460,10 +482,16 @@ def main():
     # A disturbed invocation (seen once in ~20 on the gpurun boxes: a first region at half rate, recovering over the next four while the
     # shader clock comes back) is measured longer, not reported: when the regions spread by more than 5 %, as many regions again are
     # timed and the median is taken over all of them (every rank sees the same MAX-over-ranks spans, so all ranks decide alike)
+    # (the extension's one untimed step when it times an odd number of steps keeps the last timed step on the batch it feeds
+    # without the extension: the settle loop runs steps in tens, so that batch depends on the arguments alone)
     extended = False
     if args.repeats > 1 and max(spans) > 1.05 * min(spans):
-        s2, o2 = dist.timed_repeats(comm, step, sync, args.steps, 0, args.repeats)
+        s2, o2 = dist.timed_repeats(comm, step, sync, args.steps, args.repeats * args.steps % 2, args.repeats)
         spans, own, extended = spans + s2, own + o2, True
+    if args.dump_outputs and rank == 0:        # read back before anything else launches the plan
+        o = plan.outputs
+        dump_outputs(args.dump_outputs, next(src for src, names, _ in g["flow"] if names == ["return"]),
+                     [t.get() for t in (o if isinstance(o, tuple) else (o,))])
     order = sorted(range(len(spans)), key=lambda i: spans[i])
     mid = order[len(order) // 2]
     elapsed = spans[mid]

@@ -122,6 +122,26 @@ def test_bench_default_command_prints_one_contract_line():
          (d["config"]["net_submit_images_per_sec"], d["value"]), gross=d["config"]["net_submit_images_per_sec"] < 0.8 * d["value"])
 
 
+def test_bench_dump_outputs_are_the_last_timed_step(tmp_path):
+    """`--dump-outputs DIR` writes the logits of the last timed step.  The settle loop runs steps in tens and the steps rotate
+    over two seeded batches, so after W warm-up steps and one region of K the last step fed batch (W + K - 1) mod 2 -- batch 1
+    here, the one the line's own parity check does not read (rank 0's batch i is default_rng(1 + 1000 i))."""
+    import numpy as np
+    from bench import oracle_net
+    from planer_amd.irgen import resnet18
+    from tests.conftest import RTOL, assert_close
+    env = dict(os.environ)
+    env.pop("PLANER_HIP_STREAMS", None)
+    d = _bench_line(["--steps", "8", "--warmup", "2", "--repeats", "1", "--no-cpu-baseline", "--no-extra", "--no-e2e",
+                     "--dump-outputs", str(tmp_path)], env)
+    assert d["steps"] == 8 and d["config"]["repeat_values"]["repeats"] == 1
+    assert os.listdir(tmp_path) == ["logits.npy"]
+    y = np.load(tmp_path / "logits.npy")
+    assert y.dtype == np.float32 and y.shape == (32, 1000)
+    x = np.random.default_rng(1 + 1000 * 1).standard_normal((32, 3, 224, 224)).astype(np.float32)
+    assert_close(y, oracle_net(*resnet18.build())(x), RTOL, "dumped logits vs the oracle on batch 1")
+
+
 def test_bench_two_gpus_under_the_launcher():
     """`bench.py --gpus 2` exactly as the driver launches it (one rank per GPU, RCCL weight broadcast, no collective in
     the forward pass).  Skipped unless two devices are visible.  The N=2 line must carry what makes it creditable:
