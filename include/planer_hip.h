@@ -200,6 +200,17 @@ int pl_conv2d_q4_f32(pl_ctx *ctx, const float *xq, int N, int Cin, int H, int W,
                      int pb, int pr, int group, const float *scale,
                      const float *shift, const float *resq, int act, double alpha);
 
+/* Depthwise convs (group == Cin == Cout, one filter plane per channel) on Q4 tensors: the fused
+ * tail of pl_conv2d_q4_f32 on a VALU kernel that stages each output tile's input window in LDS
+ * (any kh x kw, stride, dilation; symmetric pads).  pl_conv2d_fused_f32 takes the same kernel's
+ * NCHW form by itself for w_layout 0.  wq ("w_layout 13") from pl_conv2d_prepare_dw_q4_f32:
+ * OIHW [C][1][kh][kw] -> [ceil(C/4)][kh*kw][4], zero-padded quads: ceil(C/4)*kh*kw*4 floats. */
+int pl_conv2d_prepare_dw_q4_f32(pl_ctx *ctx, const float *w, int C, int kh, int kw, float *out);
+int pl_conv2d_dw_q4_f32(pl_ctx *ctx, const float *xq, int N, int C, int H, int W,
+                        const float *wq, int kh, int kw, const float *bias, float *yq,
+                        int sh, int sw, int dh, int dw, int pt, int pl, int pb, int pr,
+                        const float *scale, const float *shift, const float *resq, int act,
+                        double alpha);
 /* Winograd F(2x2,3x3) on Q4 tensors for 3x3 / stride 1 / pad 1 / group 1 convs with
  * Cin % 4 == 0 and Cout % 4 == 0: uq = [16][k-quad][Cout][4] filters made once per
  * model; float4 input/output transforms around one grouped 1x1 Q4 conv. */

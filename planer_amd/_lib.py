@@ -76,6 +76,8 @@ SIGNATURES = {
     "pl_conv2d_prepare_q4_f32": [_P, _P, _I, _I, _I, _I, _I, _P],
     "pl_conv2d_q4_f32": [_P, _P, _I, _I, _I, _I, _P, _I, _I, _I, _P, _P] + [_I] * 9
                         + [_P, _P, _P, _I, c_double],
+    "pl_conv2d_prepare_dw_q4_f32": [_P, _P, _I, _I, _I, _P],
+    "pl_conv2d_dw_q4_f32": [_P, _P, _I, _I, _I, _I, _P, _I, _I, _P, _P] + [_I] * 8 + [_P, _P, _P, _I, c_double],
     "pl_conv2d_winograd_q4_filter_elems": [_I, _I, POINTER(c_size_t)],
     "pl_conv2d_prepare_winograd_q4_f32": [_P, _P, _I, _I, _P],
     "pl_conv2d_winograd_q4_f32": [_P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _I, c_double],

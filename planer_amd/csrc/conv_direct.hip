@@ -581,6 +581,7 @@ __global__ void __launch_bounds__(256) permute_weights_kernel(const float *w, fl
 #include "conv_smallcin_kernel.h"
 #include "conv_smallcin_valu_kernel.h"
 #include "conv_stem_pool_kernel.h"
+#include "conv_dw_kernel.h"
 
 // ---- configurations ---------------------------------------------------------
 typedef Cfg<128, 128, 16, 2, 2> C128x128;
@@ -998,6 +999,56 @@ inline int rowpack_row_pixels(int W, int pl, int Wo, int sw, int kw, int Cin) {
     return std::max(W + 2 * pl, (Wo - 1) * sw + (4 * rq + Cin - 1) / Cin + 1);
 }
 
+// A depthwise conv (one filter plane per channel, conv_dw_kernel.h) on NCHW (vec 1: x / y [N][C][H][W], w OIHW) or channel-quad
+// (vec 4: x / y / res [N][C/4][H][W][4], w [C/4][kh*kw][4]) tensors.  Shapes are checked by the caller.  The geometry comes from
+// the shape: output tiles of about 1024 pixels whose staged input window fits 32 KB of LDS (several workgroups per CU), rows and
+// columns split evenly; windows that do not fit even for one pixel read their taps from global memory instead.
+// -> PL_EUNSUPPORTED when the grid cannot express the shape (more than 65535 channel planes or images).
+int dw_launch(pl_ctx *ctx, const float *x, int N, int C, int H, int W, const float *w, int kh, int kw, float *y, int sh, int sw,
+              int dh, int dw, int pt, int pl, int Ho, int Wo, const Epilogue &ep, int vec) {
+    const int planes = vec == 4 ? (C + 3) / 4 : C;
+    if (planes > 65535 || N > 65535) return PL_EUNSUPPORTED;
+    const size_t esize = vec * sizeof(float), budget = 32 * 1024;
+    auto win_rows = [&](int tr) { return (tr - 1) * sh + (kh - 1) * dh + 1; };
+    auto win_cols = [&](int tc) { return (tc - 1) * sw + (kw - 1) * dw + 1; };
+    auto lds = [&](int tr, int tc) { return (size_t)win_rows(tr) * win_cols(tc) * esize; };
+    int tc = std::min(Wo, 256);
+    while (tc > 1 && lds(1, tc) > budget) tc = (tc + 1) / 2;
+    int tr = std::max(1, std::min(Ho, 1024 / tc));
+    while (tr > 1 && lds(tr, tc) > budget) --tr;
+    const bool staged = lds(tr, tc) <= budget;
+    const int tiles_x = (Wo + tc - 1) / tc, tiles_y = (Ho + tr - 1) / tr;
+    tc = (Wo + tiles_x - 1) / tiles_x;                 // the same number of tiles, evened out
+    tr = (Ho + tiles_y - 1) / tiles_y;
+    PL_REQUIRE((long long)tiles_x * tiles_y < (1ll << 31), PL_EUNSUPPORTED, "depthwise conv: too many tiles");
+    DwArgs a;
+    a.x = x; a.w = w; a.y = y; a.ep = ep;
+    a.planes = planes; a.chans = C;
+    a.H = H; a.W = W; a.Ho = Ho; a.Wo = Wo;
+    a.kh = kh; a.kw = kw; a.sh = sh; a.sw = sw; a.dh = dh; a.dw = dw; a.pt = pt; a.pl = pl;
+    a.tile_rows = tr; a.tile_cols = tc;
+    a.in_rows = win_rows(tr); a.in_cols = win_cols(tc);
+    a.tiles_x = tiles_x;
+    a.div_cols = FastDiv(tc); a.div_in_cols = FastDiv(a.in_cols);
+    const size_t shmem = staged ? lds(tr, tc) : 0;
+    void (*kern)(const DwArgs) = nullptr;
+    // 3x3 (every depthwise conv of MobileNet-v2) with its taps in scalar registers; other extents loop over the filter
+    const bool k3 = kh == 3 && kw == 3;
+    if (vec == 4)
+        kern = !staged ? conv_dw_kernel<float4, 0, 0, false> : k3 ? conv_dw_kernel<float4, 3, 3, true> : conv_dw_kernel<float4, 0, 0, true>;
+    else
+        kern = !staged ? conv_dw_kernel<float, 0, 0, false> : k3 ? conv_dw_kernel<float, 3, 3, true> : conv_dw_kernel<float, 0, 0, true>;
+    const int threads = std::min(256, (tr * tc + 63) / 64 * 64);
+    hipLaunchKernelGGL(kern, dim3((unsigned)(tiles_x * tiles_y), (unsigned)planes, (unsigned)N), dim3(threads), shmem, ctx->stream, a);
+    PL_LAUNCH_CHECK();
+    ctx->last_plan = std::string(vec == 4 ? "depthwise-q4 " : "depthwise-nchw ") + std::to_string(tr) + "x" + std::to_string(tc) +
+                     "px" + (staged ? "" : " unstaged");
+    // (no MFMA: the extents describe the FMAs issued, one GEMM row per (padded) channel)
+    ctx->last_gemm[0] = (long long)planes * vec; ctx->last_gemm[1] = 1;
+    ctx->last_gemm[2] = (long long)N * Ho * Wo; ctx->last_gemm[3] = (long long)kh * kw;
+    return PL_OK;
+}
+
 }  // namespace
 
 int plhip::conv_launch(pl_ctx *ctx, const float *x, int N, int Cin, int H, int W, const float *w, int Cout, int kh, int kw,
@@ -1151,6 +1202,14 @@ int plhip::conv_launch(pl_ctx *ctx, const float *x, int N, int Cin, int H, int W
             ctx->last_gemm[2] = (long long)N * tiles_img * SC_PIX; ctx->last_gemm[3] = (long long)sa.steps * 2;
             return PL_OK;
         }
+    }
+
+    // depthwise (Cin/group == Cout/group == 1): the VALU kernel of conv_dw_kernel.h, HBM-bound where the implicit GEMM would use
+    // one MFMA row in 32; a forced configuration (tests / tuning tools) still reaches the generic kernel below
+    if (layout == 0 && Cin == group && Cout == group && ctx->conv_cfg < 0) {
+        const int rc = dw_launch(ctx, x, N, Cin, H, W, w, kh, kw, y, sh, sw, dh, dw, pt, pl, Ho, Wo,
+                                 make_epilogue(bias, scale, shift, res, act, alpha), 1);
+        if (rc != PL_EUNSUPPORTED) return rc;
     }
 
     ConvArgs a;
@@ -1766,6 +1825,44 @@ int pl_conv2d_prepare_q4_f32(pl_ctx *ctx, const float *w, int Cout, int Cin_g, i
                                                           q_pad, FastDiv(cout_g), FastDiv(q_pad), FastDiv(cqg));
     PL_LAUNCH_CHECK();
     return PL_OK;
+}
+
+int pl_conv2d_prepare_dw_q4_f32(pl_ctx *ctx, const float *w, int C, int kh, int kw, float *out) {
+    PL_REQUIRE(ctx && w && out, PL_EINVAL, "pl_conv2d_prepare_dw_q4_f32: null pointer");
+    PL_REQUIRE(C > 0 && kh > 0 && kw > 0, PL_EINVAL, "pl_conv2d_prepare_dw_q4_f32: bad shape");
+    PL_REQUIRE((reinterpret_cast<uintptr_t>(out) & 15u) == 0, PL_EINVAL, "pl_conv2d_prepare_dw_q4_f32: unaligned output");
+    const size_t total = (size_t)((C + 3) / 4) * kh * kw * 4;
+    PL_REQUIRE(total < (1ull << 31), PL_EUNSUPPORTED, "filter too large");
+    CtxGuard g(ctx);
+    const unsigned blocks = (unsigned)std::min<size_t>((total + 255) / 256, 2048);
+    pack_filter_dw_q4_kernel<<<blocks, 256, 0, ctx->stream>>>(w, out, (unsigned)total, C, kh * kw);
+    PL_LAUNCH_CHECK();
+    return PL_OK;
+}
+
+int pl_conv2d_dw_q4_f32(pl_ctx *ctx, const float *xq, int N, int C, int H, int W, const float *wq, int kh, int kw,
+                        const float *bias, float *yq, int sh, int sw, int dh, int dw, int pt, int pl, int pb, int pr,
+                        const float *scale, const float *shift, const float *resq, int act, double alpha) {
+    PL_REQUIRE(ctx && xq && wq && yq, PL_EINVAL, "pl_conv2d_dw_q4_f32: null pointer");
+    PL_REQUIRE(((reinterpret_cast<uintptr_t>(xq) | reinterpret_cast<uintptr_t>(yq) | reinterpret_cast<uintptr_t>(wq) |
+                 reinterpret_cast<uintptr_t>(resq)) & 15u) == 0, PL_EINVAL, "pl_conv2d_dw_q4_f32: Q4 tensors must be 16-byte aligned");
+    PL_REQUIRE(N >= 0 && C > 0 && H > 0 && W > 0 && kh > 0 && kw > 0, PL_EINVAL, "pl_conv2d_dw_q4_f32: bad shape");
+    PL_REQUIRE(sh > 0 && sw > 0 && dh > 0 && dw > 0 && pt >= 0 && pl >= 0, PL_EINVAL, "pl_conv2d_dw_q4_f32: bad parameter");
+    PL_REQUIRE(pt == pb && pl == pr, PL_EUNSUPPORTED, "asymmetric pads are undefined in the reference (util.py:8)");
+    PL_REQUIRE(act >= 0 && (act & 15) <= 2 && (act & ~31) == 0, PL_EINVAL, "pl_conv2d_dw_q4_f32: bad activation code");
+    const int Ho = (H + 2 * pt - (kh - 1) * dh - 1 + sh) / sh, Wo = (W + 2 * pl - (kw - 1) * dw - 1 + sw) / sw;
+    PL_REQUIRE(Ho > 0 && Wo > 0, PL_EINVAL, "pl_conv2d_dw_q4_f32: empty output (%d x %d)", Ho, Wo);
+    PL_REQUIRE(H + 2 * pt < 16384 && W + 2 * pl < 16384 && kh * dh < 16384 && kw * dw < 16384, PL_EUNSUPPORTED,
+               "pl_conv2d_dw_q4_f32: spatial extent above 16383");
+    const size_t quads = (size_t)N * ((C + 3) / 4);
+    PL_REQUIRE(quads * H * W * 4 < (1ull << 29) && quads * Ho * Wo * 4 < (1ull << 29), PL_EUNSUPPORTED,
+               "pl_conv2d_dw_q4_f32: tensor above 2 GiB");
+    if (N == 0) return PL_OK;
+    CtxGuard g(ctx);
+    const int rc = dw_launch(ctx, xq, N, C, H, W, wq, kh, kw, yq, sh, sw, dh, dw, pt, pl, Ho, Wo,
+                             make_epilogue(bias, scale, shift, resq, act, alpha), 4);
+    PL_REQUIRE(rc != PL_EUNSUPPORTED, PL_EUNSUPPORTED, "pl_conv2d_dw_q4_f32: more than 65535 channel quads or images");
+    return rc;
 }
 
 static int q4_convert(pl_ctx *ctx, const float *x, float *y, int N, int C, int HW, bool to_q4) {

@@ -41,7 +41,8 @@ W_LAYOUT_NAMES = {0: "igemm-nchw", 1: "tap-nchw", 2: "direct-q4 (conv_q4_kernel)
                   7: "wino4x4-q4 (transforms + grouped conv_q4_kernel)", 8: "w1d4 F(4,3) (conv_w1d4_kernel)",
                   9: "wf4 fused F(4x4,3x3) (conv_wf4_kernel)", 10: "stem + maxpool (conv_stem_pool_kernel)",
                   11: "wino43-q4 (mixed F(4,3) x F(3,3) tiles: transforms + 121 grouped conv_q4_kernel)",
-                  12: "stem + maxpool (conv_stem_pool_kernel)"}         # (the kernel reads the NCHW batch itself)
+                  12: "stem + maxpool (conv_stem_pool_kernel)",          # (the kernel reads the NCHW batch itself)
+                  13: "depthwise-q4 (conv_dw_kernel)"}
 
 
 def _as_list(v):
@@ -527,11 +528,13 @@ class Net:
                 lay = 2
                 if entry[2].get("rowpack") and _q4.rowpack_eligible(K.shape, **para):
                     lay = 6
+                elif _q4.dw_q4_eligible(K.shape, **para):
+                    lay = 13
                 elif (use_wino and _q4.w1d_q4_eligible(K.shape, **para)
                         and shapes.get(srcs[0].split("@")[0]) is not None):
                     lay = self._pick_conv_algo(_q4.ConvQ4, K, srcs, entry[2], shapes, wmap, q4=True)
                 key = {2: "%s@q4g%d" % (srcs[1], group), 4: srcs[1] + "@winoq4", 6: srcs[1] + "@rowpack", 7: srcs[1] + "@wino4q4",
-                       8: srcs[1] + "@w1d4q4", 9: srcs[1] + "@wf4q4", 11: srcs[1] + "@wino43q4"}[lay]
+                       8: srcs[1] + "@w1d4q4", 9: srcs[1] + "@wf4q4", 11: srcs[1] + "@wino43q4", 13: srcs[1] + "@dwq4"}[lay]
                 if key not in self._extra:
                     self._extra[key] = {2: lambda: _q4.prepare_q4_weights(K, group),
                                         4: lambda: _q4.prepare_winograd_q4_weights(K),
@@ -539,7 +542,8 @@ class Net:
                                         7: lambda: _q4.prepare_winograd4_q4_weights(K),
                                         8: lambda: _q4.prepare_w1d4_q4_weights(K),
                                         9: lambda: _q4.prepare_wf4_q4_weights(K),
-                                        11: lambda: _q4.prepare_winograd43_q4_weights(K)}[lay]()
+                                        11: lambda: _q4.prepare_winograd43_q4_weights(K),
+                                        13: lambda: _q4.prepare_dw_q4_weights(K)}[lay]()
                 srcs[1] = key
                 out_body[name] = [name, "conv_q4", dict(entry[2], w_layout=lay)]
             elif entry[1] in ("conv", "conv_fused") and len(srcs) >= 2 and srcs[1] in wmap:

@@ -117,7 +117,7 @@ def fuse_flow(layers, flow, init_names, shapes):
 # downstream of a conv -- and everything else reads NCHW, with a conversion step inserted where a
 # value is needed in the layout it was not produced in (converted copies are cached per value).
 Q4_POINTWISE = ("maxpool", "averagepool", "gap", "upsample", "batchnorm", "relu", "leakyrelu", "sigmoid",
-                "add", "concat")
+                "add", "concat", "clip")
 TO_Q4, FROM_Q4 = "@to_q4", "@from_q4"
 
 
@@ -128,7 +128,8 @@ def _is4d(shapes, key):
 
 def q4_conv_ok(srcs, para, inits, shapes):
     """A conv step can take the Q4 kernel: constant 4-D filter (and constant bias / scale / shift),
-    4-D input, symmetric pads, and groups that do not split a channel quad."""
+    4-D input, symmetric pads, and groups that do not split a channel quad -- or one input and one output channel per group
+    (a depthwise conv: q4.dw_q4_eligible)."""
     if len(srcs) < 2 or srcs[1] not in inits or not _is4d(shapes, srcs[1]) or not _is4d(shapes, srcs[0]):
         return False
     if any(k != "None" and k not in inits for k in srcs[2:5]):
@@ -138,6 +139,9 @@ def q4_conv_ok(srcs, para, inits, shapes):
     pads = list(para.get("pads", (0, 0, 0, 0)))
     if len(pads) == 4 and (pads[0] != pads[2] or pads[1] != pads[3]):
         return False
+    k = shapes[srcs[1]]
+    if cin_g == 1 and cout == group and k[2] <= 7 and k[3] <= 7:
+        return True
     return group == 1 or (cin_g % 4 == 0 and (cout // group) % 4 == 0)
 
 
@@ -152,6 +156,8 @@ def _q4_pointwise_ok(kind, srcs, para, inits, shapes):
         return para.get("axis", 0) in (1, -3) and len(acts) == len(srcs) and all(shapes[k][1] % 4 == 0 for k in srcs)
     if kind == "sigmoid":
         return c % 4 == 0
+    if kind == "clip":                    # clip(0) must be 0 where a partial last quad has padding lanes
+        return c % 4 == 0 or float(para.get("min", 0)) <= 0.0 <= float(para.get("max", 1))
     if kind == "batchnorm":
         return len(srcs) == 3 and srcs[1] in inits and srcs[2] in inits
     if kind == "upsample":
@@ -248,7 +254,7 @@ def assign_layouts(body, flow, init_names, shapes, force=False):
         if not as_q4:
             args = [need(k, False) for k in srcs]
             new_kind = kind
-        if kind == "relu":                       # in place (layer.py:46): cached copies of the input go stale
+        if kind in ("relu", "clip"):             # in place (layer.py:46, 250-251): cached copies of the input go stale
             drop_copies(srcs[0])
         out_key = dst
         produces_q4 = as_q4 and kind != "gap"
@@ -256,6 +262,11 @@ def assign_layouts(body, flow, init_names, shapes, force=False):
             out_key = dst + "@q4"                # the program's result is handed back as NCHW below
         add_layer([name, new_kind, para])
         out_flow.append([args, [name], out_key])
+        if kind == "clip" and not as_q4 and srcs[0] in q4 and i != last:
+            # clipped in place on its NCHW copy (a partial quad that clip would dirty): later readers of the input must
+            # see the clipped values, so the Q4 primary is made again from that copy
+            add_layer([TO_Q4, TO_Q4[1:], {}])
+            out_flow.append([[args[0]], [TO_Q4], srcs[0]])
         for k in _as_list(dst):
             q4.discard(k)
             drop_copies(k)
@@ -399,7 +410,7 @@ def fuse_conv1x1_wino_in(body, flow, kshape=lambda key: None, small=lambda key: 
 # the stride-2 3x3 conv and the 1x1 stride-2 projection -- both run in ONE launch (q4.ConvQ4Pair,
 # csrc/conv_q4_kernel.h conv_q4_pair_kernel).  The second conv moves up to the first one's place; it only needs the
 # shared input and constants, so that is legal unless something rewrites the input in place in between.
-_IN_PLACE = ("relu", "relu_q4", "clip", "erf", "instancenormalization")
+_IN_PLACE = ("relu", "relu_q4", "clip", "clip_q4", "erf", "instancenormalization")
 
 
 def pair_sibling_convs(body, flow, kshape=lambda key: None):

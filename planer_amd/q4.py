@@ -76,6 +76,27 @@ def prepare_q4_weights(K, group=1):
     return out
 
 
+def dw_q4_eligible(k_shape, group=1, strides=(1, 1), dilations=(1, 1), pads=(0, 0, 0, 0), **_):
+    """Depthwise conv with channel multiplier 1 (group == Cin == Cout, OIHW filter [C][1][kh][kw]), kh / kw up to 7, symmetric
+    pads: the VALU kernel of csrc/conv_dw_kernel.h (ConvQ4 w_layout=13).  Any stride and dilation."""
+    pads = list(pads)
+    return (len(k_shape) == 4 and k_shape[1] == 1 and k_shape[0] == group and 1 <= k_shape[2] <= 7 and 1 <= k_shape[3] <= 7
+            and (len(pads) != 4 or (pads[0] == pads[2] and pads[1] == pads[3])))
+
+
+def prepare_dw_q4_weights(K):
+    """OIHW depthwise filters [C][1][kh][kw] -> [ceil(C/4)][kh*kw][4] with zero-padded quads (ConvQ4 w_layout=13).  The
+    returned array keeps the logical OIHW shape; its allocation is the packed size."""
+    _f32(K)
+    c, cin_g, kh, kw = K.shape
+    if cin_g != 1:
+        raise ValueError("depthwise filters have one input channel per group")
+    out = empty(((c + 3) // 4 * kh * kw * 4,), ctx=K.ctx)
+    _lib.call("pl_conv2d_prepare_dw_q4_f32", K.ctx.handle, K.ptr, c, kh, kw, out.ptr)
+    out.shape = K.shape
+    return out
+
+
 def winograd_q4_eligible(k_shape, group=1, strides=(1, 1), dilations=(1, 1), pads=(0, 0, 0, 0), **_):
     """3x3 / stride 1 / pad 1 / no dilation / no groups, Cin and Cout multiples of 4."""
     cout, cin_g, kh, kw = k_shape
@@ -224,7 +245,8 @@ def ConvQ4(xq, Kq, B=None, scale=None, shift=None, resq=None, group=1, strides=(
            dilations=(1, 1), pads=(0, 0, 0, 0), act=ACT_NONE, alpha=0.0, w_layout=2, **_):
     """layer.ConvFused on Q4 tensors: act((conv(x,K)+B)*scale + shift + res), all activations Q4.
     w_layout=2: Kq from prepare_q4_weights(); w_layout=4: Winograd filters from
-    prepare_winograd_q4_weights(); 6 row-packed stem, 7 staged / 9 fused F(4x4,3x3), 8 fused 1-D F(4,3)."""
+    prepare_winograd_q4_weights(); 6 row-packed stem, 7 staged / 9 fused F(4x4,3x3), 8 fused 1-D F(4,3), 13 depthwise
+    (prepare_dw_q4_weights)."""
     _f32(xq, Kq, B, scale, shift, resq)
     if w_layout == 6:
         # row-packed stem: the input is the reference's NCHW tensor, the output is Q4
@@ -266,6 +288,13 @@ def ConvQ4(xq, Kq, B=None, scale=None, shift=None, resq=None, group=1, strides=(
         if not w1d_q4_eligible(Kq.shape, group, strides, dilations, pads):
             raise ValueError("1-D winograd filters serve 3x3 / stride 1 / pad 1 / group 1 convs only")
         _lib.call("pl_conv2d_w1d4_q4_f32", xq.ctx.handle, xq.ptr, n, cin, h, w, Kq.ptr, cout, _ptr(B), y.ptr,
+                  _ptr(scale), _ptr(shift), _ptr(resq), int(act), float(alpha))
+        return y
+    if w_layout == 13:
+        if not dw_q4_eligible(Kq.shape, group, strides, dilations, pads):
+            raise ValueError("depthwise Q4 filters serve group == Cin == Cout convs with kh, kw <= 7 and symmetric pads")
+        _lib.call("pl_conv2d_dw_q4_f32", xq.ctx.handle, xq.ptr, n, cin, h, w, Kq.ptr, kh, kw, _ptr(B), y.ptr,
+                  strides[0], strides[1], dilations[0], dilations[1], pads[0], pads[1], pads[2], pads[3],
                   _ptr(scale), _ptr(shift), _ptr(resq), int(act), float(alpha))
         return y
     if w_layout == 11 and (h not in (7, 14, 21) or w not in (7, 14, 21)):
@@ -596,6 +625,18 @@ def ReLUQ4(xq):
     return xq
 
 
+def clip_q4_ok(c, min=0, max=1, **_):
+    """ClipQ4 keeps the zero padding of a partial last quad only when clip(0) == 0."""
+    return c % 4 == 0 or float(min) <= 0.0 <= float(max)
+
+
+def ClipQ4(xq, min=0, max=1):
+    """layer.Clip (layer.py:247-251): in place on the padded buffer like the reference's in-place numpy branch.  Only
+    scheduled where clip_q4_ok holds (ReLU6 = clip(0, 6) always does)."""
+    _lib.call("pl_unary_f32", xq.ctx.handle, xq.ptr, xq.ptr, xq.size, 6, float(min), float(max))
+    return xq
+
+
 def LeakyReLUQ4(xq, alpha=0.2):
     y = _like(xq)
     _lib.call("pl_leakyrelu_f32", xq.ctx.handle, xq.ptr, y.ptr, xq.size, float(alpha))
@@ -663,7 +704,7 @@ def UpConcatQ4(aq, k, bq, mode="nearest", axis=1):
 # kind -> Q4 implementation, for plan.assign_layouts (conv kinds are handled by the plan compiler)
 Q4_LAYERS = {"maxpool": MaxpoolQ4, "averagepool": AveragePoolQ4, "gap": GlobalAveragePoolQ4,
              "upsample": UpSampleQ4, "batchnorm": BatchNormQ4, "relu": ReLUQ4, "leakyrelu": LeakyReLUQ4,
-             "sigmoid": SigmoidQ4, "add": AddQ4, "concat": ConcatenateQ4}
+             "sigmoid": SigmoidQ4, "add": AddQ4, "concat": ConcatenateQ4, "clip": ClipQ4}
 
 
 def register(layer_map):
