@@ -211,6 +211,20 @@ int pl_conv2d_dw_q4_f32(pl_ctx *ctx, const float *xq, int N, int C, int H, int W
                         int sh, int sw, int dh, int dw, int pt, int pl, int pb, int pr,
                         const float *scale, const float *shift, const float *resq, int act,
                         double alpha);
+/* Transposed convs (ConvTranspose2d, filter [Cin][Cout][kh][kw], group 1, dilation 1) on Q4 tensors, by output
+ * phase: each of the sh*sw phases is a stride-1 conv of x with a ceil(kh/sh) x ceil(kw/sw) sub-filter, written to
+ * every sh-th row / sw-th column of y -- no zero-stuffed input.  Output Ho = (H-1)*sh - pt - pb + kh + oph (Wo
+ * alike); pads may be asymmetric up to the kernel reach (pt <= kh-1, pb <= kh-1+oph).  The fused tail is
+ * pl_conv2d_q4_f32's.  wq ("w_layout 14") from pl_conv2d_prepare_convt_q4_f32: [sh*sw][q][Cout][4] with
+ * q = tap*ceil(Cin/4) + cin/4 padded to a multiple of 8, pl_conv2d_convt_filter_elems floats. */
+int pl_conv2d_convt_filter_elems(int Cin, int Cout, int kh, int kw, int sh, int sw, size_t *elems);
+int pl_conv2d_prepare_convt_q4_f32(pl_ctx *ctx, const float *w, int Cin, int Cout, int kh, int kw,
+                                   int sh, int sw, float *out);
+int pl_conv2d_convt_q4_f32(pl_ctx *ctx, const float *xq, int N, int Cin, int H, int W,
+                           const float *wq, int Cout, int kh, int kw, const float *bias, float *yq,
+                           int sh, int sw, int dh, int dw, int pt, int pl, int pb, int pr, int oph,
+                           int opw, const float *scale, const float *shift, const float *resq,
+                           int act, double alpha);
 /* Winograd F(2x2,3x3) on Q4 tensors for 3x3 / stride 1 / pad 1 / group 1 convs with
  * Cin % 4 == 0 and Cout % 4 == 0: uq = [16][k-quad][Cout][4] filters made once per
  * model; float4 input/output transforms around one grouped 1x1 Q4 conv. */

@@ -78,6 +78,9 @@ SIGNATURES = {
                         + [_P, _P, _P, _I, c_double],
     "pl_conv2d_prepare_dw_q4_f32": [_P, _P, _I, _I, _I, _P],
     "pl_conv2d_dw_q4_f32": [_P, _P, _I, _I, _I, _I, _P, _I, _I, _P, _P] + [_I] * 8 + [_P, _P, _P, _I, c_double],
+    "pl_conv2d_convt_filter_elems": [_I] * 6 + [POINTER(c_size_t)],
+    "pl_conv2d_prepare_convt_q4_f32": [_P, _P] + [_I] * 6 + [_P],
+    "pl_conv2d_convt_q4_f32": [_P, _P, _I, _I, _I, _I, _P, _I, _I, _I, _P, _P] + [_I] * 10 + [_P, _P, _P, _I, c_double],
     "pl_conv2d_winograd_q4_filter_elems": [_I, _I, POINTER(c_size_t)],
     "pl_conv2d_prepare_winograd_q4_f32": [_P, _P, _I, _I, _P],
     "pl_conv2d_winograd_q4_f32": [_P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _I, c_double],

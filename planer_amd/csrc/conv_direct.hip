@@ -631,6 +631,9 @@ struct CfgInfo {
     void (*reduce4)(const ConvArgs, const float *, float *);
     bool ks;     // intra-workgroup K split (conv_ks_kernel.h): 1024 threads, 32x32 tile, no split-K plans
     void (*pair)(const ConvArgs, const ConvArgs);    // two convs on one input in one launch (conv_q4_pair_kernel), or null
+    // the transposed conv by output phase on this tile (convt_q4_kernel) and its split-K reduce, or null
+    void (*convt)(const ConvArgs);
+    void (*convt_reduce)(const ConvArgs, const float *, float *);
 };
 
 #define CFG_ENTRY(T, nm)                                                                                 \
@@ -644,10 +647,12 @@ struct CfgInfo {
 
 #define Q4_ENTRY(T, nm) \
     { nm, 2, T::BM, T::BN, T::BK, T::LDS_BYTES, conv_q4_kernel<T>, conv_q4_kernel<T>, \
-      reduce_tiles_q4_kernel<T::BM, T::BN>, reduce_tiles_q4_kernel<T::BM, T::BN> }
+      reduce_tiles_q4_kernel<T::BM, T::BN>, reduce_tiles_q4_kernel<T::BM, T::BN>, false, nullptr, \
+      convt_q4_kernel<T>, reduce_tiles_q4_kernel<T::BM, T::BN, true> }
 #define Q4P_ENTRY(T, nm) \
     { nm, 2, T::BM, T::BN, T::BK, T::LDS_BYTES, conv_q4_kernel<T>, conv_q4_kernel<T>, \
-      reduce_tiles_q4_kernel<T::BM, T::BN>, reduce_tiles_q4_kernel<T::BM, T::BN>, false, conv_q4_pair_kernel<T> }
+      reduce_tiles_q4_kernel<T::BM, T::BN>, reduce_tiles_q4_kernel<T::BM, T::BN>, false, conv_q4_pair_kernel<T>, \
+      convt_q4_kernel<T>, reduce_tiles_q4_kernel<T::BM, T::BN, true> }
 
 const CfgInfo kCfgs[] = {
     CFG_ENTRY(C128x128, "128x128"), CFG_ENTRY(C64x128, "64x128"), CFG_ENTRY(C128x64, "128x64"),
@@ -673,8 +678,10 @@ const CfgInfo kCfgs[] = {
 constexpr int kNumCfgs = sizeof(kCfgs) / sizeof(kCfgs[0]);
 constexpr int kLdsPerCu = 160 * 1024;
 
-// weight layouts: 0 OIHW (generic kernel), 1 tap-major, 2 Q4 (activations AND filter in quad form)
+// weight layouts: 0 OIHW (generic kernel), 1 tap-major, 2 Q4 (activations AND filter in quad form), 14 transposed conv by
+// output phase (Q4, convt_q4_launch)
 bool cfg_applies(const CfgInfo &ci, int layout, int cin_g, int q_pad = 1 << 20) {
+    if (layout == 14) return ci.convt != nullptr;
     if (ci.ks && (layout != 2 || (getenv("PLANER_HIP_KS") && atoi(getenv("PLANER_HIP_KS")) == 0))) return false;
     if (layout == 6) layout = 2;            // row-packed input: the channel-quad kernel with another gather
     if (ci.tap != layout) return false;
@@ -766,7 +773,7 @@ int launch_pass(pl_ctx *ctx, ConvArgs a, const CfgInfo &ci, bool avec, int tile_
         const int want = (kLdsPerCu / occ) & ~255;          // occ blocks fit, occ+1 do not
         if (want > lds && kLdsPerCu / (occ + 1) < want) lds = want;
     }
-    auto kern = kernel_of(ci, avec);
+    auto kern = a.ph_sh ? ci.convt : kernel_of(ci, avec);
     if (lds > 48 * 1024) {
         int rc = ensure_lds_attr((const void *)kern, lds);
         if (rc != PL_OK) return rc;
@@ -830,7 +837,7 @@ int run_plan(pl_ctx *ctx, const ConvArgs &a0, const Plan &pl, bool avec, float *
         const bool vec4 = ci.tap == 2 || (a.HoWo % 4 == 0 && (reinterpret_cast<uintptr_t>(y) & 15u) == 0 &&
                                           (!a.ep.res || (reinterpret_cast<uintptr_t>(a.ep.res) & 15u) == 0));
         const int rows = ci.tap == 2 ? REDUCE_Q4_QUADS * 4 : vec4 ? std::min(ci.bm, REDUCE_ROWS * 4) : REDUCE_ROWS;
-        hipLaunchKernelGGL(vec4 ? ci.reduce4 : ci.reduce, dim3((unsigned)tail, (unsigned)((ci.bm + rows - 1) / rows)),
+        hipLaunchKernelGGL(a.ph_sh ? ci.convt_reduce : vec4 ? ci.reduce4 : ci.reduce, dim3((unsigned)tail, (unsigned)((ci.bm + rows - 1) / rows)),
                            dim3(256), 0, ctx->stream, r, (const float *)ws, y);
         hipError_t le = hipGetLastError();
         if (le != hipSuccess) {
@@ -1049,6 +1056,78 @@ int dw_launch(pl_ctx *ctx, const float *x, int N, int C, int H, int W, const flo
     return PL_OK;
 }
 
+// How a conv of `layout` is run: the forced configuration (tests / tuning tools: split > 1 means split-K over all tiles), else
+// the plan remembered for `key` on this device, else the static choice -- measured first when autotuning and `may_tune`
+// (the timing runs write y, so y must alias no input).
+int plan_and_run(pl_ctx *ctx, int layout, const ConvArgs &a, const TuneKey &key, bool avec, float *y, bool may_tune) {
+    if (ctx->conv_cfg >= 0 && ctx->conv_cfg < kNumCfgs && cfg_applies(kCfgs[ctx->conv_cfg], layout, a.cin_g, a.Qpad)) {
+        const int s = ctx->conv_split_k > 0 ? ctx->conv_split_k : 1;
+        Plan pl{ctx->conv_cfg, s > 1 ? ctx->conv_t1 : (1 << 30), s, ctx->conv_occ};
+        return run_plan(ctx, a, pl, avec, y);
+    }
+    Plan plan{-1, 0, 1, 0};
+    bool have = false;
+    {
+        std::lock_guard<std::mutex> lk(g_tune_mu);
+        auto it = g_tune.find({ctx->device, key});
+        if (it != g_tune.end()) {
+            plan = it->second;
+            have = true;
+        }
+    }
+    if (!have) {
+        plan = choose_plan(ctx, layout, a);
+        PL_REQUIRE(plan.cfg >= 0, PL_EUNSUPPORTED, "conv2d: no kernel configuration applies");
+        const bool tune = ctx->autotune && !ctx->capturing && may_tune;
+        if (tune) {
+            plan = tune_plan(ctx, layout, a, avec, y, plan);
+            ++ctx->tune_misses;
+        }
+        if (tune || !ctx->autotune) {
+            std::lock_guard<std::mutex> lk(g_tune_mu);
+            g_tune[{ctx->device, key}] = plan;
+        }
+    }
+    return run_plan(ctx, a, plan, avec, y);
+}
+
+// A transposed conv (ConvTranspose2d: filter [Cin][Cout][kh][kw], dilation 1, group 1) by output phase, on Q4 tensors:
+// sh*sw stride-1 convs of x with th x tw sub-filters (th = ceil(kh/sh), tw = ceil(kw/sw); wq from
+// pl_conv2d_prepare_convt_q4_f32), one tile group per phase (convt_q4_kernel).  Per dimension the output is
+//   Ho = (H-1)*sh - pt - pb + kh + oph,   y[o] = sum_u x[q - u] * K[r + sh*u],  r = (o+pt) % sh, q = (o+pt) / sh,
+// so phase r's pixel i reads input rows i + pt/sh - (th-1) .. i + pt/sh (a stride-1 conv with pad th-1-pt/sh, which may be
+// negative) and lands on output row sh*(i + pt/sh) + r - pt.  Shapes are checked by the caller.
+int convt_q4_launch(pl_ctx *ctx, const float *x, int N, int Cin, int H, int W, const float *wq, int Cout, int kh, int kw,
+                    const float *bias, float *y, int sh, int sw, int pt, int pl, int Ho, int Wo, const float *scale,
+                    const float *shift, const float *res, int act, double alpha, const TuneKey &key) {
+    const int th = (kh + sh - 1) / sh, tw = (kw + sw - 1) / sw;
+    const int Hq = (Ho - 1 + pt) / sh - pt / sh + 1, Wq = (Wo - 1 + pl) / sw - pl / sw + 1;
+    const int cqg = (Cin + 3) / 4, q_tot = th * tw * cqg, q_pad = (q_tot + 7) / 8 * 8;
+    ConvArgs a;
+    memset(&a, 0, sizeof a);
+    a.x = x; a.w = wq; a.y = y;
+    a.N = N; a.Cin = Cin; a.H = H; a.W = W; a.Cout = Cout; a.Ho = Hq; a.Wo = Wq;
+    a.kh = th; a.kw = tw; a.sh = a.sw = a.dh = a.dw = 1; a.pt = th - 1 - pt / sh; a.pl = tw - 1 - pl / sw;
+    a.groups = sh * sw; a.cin_g = Cin; a.cout_g = Cout;
+    a.K = q_tot * 4;
+    a.cqg = cqg; a.Cq = cqg; a.Coq = (Cout + 3) / 4; a.Qtot = q_tot; a.Qpad = q_pad;
+    a.cols = N * Hq * Wq;
+    a.HoWo = Hq * Wq; a.HW = H * W;
+    a.y_bytes = (int)((size_t)N * a.Coq * Ho * Wo * 16);
+    a.x_bytes = (int)((size_t)N * cqg * H * W * 16); a.w_bytes = (int)((size_t)a.groups * q_pad * Cout * 16);
+    a.divKhw = FastDiv(th * tw); a.divKw = FastDiv(tw);
+    a.divHoWo = FastDiv(a.HoWo); a.divWo = FastDiv(Wq);
+    a.divMt = FastDiv(1); a.divCpt = FastDiv(1);
+    a.ep = make_epilogue(bias, scale, shift, res, act, alpha);
+    a.ph_sh = sh; a.ph_sw = sw; a.ph_oh = pt % sh; a.ph_ow = pl % sw; a.ph_Ho = Ho; a.ph_Wo = Wo;
+    const int rc = plan_and_run(ctx, 14, a, key, true, y, res != y && x != y);
+    if (rc == PL_OK) {
+        char buf[64];
+        snprintf(buf, sizeof buf, "convt-q4 phases=%dx%d taps=%dx%d ", sh, sw, th, tw);
+        ctx->last_plan = buf + ctx->last_plan;
+    }
+    return rc;
+}
 }  // namespace
 
 int plhip::conv_launch(pl_ctx *ctx, const float *x, int N, int Cin, int H, int W, const float *w, int Cout, int kh, int kw,
@@ -1236,38 +1315,9 @@ int plhip::conv_launch(pl_ctx *ctx, const float *x, int N, int Cin, int H, int W
     a.xcd_cols = ctx->xcd_cols_request;
     const bool avec = (a.K % 4 == 0) && ((reinterpret_cast<uintptr_t>(w) & 15u) == 0);
 
-    // forced configuration (tests / tuning tools): split > 1 means split-K over all tiles
-    if (ctx->conv_cfg >= 0 && ctx->conv_cfg < kNumCfgs && cfg_applies(kCfgs[ctx->conv_cfg], layout, a.cin_g, a.Qpad)) {
-        const int s = ctx->conv_split_k > 0 ? ctx->conv_split_k : 1;
-        Plan pl{ctx->conv_cfg, s > 1 ? ctx->conv_t1 : (1 << 30), s, ctx->conv_occ};
-        return run_plan(ctx, a, pl, avec, y);
-    }
     TuneKey key = {{layout, N, Cin, H, W, Cout, kh, kw, sh, sw, dh, dw, pt, pl, group, res != nullptr,
                     (scale != nullptr) * 2 + (bias != nullptr), act}};
-    Plan plan{-1, 0, 1, 0};
-    bool have = false;
-    {
-        std::lock_guard<std::mutex> lk(g_tune_mu);
-        auto it = g_tune.find({ctx->device, key});
-        if (it != g_tune.end()) {
-            plan = it->second;
-            have = true;
-        }
-    }
-    if (!have) {
-        plan = choose_plan(ctx, layout, a);
-        PL_REQUIRE(plan.cfg >= 0, PL_EUNSUPPORTED, "conv2d: no kernel configuration applies");
-        const bool tune = ctx->autotune && !ctx->capturing && res != y && x != y;
-        if (tune) {
-            plan = tune_plan(ctx, layout, a, avec, y, plan);
-            ++ctx->tune_misses;
-        }
-        if (tune || !ctx->autotune) {
-            std::lock_guard<std::mutex> lk(g_tune_mu);
-            g_tune[{ctx->device, key}] = plan;
-        }
-    }
-    return run_plan(ctx, a, plan, avec, y);
+    return plan_and_run(ctx, layout, a, key, avec, y, res != y && x != y);
 }
 
 namespace {
@@ -1863,6 +1913,61 @@ int pl_conv2d_dw_q4_f32(pl_ctx *ctx, const float *xq, int N, int C, int H, int W
                              make_epilogue(bias, scale, shift, resq, act, alpha), 4);
     PL_REQUIRE(rc != PL_EUNSUPPORTED, PL_EUNSUPPORTED, "pl_conv2d_dw_q4_f32: more than 65535 channel quads or images");
     return rc;
+}
+
+int pl_conv2d_convt_filter_elems(int Cin, int Cout, int kh, int kw, int sh, int sw, size_t *elems) {
+    PL_REQUIRE(elems && Cin > 0 && Cout > 0 && kh > 0 && kw > 0 && sh > 0 && sw > 0, PL_EINVAL,
+               "pl_conv2d_convt_filter_elems: bad argument");
+    const size_t q_tot = (size_t)((kh + sh - 1) / sh) * ((kw + sw - 1) / sw) * ((Cin + 3) / 4);
+    *elems = (size_t)sh * sw * ((q_tot + 7) / 8 * 8) * Cout * 4;
+    return PL_OK;
+}
+
+int pl_conv2d_prepare_convt_q4_f32(pl_ctx *ctx, const float *w, int Cin, int Cout, int kh, int kw, int sh, int sw, float *out) {
+    PL_REQUIRE(ctx && w && out, PL_EINVAL, "pl_conv2d_prepare_convt_q4_f32: null pointer");
+    PL_REQUIRE(Cin > 0 && Cout > 0 && kh > 0 && kw > 0 && sh > 0 && sw > 0, PL_EINVAL, "pl_conv2d_prepare_convt_q4_f32: bad shape");
+    PL_REQUIRE((reinterpret_cast<uintptr_t>(out) & 15u) == 0, PL_EINVAL, "pl_conv2d_prepare_convt_q4_f32: unaligned output");
+    size_t elems = 0;
+    pl_conv2d_convt_filter_elems(Cin, Cout, kh, kw, sh, sw, &elems);
+    PL_REQUIRE(elems < (1ull << 29) && (size_t)Cin * Cout * kh * kw < (1ull << 31), PL_EUNSUPPORTED, "filter too large");
+    const int th = (kh + sh - 1) / sh, tw = (kw + sw - 1) / sw, cqg = (Cin + 3) / 4, q_tot = th * tw * cqg;
+    const int q_pad = (q_tot + 7) / 8 * 8;
+    const size_t total = elems / 4;                             // float4s
+    CtxGuard g(ctx);
+    const unsigned blocks = (unsigned)std::min<size_t>((total + 255) / 256, 2048);
+    pack_filter_convt_q4_kernel<<<blocks, 256, 0, ctx->stream>>>(w, out, (unsigned)total, Cin, Cout, kh, kw, sh, sw, th, tw, cqg,
+                                                                q_tot, q_pad, FastDiv(Cout), FastDiv(q_pad), FastDiv(cqg),
+                                                                FastDiv(tw));
+    PL_LAUNCH_CHECK();
+    return PL_OK;
+}
+
+int pl_conv2d_convt_q4_f32(pl_ctx *ctx, const float *xq, int N, int Cin, int H, int W, const float *wq, int Cout, int kh, int kw,
+                           const float *bias, float *yq, int sh, int sw, int dh, int dw, int pt, int pl, int pb, int pr, int oph,
+                           int opw, const float *scale, const float *shift, const float *resq, int act, double alpha) {
+    PL_REQUIRE(ctx && xq && wq && yq, PL_EINVAL, "pl_conv2d_convt_q4_f32: null pointer");
+    PL_REQUIRE(((reinterpret_cast<uintptr_t>(xq) | reinterpret_cast<uintptr_t>(yq) | reinterpret_cast<uintptr_t>(wq) |
+                 reinterpret_cast<uintptr_t>(resq)) & 15u) == 0, PL_EINVAL, "pl_conv2d_convt_q4_f32: Q4 tensors must be 16-byte aligned");
+    PL_REQUIRE(N >= 0 && Cin > 0 && H > 0 && W > 0 && Cout > 0 && kh > 0 && kw > 0, PL_EINVAL, "pl_conv2d_convt_q4_f32: bad shape");
+    PL_REQUIRE(sh > 0 && sw > 0 && pt >= 0 && pl >= 0 && pb >= 0 && pr >= 0 && oph >= 0 && opw >= 0, PL_EINVAL,
+               "pl_conv2d_convt_q4_f32: bad parameter");
+    PL_REQUIRE(dh == 1 && dw == 1, PL_EUNSUPPORTED, "pl_conv2d_convt_q4_f32: dilation 1 only");
+    // pads within the kernel reach: the zero-stuffed form of the reference (layer.py:28-34) keeps a non-negative border
+    PL_REQUIRE(pt <= kh - 1 && pl <= kw - 1 && pb <= kh - 1 + oph && pr <= kw - 1 + opw, PL_EUNSUPPORTED,
+               "pl_conv2d_convt_q4_f32: pads beyond the kernel reach");
+    PL_REQUIRE(act >= 0 && (act & 15) <= 2 && (act & ~31) == 0, PL_EINVAL, "pl_conv2d_convt_q4_f32: bad activation code");
+    PL_REQUIRE(H < 16384 && W < 16384 && kh < 16384 && kw < 16384 && sh < 16384 && sw < 16384, PL_EUNSUPPORTED,
+               "pl_conv2d_convt_q4_f32: extent above 16383");
+    const long long Ho = (long long)(H - 1) * sh - pt - pb + kh + oph, Wo = (long long)(W - 1) * sw - pl - pr + kw + opw;
+    PL_REQUIRE(Ho > 0 && Wo > 0 && Ho < 16384 && Wo < 16384, PL_EINVAL, "pl_conv2d_convt_q4_f32: output %lld x %lld", Ho, Wo);
+    const size_t xq_elems = (size_t)N * ((Cin + 3) / 4) * 4 * H * W, yq_elems = (size_t)N * ((Cout + 3) / 4) * 4 * Ho * Wo;
+    PL_REQUIRE(xq_elems < (1ull << 29) && yq_elems < (1ull << 29), PL_EUNSUPPORTED, "pl_conv2d_convt_q4_f32: tensor above 2 GiB");
+    if (N == 0) return PL_OK;
+    CtxGuard g(ctx);
+    TuneKey key = {{14, N, Cin, H, W, Cout, kh, kw, sh, sw, pt, pl, pb, pr, oph + 1024 * opw, resq != nullptr,
+                    (scale != nullptr) * 2 + (bias != nullptr), act}};
+    return convt_q4_launch(ctx, xq, N, Cin, H, W, wq, Cout, kh, kw, bias, yq, sh, sw, pt, pl, (int)Ho, (int)Wo, scale, shift,
+                           resq, act, alpha, key);
 }
 
 static int q4_convert(pl_ctx *ctx, const float *x, float *y, int N, int C, int HW, bool to_q4) {

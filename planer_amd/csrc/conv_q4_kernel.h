@@ -47,11 +47,23 @@ struct QuadCfg {
     static constexpr int MIN_WAVES = 512 / ((REGS_EST + 7) / 8 * 8) > 5 ? 5 : 512 / ((REGS_EST + 7) / 8 * 8);
 };
 
+// Transposed conv by output phase (ConvArgs::ph_*): column pixel `pix` of phase g's grid -> its output pixel, or -1 when it
+// falls outside the output (the phase grids cover a little more than the output where pads and output_padding clip it)
+__device__ __forceinline__ int phase_pixel(const ConvArgs &p, unsigned g, unsigned pix) {
+    unsigned i, j;
+    p.divWo.divmod(pix, i, j);
+    const unsigned rh = g / (unsigned)p.ph_sw, rw = g - rh * (unsigned)p.ph_sw;
+    const int oh = (int)(i * (unsigned)p.ph_sh + rh) - p.ph_oh, ow = (int)(j * (unsigned)p.ph_sw + rw) - p.ph_ow;
+    return ((unsigned)oh < (unsigned)p.ph_Ho && (unsigned)ow < (unsigned)p.ph_Wo) ? oh * p.ph_Wo + ow : -1;
+}
+
 // One wave's accumulators -> Q4 output (fused pass) or this (split, tile)'s slab, laid out
 // [row/4][BN][4] so both sides move float4s.  Fused pass: `prm` points at the tile's per-row
 // parameters in LDS ([3][BM]: bias, scale, shift -- fetched from HBM when the kernel started, so
 // nothing here waits on them); every residual quad is requested before the first is needed.
-template <int BM, int BN, int TM, int TN, int WTM, int WTN>
+// PH: transposed conv by output phase -- every phase writes the same output channels (no group offset), at the pixels
+// phase_pixel gives; the host guarantees a buffer-addressed tail (y_bytes) there.
+template <int BM, int BN, int TM, int TN, int WTM, int WTN, bool PH = false>
 __device__ __forceinline__ void store_tile_q4(const ConvArgs &p, const TileCoord &tc, f32x16 (&acc)[TM][TN], int wm,
                                               int wn, int lane, const float *prm) {
     const int l31 = lane & 31, lhi = lane >> 5;
@@ -72,7 +84,9 @@ __device__ __forceinline__ void store_tile_q4(const ConvArgs &p, const TileCoord
     float4 *y4 = reinterpret_cast<float4 *>(p.y);
     const float4 *res4 = reinterpret_cast<const float4 *>(p.ep.res);
     const float4 *prm4 = reinterpret_cast<const float4 *>(prm);
-    if (p.y_bytes) {
+    const unsigned gch = PH ? 0u : tc.g;                              // group whose channels this tile writes
+    const unsigned ohw = PH ? (unsigned)(p.ph_Ho * p.ph_Wo) : (unsigned)p.HoWo;     // output pixels per channel quad
+    if (PH || p.y_bytes) {
         // Branch-free tail (outputs under 2 GiB): residual and y go through buffer descriptors whose range check
         // drops lanes outside the tensor -- a predicated plain load / store costs a branch and a wait per element.
         // All residual quads of a 32-row block are in flight before the first is used.
@@ -88,7 +102,12 @@ __device__ __forceinline__ void store_tile_q4(const ConvArgs &p, const TileCoord
             ck[b] = jc < p.cols;
             unsigned n, pix;
             p.divHoWo.divmod((unsigned)(ck[b] ? jc : 0), n, pix);
-            ob[b] = (n * (unsigned)p.Coq + (unsigned)(((int)tc.g * p.cout_g + tc.m0 + wm * WTM) >> 2)) * (unsigned)p.HoWo + pix;
+            if constexpr (PH) {
+                const int op = phase_pixel(p, tc.g, pix);
+                ck[b] = ck[b] && op >= 0;
+                pix = (unsigned)(op >= 0 ? op : 0);
+            }
+            ob[b] = (n * (unsigned)p.Coq + (unsigned)(((int)gch * p.cout_g + tc.m0 + wm * WTM) >> 2)) * ohw + pix;
         }
 #pragma unroll
         for (int a = 0; a < TM; ++a) {
@@ -100,7 +119,7 @@ __device__ __forceinline__ void store_tile_q4(const ConvArgs &p, const TileCoord
                 for (int b = 0; b < TN; ++b) {
                     const int Rl = a * 32 + 8 * rq + 4 * lhi;
                     const bool ok = ck[b] && tc.m0 + wm * WTM + Rl < p.cout_g;
-                    off[rq][b] = ok ? (int)((ob[b] + (unsigned)(Rl >> 2) * (unsigned)p.HoWo) << 4) : OOB;
+                    off[rq][b] = ok ? (int)((ob[b] + (unsigned)(Rl >> 2) * ohw) << 4) : OOB;
                     rs[rq][b] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rrsrc, off[rq][b], 0, 0));
                 }
 #pragma unroll
@@ -120,6 +139,7 @@ __device__ __forceinline__ void store_tile_q4(const ConvArgs &p, const TileCoord
         }
         return;
     }
+    if constexpr (PH) return;
     // quad index of (first row of the wave tile, this lane's pixel); < 2^29 (checked by the host)
     unsigned obase[TN];
     bool cok[TN];
@@ -166,7 +186,8 @@ __device__ __forceinline__ void store_tile_q4(const ConvArgs &p, const TileCoord
 // Sum the split-K slabs ([row/4][BN][4]) of tiles [tile_offset, +tile_count) and
 // write Q4 with the fused tail.  blockIdx.x = tile, blockIdx.y = band of row quads.
 constexpr int REDUCE_Q4_QUADS = 8;   // row quads per block: BN * 8 float4 per 256 threads
-template <int BM, int BN>
+// PH: the transposed-conv phase form (see store_tile_q4).
+template <int BM, int BN, bool PH = false>
 __global__ void __launch_bounds__(256) reduce_tiles_q4_kernel(const ConvArgs p, const float *slabs, float *y) {
     const unsigned local = blockIdx.x;
     const unsigned gt = local + (unsigned)p.tile_offset;
@@ -180,11 +201,19 @@ __global__ void __launch_bounds__(256) reduce_tiles_q4_kernel(const ConvArgs p, 
     if (jc >= p.cols) return;
     unsigned n, pix;
     p.divHoWo.divmod((unsigned)jc, n, pix);
-    const size_t obase = (size_t)n * p.Coq * p.HoWo + pix;
+    const unsigned gch = PH ? 0u : g;
+    size_t ohw = (size_t)p.HoWo;
+    if constexpr (PH) {
+        const int op = phase_pixel(p, g, pix);
+        if (op < 0) return;
+        pix = (unsigned)op;
+        ohw = (size_t)p.ph_Ho * p.ph_Wo;
+    }
+    const size_t obase = (size_t)n * p.Coq * ohw + pix;
     const size_t sstride = (size_t)p.tile_count * (BM * BN / 4);      // float4 units
     const float4 *sp = reinterpret_cast<const float4 *>(slabs) + (size_t)local * (BM * BN / 4) + cl;
     float4 *y4 = reinterpret_cast<float4 *>(y);
-    const int cend = (int)g * p.cout_g + p.cout_g;
+    const int cend = (int)gch * p.cout_g + p.cout_g;
 #pragma unroll
     for (int i = 0; i < REDUCE_Q4_QUADS / RPP; ++i) {
         const int rq = blockIdx.y * REDUCE_Q4_QUADS + i * RPP + threadIdx.x / BN;
@@ -195,8 +224,8 @@ __global__ void __launch_bounds__(256) reduce_tiles_q4_kernel(const ConvArgs p, 
                 const float4 w = sp[z * sstride + (size_t)rq * BN];
                 v.x += w.x; v.y += w.y; v.z += w.z; v.w += w.w;
             }
-            const int c0 = (int)g * p.cout_g + R;
-            const size_t idx4 = obase + (size_t)(c0 >> 2) * p.HoWo;
+            const int c0 = (int)gch * p.cout_g + R;
+            const size_t idx4 = obase + (size_t)(c0 >> 2) * ohw;
             float bs[4], sc[4], sh[4];
 #pragma unroll
             for (int e = 0; e < 4; ++e) load_chan_params(p.ep, min(c0 + e, cend - 1), bs[e], sc[e], sh[e]);
@@ -208,7 +237,9 @@ __global__ void __launch_bounds__(256) reduce_tiles_q4_kernel(const ConvArgs p, 
     }
 }
 
-template <class C>
+// PH: a transposed conv by output phase (convt_q4_kernel): tile group g = phase, with its own sub-filter (g*Qpad k-quads
+// in) over ALL input channels, writing all output channels at the phase's pixels.
+template <class C, bool PH = false>
 __device__ __forceinline__ void conv_q4_body(const ConvArgs &p, unsigned bid = blockIdx.x, unsigned nblk = gridDim.x) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float *As = smem;                         // [2][KG][BM][4]
@@ -221,6 +252,7 @@ __device__ __forceinline__ void conv_q4_body(const ConvArgs &p, unsigned bid = b
 
     const TileCoord tc = tile_coord<C::BM, C::BN>(p, bid, nblk);
     const unsigned g = tc.g;
+    const int gch = PH ? 0 : (int)g;                           // group of the input / output channels
     const int m0 = tc.m0, col0 = tc.col0;
     const int split = blockIdx.y;
     const int total_chunks = (p.Qtot + C::KG - 1) / C::KG;
@@ -230,7 +262,7 @@ __device__ __forceinline__ void conv_q4_body(const ConvArgs &p, unsigned bid = b
     // per-row epilogue parameters: requested now, parked in LDS after the K loop
     float prm_b = 0.f, prm_sc = 1.f, prm_sh = 0.f;
     if (p.splits <= 1 && tid < C::BM)
-        load_chan_params(p.ep, (int)g * p.cout_g + min(m0 + tid, p.cout_g - 1), prm_b, prm_sc, prm_sh);
+        load_chan_params(p.ep, gch * p.cout_g + min(m0 + tid, p.cout_g - 1), prm_b, prm_sc, prm_sh);
 
     // ---- B: thread -> (pixel column jl, k-quad kg0 + pass*KG_PER_PASS) ----------
     // for BN >= 64 the k-quad index is wave-uniform: its tap / channel arithmetic runs on the SALU
@@ -247,7 +279,7 @@ __device__ __forceinline__ void conv_q4_body(const ConvArgs &p, unsigned bid = b
         p.divWo.divmod(pix, ho, wo);
         hbase = (int)ho * p.sh - p.pt;
         wbase = (int)wo * p.sw - p.pl;
-        cbase = ((int)n * p.Cq + (int)g * p.cqg) * p.HW + hbase * p.W + wbase;     // in quads
+        cbase = ((int)n * p.Cq + gch * p.cqg) * p.HW + hbase * p.W + wbase;     // in quads
         j_n = (int)n;
     }
     constexpr int OOB = (int)0x80000000;
@@ -468,13 +500,23 @@ __device__ __forceinline__ void conv_q4_body(const ConvArgs &p, unsigned bid = b
         }
         __syncthreads();
     }
-    store_tile_q4<C::BM, C::BN, C::TM, C::TN, C::WTM, C::WTN>(p, tc, acc, wm, wn, lane, smem);
+    store_tile_q4<C::BM, C::BN, C::TM, C::TN, C::WTM, C::WTN, PH>(p, tc, acc, wm, wn, lane, smem);
 }
 
 template <class C>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(C::MIN_WAVES)))
 conv_q4_kernel(const ConvArgs p) {
     conv_q4_body<C>(p);
+}
+
+// Transposed conv by output phase ("sub-pixel" decomposition, convt_q4_launch in conv_direct.hip): output pixel o of a
+// stride-s transposed conv is  sum_u x[(o+p)/s - u] * K[(o+p)%s + s*u]  per dimension, i.e. each of the sh*sw phases is
+// a stride-1 conv of the ORIGINAL x with a ceil(kh/sh) x ceil(kw/sw) sub-filter, written to every s-th output pixel --
+// no zero-stuffed input and no multiply by a stuffed zero.  The phases are the tile groups of one launch.
+template <class C>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(C::MIN_WAVES)))
+convt_q4_kernel(const ConvArgs p) {
+    conv_q4_body<C, true>(p);
 }
 
 // Two convolutions that read the SAME input in one launch: workgroups [0, pa.tile_count) run conv a, the rest conv b (both
@@ -512,6 +554,37 @@ __global__ void __launch_bounds__(256) pack_filter_q4_kernel(const float *w, flo
             if (left > 3) v.w = src[3 * khw];
         }
         reinterpret_cast<float4 *>(out)[i] = v;
+    }
+}
+
+// ConvTranspose filter [Cin][Cout][kh][kw] -> per output phase ph = (rh, rw) a th x tw stride-1 sub-filter in the
+// k-quad-major form of pack_filter_q4_kernel: wq[ph][q][co][4], q = (a*tw + b)*cqg + cin/4 holds
+// K[cin][co][rh + sh*(th-1-a)][rw + sw*(tw-1-b)] -- zero where that tap lies beyond the filter, in padding lanes and quads.
+__global__ void __launch_bounds__(256) pack_filter_convt_q4_kernel(const float *w, float *out, unsigned total, int Cin,
+                                                                   int Cout, int kh, int kw, int sh, int sw, int th, int tw,
+                                                                   int cqg, int Qtot, int Qpad, FastDiv divCo,
+                                                                   FastDiv divQpad, FastDiv divCqg, FastDiv divTw) {
+    const unsigned stride = gridDim.x * 256;
+    for (unsigned i = blockIdx.x * 256 + threadIdx.x; i < total; i += stride) {   // i = (ph*Qpad + q)*Cout + co
+        unsigned r, co, ph, q;
+        divCo.divmod(i, r, co);
+        divQpad.divmod(r, ph, q);
+        float v[4] = {0.f, 0.f, 0.f, 0.f};
+        if ((int)q < Qtot) {
+            unsigned tap, cq, a, b;
+            divCqg.divmod(q, tap, cq);
+            divTw.divmod(tap, a, b);
+            const int rh = (int)ph / sw, rw = (int)ph % sw;
+            const int ky = rh + sh * (th - 1 - (int)a), kx = rw + sw * (tw - 1 - (int)b);
+            if (ky < kh && kx < kw) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int cin = (int)cq * 4 + e;
+                    if (cin < Cin) v[e] = w[(((size_t)cin * Cout + co) * kh + ky) * kw + kx];
+                }
+            }
+        }
+        reinterpret_cast<float4 *>(out)[i] = make_float4(v[0], v[1], v[2], v[3]);
     }
 }
 

@@ -38,6 +38,10 @@ struct ConvArgs {
                       // wrote a column block of the grouped GEMM's input also reads it (Winograd hand-offs, wino4_gemm_launch)
     FastDiv divKhw, divKw, divHoWo, divWo, divMt, divCpt;
     Epilogue ep;
+    // Transposed conv by output phase (convt_q4_kernel) only, else 0: the tile group g is the output phase
+    // (g / ph_sw, g % ph_sw), and pixel (i, j) of the Ho x Wo phase grid lands on output pixel
+    // (ph_sh*i + g/ph_sw - ph_oh, ph_sw*j + g%ph_sw - ph_ow) of the ph_Ho x ph_Wo output, or nowhere
+    int ph_sh, ph_sw, ph_oh, ph_ow, ph_Ho, ph_Wo;
 };
 // blockIdx.x -> (group, m-tile, n-tile).  XCD-aware: the 8 XCDs (private L2s)
 // each walk a contiguous range of tiles, M-tiles fastest, so workgroups that

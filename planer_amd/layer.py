@@ -13,6 +13,8 @@ Every kind of the reference's table (layer.py:262-281) is here; an unknown
 kind raises KeyError in Net like the reference (net.py:15), and inputs a kernel
 does not cover raise NotImplementedError instead of silently running on the CPU.
 """
+import ctypes
+
 import numpy
 
 from . import _lib
@@ -791,10 +793,86 @@ def Split(x, split=None, axis=0):
     return outs
 
 
+def convt_phase_eligible(k_shape, group=1, strides=(2, 2), dilations=(1, 1), pads=(0, 0, 0, 0), output_padding=(0, 0), **_):
+    """A transposed conv the phase-decomposed kernel runs (pl_conv2d_convt_q4_f32): 4-D filter [Cin][Cout][kh][kw], group 1,
+    dilation 1, pads within the kernel reach.  Any stride, kh != kw, asymmetric pads and output_padding."""
+    if len(k_shape) != 4 or int(group) != 1 or [int(d) for d in dilations] != [1, 1] or len(list(pads)) != 4:
+        return False
+    kh, kw = k_shape[2:]
+    p, op = [int(v) for v in pads], [int(v) for v in output_padding]
+    return min(int(s) for s in strides) >= 1 and min(kh - 1 - p[0], kh - 1 - p[2] + op[0], kw - 1 - p[1], kw - 1 - p[3] + op[1]) >= 0
+
+
+def prepare_convt_weights(K, strides=(2, 2)):
+    """ConvTranspose filters [Cin][Cout][kh][kw] -> one stride-1 sub-filter per output phase in the channel-quad form
+    (w_layout=14, pl_conv2d_prepare_convt_q4_f32): done once per model by Net's plan compiler.  The returned array keeps the
+    logical shape; its allocation is the packed size, which depends on the strides."""
+    _f32(K)
+    cin, cout, kh, kw = K.shape
+    sh, sw = [int(v) for v in strides]
+    elems = ctypes.c_size_t()
+    _lib.call("pl_conv2d_convt_filter_elems", cin, cout, kh, kw, sh, sw, ctypes.byref(elems))
+    out = empty((elems.value,), ctx=K.ctx)
+    _lib.call("pl_conv2d_prepare_convt_q4_f32", K.ctx.handle, K.ptr, cin, cout, kh, kw, sh, sw, out.ptr)
+    out.shape = K.shape
+    return out
+
+
+def convt_out_hw(h, w, kh, kw, strides, pads, output_padding):
+    """Output extent of the reference's zero-stuffed form (layer.py:28-34) at dilation 1."""
+    return ((h - 1) * int(strides[0]) - int(pads[0]) - int(pads[2]) + kh + int(output_padding[0]),
+            (w - 1) * int(strides[1]) - int(pads[1]) - int(pads[3]) + kw + int(output_padding[1]))
+
+
+def convt_q4_call(xq, Kp, B, yq, scale, shift, resq, strides, pads, output_padding, act, alpha):
+    """pl_conv2d_convt_q4_f32 on channel-quad buffers: xq [N][ceil(Cin/4)][H][W][4] -> yq, Kp from prepare_convt_weights."""
+    n, _, h, w, _ = xq.shape
+    cin, cout, kh, kw = Kp.shape
+    _lib.call("pl_conv2d_convt_q4_f32", xq.ctx.handle, xq.ptr, n, cin, h, w, Kp.ptr, cout, kh, kw, _ptr(B), yq.ptr,
+              int(strides[0]), int(strides[1]), 1, 1, int(pads[0]), int(pads[1]), int(pads[2]), int(pads[3]),
+              int(output_padding[0]), int(output_padding[1]), _ptr(scale), _ptr(shift), _ptr(resq), int(act), float(alpha))
+
+
+def ConvTransposeFused(x, K, B=None, scale=None, shift=None, res=None, strides=(2, 2), dilations=(1, 1), pads=(0, 0, 0, 0),
+                       output_padding=(0, 0), group=1, act=ACT_NONE, alpha=0.0, w_layout=0):
+    """ConvTranspose2d with BatchNorm / Add / (Leaky)ReLU folded into its epilogue, NCHW in and out:
+    act((convtranspose(x,K)+B)*scale + shift + res).  The phase-decomposed kernel reads channel quads, so x (and res) are
+    converted on the way in and y on the way out.  w_layout=14: K holds prepare_convt_weights() bytes for these strides;
+    otherwise the filter is prepared here.  Emitted by Net's plan compiler; not a reference op."""
+    _f32(x, K, B, scale, shift, res)
+    if not convt_phase_eligible(K.shape, group, strides, dilations, pads, output_padding):
+        raise ValueError("phase-decomposed convtranspose: group 1, dilation 1 and pads within the kernel reach only")
+    n, cin, h, w = x.shape
+    if K.shape[0] != cin:
+        raise ValueError("convtranspose: weight %s does not match input %s" % (K.shape, x.shape))
+    cout, kh, kw = K.shape[1:]
+    ho, wo = convt_out_hw(h, w, kh, kw, strides, pads, output_padding)
+    y = empty((n, cout, ho, wo), ctx=x.ctx)
+    if res is not None and tuple(res.shape) != y.shape:
+        raise ValueError("fused residual shape %s != convtranspose output %s" % (res.shape, y.shape))
+    if not y.size:
+        return y
+    Kp = K if int(w_layout) == 14 else prepare_convt_weights(K, strides)
+
+    def quads(a, c, hh, ww):
+        q = empty((a.shape[0], (c + 3) // 4, hh, ww, 4), ctx=x.ctx)
+        if q.size:
+            _lib.call("pl_nchw_to_q4_f32", x.ctx.handle, a.ptr, q.ptr, a.shape[0], c, hh * ww)
+        return q
+    xq = quads(x, cin, h, w)
+    resq = quads(res, cout, ho, wo) if res is not None else None
+    yq = empty((n, (cout + 3) // 4, ho, wo, 4), ctx=x.ctx)
+    convt_q4_call(xq, Kp, B, yq, scale, shift, resq, strides, pads, output_padding, act, alpha)
+    _lib.call("pl_q4_to_nchw_f32", x.ctx.handle, yq.ptr, y.ptr, n, cout, ho * wo)
+    return y
+
+
 def ConvTranspose2d(x, K, B=None, strides=[2, 2], dilations=[1, 1], pads=[0, 0, 0, 0], output_padding=[0, 0],
                     group=1):
-    """layer.ConvTranspose2d (layer.py:28-34): scatter x into a zero-stuffed buffer (one strided-map
-    launch), flip + transpose the filter (one launch), then the stride-1 MFMA convolution."""
+    """layer.ConvTranspose2d (layer.py:28-34).  Dilation 1: the phase-decomposed kernel (ConvTransposeFused) -- each output
+    phase is a stride-1 conv of x itself, so nothing multiplies a stuffed zero.  Dilation > 1: the reference's own form,
+    scatter x into a zero-stuffed buffer (one strided-map launch), flip + transpose the filter (one launch), then the
+    stride-1 MFMA convolution."""
     _f32(x, K, B)
     if group != 1:
         raise NotImplementedError("convtranspose with group > 1: the reference's filter transpose is only "
@@ -807,6 +885,8 @@ def ConvTranspose2d(x, K, B=None, strides=[2, 2], dilations=[1, 1], pads=[0, 0, 
     low_w, high_w = (kw - 1) * d2 - pads[1], (kw - 1) * d2 - pads[3] + output_padding[1]
     if min(low_h, high_h, low_w, high_w) < 0:
         raise NotImplementedError("convtranspose: pads larger than the dilated kernel reach are not on the HIP path")
+    if convt_phase_eligible(K.shape, group, strides, dilations, pads, output_padding):
+        return ConvTransposeFused(x, K, B, strides=strides, pads=pads, output_padding=output_padding)
     bh, bw = (h - 1) * s1 + low_h + high_h + 1, (w - 1) * s2 + low_w + high_w + 1
     buf = _strided_map(x, [n, c, bh, bw], _contig_strides(x.shape), [0, 0, -low_h, -low_w], [1, 1, 1, 1],
                        div=[1, 1, s1, s2], extent=[n, c, h, w])
@@ -1132,7 +1212,7 @@ layer_map = {"dense": Dense, "conv": Conv2d, "relu": ReLU, "leakyrelu": LeakyReL
              "erf": Erf, "instancenormalization": InstanceNormalization,
              "scatternd": Scatternd, "nonzero": NonZero, "topk": TopK, "lstm": LSTM,
              # plan-compiler internal
-             "conv_fused": ConvFused}
+             "conv_fused": ConvFused, "convt_fused": ConvTransposeFused}
 # integer shape arithmetic: the same kinds, evaluated on host mirrors when no activation is involved
 for _k, _ref in (("add", lambda a, b: a + b), ("sub", lambda a, b: a - b), ("mul", lambda a, b: a * b),
                  ("div", lambda a, b: a / b), ("concat", lambda *xs, axis=0: numpy.concatenate(xs, axis=axis)),

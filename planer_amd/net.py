@@ -42,7 +42,8 @@ W_LAYOUT_NAMES = {0: "igemm-nchw", 1: "tap-nchw", 2: "direct-q4 (conv_q4_kernel)
                   9: "wf4 fused F(4x4,3x3) (conv_wf4_kernel)", 10: "stem + maxpool (conv_stem_pool_kernel)",
                   11: "wino43-q4 (mixed F(4,3) x F(3,3) tiles: transforms + 121 grouped conv_q4_kernel)",
                   12: "stem + maxpool (conv_stem_pool_kernel)",          # (the kernel reads the NCHW batch itself)
-                  13: "depthwise-q4 (conv_dw_kernel)"}
+                  13: "depthwise-q4 (conv_dw_kernel)",
+                  14: "convt-q4 (phase-decomposed convt_q4_kernel)"}
 
 
 def _as_list(v):
@@ -445,7 +446,7 @@ class Net:
                 if profile:                                  # ONE marker per step boundary: step time = marker to marker
                     events.append((name, obj.name, hip.Event(self.ctx).record()))
                 if record is not None and obj.name in ("conv", "conv_fused", "conv_q4", "dense", "matmul", "wino4_gemm", "wino43_gemm",
-                                                       "conv_q4_pair", "conv_pool_q4", "conv1x1_wino_in"):
+                                                       "conv_q4_pair", "conv_pool_q4", "conv1x1_wino_in", "convt_q4", "convt_fused"):
                     lay = obj.para().get("w_layout", 2 if obj.name in ("conv_q4_pair", "conv1x1_wino_in") else 0) if obj.name != "conv" else 0
                     lname = name
                     if obj.name in ("wino4_gemm", "wino43_gemm"):       # the GEMM stage of a staged Winograd conv
@@ -546,6 +547,16 @@ class Net:
                                         13: lambda: _q4.prepare_dw_q4_weights(K)}[lay]()
                 srcs[1] = key
                 out_body[name] = [name, "conv_q4", dict(entry[2], w_layout=lay)]
+            elif (entry[1] in ("convt_q4", "convt_fused", "convtranspose") and len(srcs) >= 2 and srcs[1] in wmap
+                    and _q4.convt_q4_eligible(wmap[srcs[1]].shape, **entry[2])):
+                # transposed convs: the per-phase sub-filters are made once per model (w_layout 14), not on every call
+                strides = [int(v) for v in entry[2].get("strides", (2, 2))]
+                key = "%s@convt%dx%d" % (srcs[1], strides[0], strides[1])
+                if key not in self._extra:
+                    self._extra[key] = _q4.prepare_convt_q4_weights(wmap[srcs[1]], strides)
+                srcs[1] = key
+                kind = "convt_q4" if entry[1] == "convt_q4" else "convt_fused"
+                out_body[name] = [name, kind, dict(entry[2], w_layout=14)]
             elif entry[1] in ("conv", "conv_fused") and len(srcs) >= 2 and srcs[1] in wmap:
                 K = wmap[srcs[1]]
                 if K.ndim == 4 and K.dtype == numpy.float32 and K.shape[1] % 16 == 0:

@@ -6,12 +6,16 @@ MI355X the HBM-bound layers that follow a convolution -- folded BatchNorm
 (layer.py:44-51) -- cost more than the bytes they compute on, so the plan
 folds each chain  conv -> batchnorm -> [add] -> [relu|leakyrelu] -> [add]  into
 the conv kernel's epilogue (`conv_fused`; the residual goes before the
-activation in ResNet's blocks and after it in YOLO-v3's, never both).  A link is absorbed only when the
+activation in ResNet's blocks and after it in YOLO-v3's, never both).  A
+transposed conv that the phase-decomposed kernel runs heads the same chains
+(`convt_fused`: a U-Net's up-step followed by BatchNorm / ReLU).  A link is absorbed only when the
 intermediate tensor has exactly one reader and one writer, so nothing a user
 could observe disappears; the fused step sits where the LAST link of its
 chain was, so a residual operand produced after the conv is still available.
 """
 import os
+
+from .layer import convt_phase_eligible
 
 ACT_NONE, ACT_RELU, ACT_LEAKY = 0, 1, 2
 ACT_RES_AFTER = 16      # OR-ed into `act`: the residual is added after the activation
@@ -28,6 +32,13 @@ def expand_steps(flow):
         for pos, name in enumerate(_as_list(names)):
             steps.append((_as_list(src if pos == 0 else dst), name, dst))
     return steps
+
+
+def convt_ok(srcs, para, inits, shapes):
+    """A convtranspose step the phase-decomposed kernel takes: constant 4-D filter, 4-D input, and a geometry
+    layer.convt_phase_eligible accepts (group 1, dilation 1, pads within the kernel reach)."""
+    return (len(srcs) >= 2 and srcs[1] in inits and _is4d(shapes, srcs[1]) and _is4d(shapes, srcs[0])
+            and convt_phase_eligible(shapes[srcs[1]], **para))
 
 
 def fuse_flow(layers, flow, init_names, shapes):
@@ -48,7 +59,9 @@ def fuse_flow(layers, flow, init_names, shapes):
     consumed, fused_at, nfused = set(), {}, 0
     for i, (srcs, name, dst) in enumerate(steps):
         kind, para = kinds[name]
-        if kind != "conv" or i in consumed or not isinstance(dst, str):
+        if i in consumed or not isinstance(dst, str):
+            continue
+        if kind != "conv" and not (kind == "convtranspose" and convt_ok(srcs, para, inits, shapes)):
             continue
         chain, cur, stage = [i], dst, 0
         extra = {"scale": "None", "shift": "None", "res": "None", "act": ACT_NONE, "alpha": 0.0}
@@ -87,7 +100,7 @@ def fuse_flow(layers, flow, init_names, shapes):
             cur = jdst
         if len(chain) > 1:
             consumed.update(chain)
-            fused_at[chain[-1]] = (srcs, name, para, extra, cur)
+            fused_at[chain[-1]] = (srcs, name, kind, para, extra, cur)
             nfused += len(chain) - 1
     body, out_flow, seen = [], [], set()
 
@@ -98,11 +111,11 @@ def fuse_flow(layers, flow, init_names, shapes):
 
     for i, (srcs, name, dst) in enumerate(steps):
         if i in fused_at:
-            csrcs, cname, cpara, extra, out = fused_at[i]
+            csrcs, cname, ckind, cpara, extra, out = fused_at[i]
             para = dict(cpara, act=extra["act"], alpha=extra["alpha"])
             args = [csrcs[0], csrcs[1], csrcs[2] if len(csrcs) > 2 else "None",
                     extra["scale"], extra["shift"], extra["res"]]
-            add_layer([cname + "+", "conv_fused", para])
+            add_layer([cname + "+", "conv_fused" if ckind == "conv" else "convt_fused", para])
             out_flow.append([args, [cname + "+"], out])
         elif i not in consumed:
             kind, para = kinds[name]
@@ -179,7 +192,8 @@ def _nbytes(shape):
 
 
 def assign_layouts(body, flow, init_names, shapes, force=False):
-    """-> (body', flow', number of Q4 steps).  Rewrites conv / conv_fused steps to `conv_q4` and the
+    """-> (body', flow', number of Q4 steps).  Rewrites conv / conv_fused steps to `conv_q4`, the transposed convs
+    the phase-decomposed kernel takes (convtranspose / convt_fused) to `convt_q4`, and the
     HBM-bound layers that follow them to their `*_q4` kinds, inserting `to_q4` / `from_q4` steps at
     the edges.  The program's observable values (its last step's outputs) stay NCHW.
 
@@ -246,6 +260,17 @@ def assign_layouts(body, flow, init_names, shapes, force=False):
                 if shapes.get(dst) is not None:
                     k = shapes[srcs[1]]
                     est["gain"] += 2.0 * (_nbytes(shapes[dst]) / 4) * k[1] * k[2] * k[3] * _Q4_CONV_GAIN_S_PER_FLOP
+        elif (kind in ("convtranspose", "convt_fused") and single and convt_ok(srcs, para, inits, shapes)
+              and all(k == "None" or k in inits for k in srcs[2:5])
+              and (len(srcs) < 6 or srcs[5] == "None" or (srcs[5] not in inits and _is4d(shapes, srcs[5])))):
+            # the NCHW entry converts its input and output itself (layer.ConvTransposeFused): in Q4 those two passes go
+            as_q4 = True
+            full = list(srcs) + ["None"] * (6 - len(srcs))
+            args = [need(full[0], True)] + full[1:5] + [need(full[5], True)]
+            new_kind = "convt_q4"
+            for k in (srcs[0], dst):
+                if shapes.get(k) is not None:
+                    est["gain"] += _nbytes(shapes[k]) * _CONVERT_S_PER_BYTE
         elif kind in Q4_POINTWISE and single and _q4_pointwise_ok(kind, srcs, para, inits, shapes) \
                 and any(k in q4 for k in srcs):
             as_q4 = True
@@ -292,7 +317,7 @@ def assign_layouts(body, flow, init_names, shapes, force=False):
 # when nothing else reads y it is never written at all.  `chain_winograd` makes the stages explicit plan
 # steps and merges the out / in pairs.  Kinds that only read their inputs (no in-place update): a
 # Winograd input transform may be hoisted over them.
-_PURE_READERS = ("conv_q4", "wino4_in", "wino4_gemm", "wino4_out", "wino4_chain", "wino43_in", "wino43_gemm", "wino43_out",
+_PURE_READERS = ("conv_q4", "convt_q4", "wino4_in", "wino4_gemm", "wino4_out", "wino4_chain", "wino43_in", "wino43_gemm", "wino43_out",
                  "wino43_chain", "conv1x1_wino_in", "conv_q4_pair", "add_q4", "maxpool_q4",
                  "averagepool_q4", "gap_q4", "upsample_q4", "concat_q4", "upconcat_q4", "batchnorm_q4",
                  "leakyrelu_q4", "sigmoid_q4", "from_q4")

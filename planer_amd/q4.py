@@ -17,7 +17,8 @@ import numpy
 
 from . import _lib
 from .hip import DeviceArray, empty
-from .layer import ACT_NONE, _f32, _host_values, _ptr, conv_out_hw
+from .layer import (ACT_NONE, _f32, _host_values, _ptr, conv_out_hw, convt_out_hw, convt_phase_eligible, convt_q4_call,
+                    prepare_convt_weights)
 
 
 def is_q4(a):
@@ -95,6 +96,40 @@ def prepare_dw_q4_weights(K):
     _lib.call("pl_conv2d_prepare_dw_q4_f32", K.ctx.handle, K.ptr, c, kh, kw, out.ptr)
     out.shape = K.shape
     return out
+
+
+def convt_q4_eligible(k_shape, group=1, strides=(2, 2), dilations=(1, 1), pads=(0, 0, 0, 0), output_padding=(0, 0), **_):
+    """A transposed conv ConvTransposeQ4 runs: group 1, dilation 1, pads within the kernel reach (layer.convt_phase_eligible)."""
+    return convt_phase_eligible(k_shape, group, strides, dilations, pads, output_padding)
+
+
+def prepare_convt_q4_weights(K, strides=(2, 2)):
+    """ConvTranspose filters [Cin][Cout][kh][kw] -> per output phase a stride-1 sub-filter in k-quad-major form
+    (ConvTransposeQ4 w_layout=14; layer.prepare_convt_weights).  The packing depends on the strides."""
+    return prepare_convt_weights(K, strides)
+
+
+def ConvTransposeQ4(xq, Kq, B=None, scale=None, shift=None, resq=None, strides=(2, 2), dilations=(1, 1), pads=(0, 0, 0, 0),
+                    output_padding=(0, 0), group=1, act=ACT_NONE, alpha=0.0, w_layout=0, **_):
+    """layer.ConvTranspose2d with the fused tail of ConvQ4 on Q4 tensors, by output phase (pl_conv2d_convt_q4_f32).
+    w_layout=14: Kq from prepare_convt_q4_weights() for these strides; otherwise the filter is prepared here."""
+    _f32(xq, Kq, B, scale, shift, resq)
+    if not is_q4(xq) or (resq is not None and not is_q4(resq)):
+        raise TypeError("ConvTransposeQ4 needs Q4 activations (planer_amd.q4.to_q4)")
+    if not convt_q4_eligible(Kq.shape, group, strides, dilations, pads, output_padding):
+        raise ValueError("phase-decomposed convtranspose: group 1, dilation 1 and pads within the kernel reach only")
+    n, cin, h, w = logical_shape(xq)
+    if Kq.shape[0] != cin:
+        raise ValueError("convtranspose: weight %s does not match input %s" % (Kq.shape, (n, cin, h, w)))
+    cout, kh, kw = Kq.shape[1:]
+    ho, wo = convt_out_hw(h, w, kh, kw, strides, pads, output_padding)
+    y = _new_q4(n, cout, ho, wo, xq.ctx)
+    if resq is not None and resq.shape != y.shape:
+        raise ValueError("fused residual shape %s != convtranspose output %s" % (resq.shape, y.shape))
+    if y.size:
+        Kp = Kq if int(w_layout) == 14 else prepare_convt_weights(Kq, strides)
+        convt_q4_call(xq, Kp, B, y, scale, shift, resq, strides, pads, output_padding, act, alpha)
+    return y
 
 
 def winograd_q4_eligible(k_shape, group=1, strides=(1, 1), dilations=(1, 1), pads=(0, 0, 0, 0), **_):
@@ -709,7 +744,7 @@ Q4_LAYERS = {"maxpool": MaxpoolQ4, "averagepool": AveragePoolQ4, "gap": GlobalAv
 
 def register(layer_map):
     """Plan-internal kinds (never present in a user's IR)."""
-    layer_map.update({"to_q4": to_q4, "from_q4": from_q4, "conv_q4": ConvQ4, "upconcat_q4": UpConcatQ4,
+    layer_map.update({"to_q4": to_q4, "from_q4": from_q4, "conv_q4": ConvQ4, "convt_q4": ConvTransposeQ4, "upconcat_q4": UpConcatQ4,
                       "wino4_in": Wino4In, "wino4_gemm": Wino4Gemm, "wino4_out": Wino4Out, "wino4_chain": Wino4Chain,
                       "conv_q4_pair": ConvQ4Pair, "conv_pool_q4": ConvPoolQ4, "conv1x1_wino_in": Conv1x1WinoIn,
                       "wino43_in": Wino43In, "wino43_gemm": Wino43Gemm, "wino43_out": Wino43Out, "wino43_chain": Wino43Chain})
