@@ -444,6 +444,15 @@ class DeviceArray:
 ndarray = DeviceArray
 
 
+def _f32(*arrays):
+    for a in arrays:
+        if a is not None:
+            if not isinstance(a, DeviceArray):
+                raise TypeError("expected DeviceArray, got %s (use planer_amd.asarray)" % type(a).__name__)
+            if a.dtype != numpy.float32:
+                raise NotImplementedError("the HIP path computes in float32, got %s" % a.dtype)
+
+
 def empty(shape, dtype=numpy.float32, ctx=None):
     if isinstance(shape, (int, numpy.integer)):
         shape = (shape,)

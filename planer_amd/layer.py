@@ -13,12 +13,13 @@ Every kind of the reference's table (layer.py:262-281) is here; an unknown
 kind raises KeyError in Net like the reference (net.py:15), and inputs a kernel
 does not cover raise NotImplementedError instead of silently running on the CPU.
 """
-import ctypes
 
 import numpy
 
 from . import _lib
-from .hip import DeviceArray, asarray, empty
+from .conv_layouts import (CONVT_Q4, convt_phase_eligible, prepare_conv_weights, prepare_convt_weights,  # noqa: F401
+                           prepare_winograd_weights, winograd_eligible)
+from .hip import DeviceArray, _f32, asarray, empty
 
 ACT_NONE, ACT_RELU, ACT_LEAKY = _lib.ACT_NONE, _lib.ACT_RELU, _lib.ACT_LEAKY
 
@@ -43,15 +44,6 @@ def wrap(f, layername="layer"):
 
 
 # ---- helpers -----------------------------------------------------------------
-def _f32(*arrays):
-    for a in arrays:
-        if a is not None:
-            if not isinstance(a, DeviceArray):
-                raise TypeError("expected DeviceArray, got %s (use planer_amd.asarray)" % type(a).__name__)
-            if a.dtype != numpy.float32:
-                raise NotImplementedError("the HIP path computes in float32, got %s" % a.dtype)
-
-
 def _ptr(a):
     return None if a is None else a.ptr
 
@@ -77,48 +69,13 @@ def Conv2d(x, K, B=None, group=1, strides=(1, 1), dilations=(1, 1), pads=(0, 0, 
     return ConvFused(x, K, B, group=group, strides=strides, dilations=dilations, pads=pads)
 
 
-def prepare_conv_weights(K):
-    """OIHW filters -> the tap-major layout [Cout][kh*kw][Cin/g] the fast conv
-    kernel reads (done once per model by Net's plan compiler).  The returned
-    array keeps the logical OIHW shape; only the bytes are permuted."""
-    _f32(K)
-    cout, cin_g, kh, kw = K.shape
-    if cin_g % 16:
-        raise ValueError("tap-major filters need Cin/group % 16 == 0")
-    if kh * kw == 1:
-        return K                                   # identical in both layouts
-    out = empty(K.shape, ctx=K.ctx)
-    _lib.call("pl_conv2d_prepare_weights_f32", K.ctx.handle, K.ptr, cout, cin_g, kh, kw, out.ptr)
-    return out
-
-
-def winograd_eligible(k_shape, group=1, strides=(1, 1), dilations=(1, 1), pads=(0, 0, 0, 0)):
-    """3x3 / stride 1 / pad 1 / no dilation / no groups, Cin % 16 == 0."""
-    cout, cin_g, kh, kw = k_shape
-    return (kh == 3 and kw == 3 and group == 1 and cin_g % 16 == 0 and list(strides) == [1, 1]
-            and list(dilations) == [1, 1] and list(pads) == [1, 1, 1, 1])
-
-
-def prepare_winograd_weights(K):
-    """OIHW 3x3 filters -> Winograd F(2x2,3x3) domain U[16][Cout][Cin] (w_layout=3).  The
-    returned array keeps the logical OIHW shape; its allocation holds 16*Cout*Cin floats."""
-    _f32(K)
-    cout, cin, kh, kw = K.shape
-    if (kh, kw) != (3, 3) or cin % 16:
-        raise ValueError("winograd filters need 3x3 kernels and Cin % 16 == 0")
-    out = empty((16 * cout * cin,), ctx=K.ctx)
-    _lib.call("pl_conv2d_prepare_winograd_f32", K.ctx.handle, K.ptr, cout, cin, out.ptr)
-    out.shape = K.shape
-    return out
-
-
 def ConvFused(x, K, B=None, scale=None, shift=None, res=None, group=1, strides=(1, 1),
               dilations=(1, 1), pads=(0, 0, 0, 0), act=ACT_NONE, alpha=0.0, w_layout=0):
     """Conv2d with BatchNorm / Add / (Leaky)ReLU folded into its epilogue:
     act((conv(x,K)+B)*scale + shift + res).  Emitted by Net's plan compiler for
     the chains conv->batchnorm->[add]->[relu|leakyrelu]; not a reference op.
-    w_layout=1: K holds tap-major bytes from prepare_conv_weights();
-    w_layout=3: K holds Winograd-domain filters from prepare_winograd_weights()."""
+    w_layout (conv_layouts): TAP_NCHW, K holds tap-major bytes from prepare_conv_weights(); WINO2_NCHW, Winograd-domain
+    filters from prepare_winograd_weights()."""
     _f32(x, K, B, scale, shift, res)
     n, cin, h, w = x.shape
     cout, cin_g, kh, kw = K.shape
@@ -793,31 +750,6 @@ def Split(x, split=None, axis=0):
     return outs
 
 
-def convt_phase_eligible(k_shape, group=1, strides=(2, 2), dilations=(1, 1), pads=(0, 0, 0, 0), output_padding=(0, 0), **_):
-    """A transposed conv the phase-decomposed kernel runs (pl_conv2d_convt_q4_f32): 4-D filter [Cin][Cout][kh][kw], group 1,
-    dilation 1, pads within the kernel reach.  Any stride, kh != kw, asymmetric pads and output_padding."""
-    if len(k_shape) != 4 or int(group) != 1 or [int(d) for d in dilations] != [1, 1] or len(list(pads)) != 4:
-        return False
-    kh, kw = k_shape[2:]
-    p, op = [int(v) for v in pads], [int(v) for v in output_padding]
-    return min(int(s) for s in strides) >= 1 and min(kh - 1 - p[0], kh - 1 - p[2] + op[0], kw - 1 - p[1], kw - 1 - p[3] + op[1]) >= 0
-
-
-def prepare_convt_weights(K, strides=(2, 2)):
-    """ConvTranspose filters [Cin][Cout][kh][kw] -> one stride-1 sub-filter per output phase in the channel-quad form
-    (w_layout=14, pl_conv2d_prepare_convt_q4_f32): done once per model by Net's plan compiler.  The returned array keeps the
-    logical shape; its allocation is the packed size, which depends on the strides."""
-    _f32(K)
-    cin, cout, kh, kw = K.shape
-    sh, sw = [int(v) for v in strides]
-    elems = ctypes.c_size_t()
-    _lib.call("pl_conv2d_convt_filter_elems", cin, cout, kh, kw, sh, sw, ctypes.byref(elems))
-    out = empty((elems.value,), ctx=K.ctx)
-    _lib.call("pl_conv2d_prepare_convt_q4_f32", K.ctx.handle, K.ptr, cin, cout, kh, kw, sh, sw, out.ptr)
-    out.shape = K.shape
-    return out
-
-
 def convt_out_hw(h, w, kh, kw, strides, pads, output_padding):
     """Output extent of the reference's zero-stuffed form (layer.py:28-34) at dilation 1."""
     return ((h - 1) * int(strides[0]) - int(pads[0]) - int(pads[2]) + kh + int(output_padding[0]),
@@ -852,7 +784,7 @@ def ConvTransposeFused(x, K, B=None, scale=None, shift=None, res=None, strides=(
         raise ValueError("fused residual shape %s != convtranspose output %s" % (res.shape, y.shape))
     if not y.size:
         return y
-    Kp = K if int(w_layout) == 14 else prepare_convt_weights(K, strides)
+    Kp = K if int(w_layout) == CONVT_Q4 else prepare_convt_weights(K, strides)
 
     def quads(a, c, hh, ww):
         q = empty((a.shape[0], (c + 3) // 4, hh, ww, 4), ctx=x.ctx)

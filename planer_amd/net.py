@@ -27,6 +27,8 @@ from . import _lib
 from . import hip
 from .hip import DeviceArray
 from . import q4 as _q4
+from .conv_layouts import (CONV_KINDS, CONVT_KINDS, DIRECT_Q4, IGEMM_NCHW, LAYOUTS, ROWPACK_Q4, STEM_POOL, STEM_POOL_NCHW, WINO4_Q4,
+                           WINO43_Q4, choose, suffix)
 from .layer import layer_map, wrap
 from .plan import assign_layouts, chain_winograd, fuse_conv1x1_wino_in, fuse_flow, pair_sibling_convs
 
@@ -34,16 +36,8 @@ _q4.register(layer_map)
 
 _ALIGN = 256
 
-# ConvQ4 / ConvFused w_layout codes -> what runs (for run reports)
-W_LAYOUT_NAMES = {0: "igemm-nchw", 1: "tap-nchw", 2: "direct-q4 (conv_q4_kernel)", 3: "wino2x2-nchw",
-                  4: "wino2x2-q4 (transforms + grouped conv_q4_kernel)",
-                  6: "rowpack-q4 (nchw_to_rowpack + conv_q4_kernel)",
-                  7: "wino4x4-q4 (transforms + grouped conv_q4_kernel)", 8: "w1d4 F(4,3) (conv_w1d4_kernel)",
-                  9: "wf4 fused F(4x4,3x3) (conv_wf4_kernel)", 10: "stem + maxpool (conv_stem_pool_kernel)",
-                  11: "wino43-q4 (mixed F(4,3) x F(3,3) tiles: transforms + 121 grouped conv_q4_kernel)",
-                  12: "stem + maxpool (conv_stem_pool_kernel)",          # (the kernel reads the NCHW batch itself)
-                  13: "depthwise-q4 (conv_dw_kernel)",
-                  14: "convt-q4 (phase-decomposed convt_q4_kernel)"}
+# w_layout code -> what runs (for run reports; conv_layouts.LAYOUTS)
+W_LAYOUT_NAMES = {code: lay.name for code, lay in LAYOUTS.items()}
 
 
 def _as_list(v):
@@ -447,10 +441,11 @@ class Net:
                     events.append((name, obj.name, hip.Event(self.ctx).record()))
                 if record is not None and obj.name in ("conv", "conv_fused", "conv_q4", "dense", "matmul", "wino4_gemm", "wino43_gemm",
                                                        "conv_q4_pair", "conv_pool_q4", "conv1x1_wino_in", "convt_q4", "convt_fused"):
-                    lay = obj.para().get("w_layout", 2 if obj.name in ("conv_q4_pair", "conv1x1_wino_in") else 0) if obj.name != "conv" else 0
+                    lay = (obj.para().get("w_layout", DIRECT_Q4 if obj.name in ("conv_q4_pair", "conv1x1_wino_in") else IGEMM_NCHW)
+                           if obj.name != "conv" else IGEMM_NCHW)
                     lname = name
                     if obj.name in ("wino4_gemm", "wino43_gemm"):       # the GEMM stage of a staged Winograd conv
-                        lay, lname = (7 if obj.name == "wino4_gemm" else 11), name[:-len("@gemm")]
+                        lay, lname = (WINO4_Q4 if obj.name == "wino4_gemm" else WINO43_Q4), name[:-len("@gemm")]
                     ctx_ = args[0].ctx if isinstance(args[0], DeviceArray) else self.ctx
                     xshape = (args[0].meta if args[0].meta is not None else
                               _q4.logical_shape(args[0]) if _q4.is_q4(args[0]) else args[0].shape)
@@ -512,63 +507,27 @@ class Net:
     def _prepare_filters(self, body, flow, shapes):
         """Give every eligible conv a prepared copy of its (constant) filter: tap-major for the
         fast implicit-GEMM kernel, or Winograd-domain where that measures faster for this shape."""
-        from .layer import prepare_conv_weights, prepare_winograd_weights, winograd_eligible, ConvFused
         wmap = dict(zip(self.inits, self.weights))
         kinds = {b[0]: b for b in body}
         out_body = {b[0]: list(b) for b in body}
         out_flow = []
-        use_wino = os.environ.get("PLANER_HIP_WINOGRAD", "1") != "0"
         for src, names, dst in flow:
             name = names[0] if isinstance(names, list) else names
-            entry = kinds[name]
+            _, kind, para = kinds[name]
             srcs = list(src) if isinstance(src, list) else [src]
-            if entry[1] == "conv_q4":
-                K = wmap[srcs[1]]
-                group = int(entry[2].get("group", 1))
-                para = {k: v for k, v in entry[2].items() if k in ("group", "strides", "dilations", "pads")}
-                lay = 2
-                if entry[2].get("rowpack") and _q4.rowpack_eligible(K.shape, **para):
-                    lay = 6
-                elif _q4.dw_q4_eligible(K.shape, **para):
-                    lay = 13
-                elif (use_wino and _q4.w1d_q4_eligible(K.shape, **para)
-                        and shapes.get(srcs[0].split("@")[0]) is not None):
-                    lay = self._pick_conv_algo(_q4.ConvQ4, K, srcs, entry[2], shapes, wmap, q4=True)
-                key = {2: "%s@q4g%d" % (srcs[1], group), 4: srcs[1] + "@winoq4", 6: srcs[1] + "@rowpack", 7: srcs[1] + "@wino4q4",
-                       8: srcs[1] + "@w1d4q4", 9: srcs[1] + "@wf4q4", 11: srcs[1] + "@wino43q4", 13: srcs[1] + "@dwq4"}[lay]
-                if key not in self._extra:
-                    self._extra[key] = {2: lambda: _q4.prepare_q4_weights(K, group),
-                                        4: lambda: _q4.prepare_winograd_q4_weights(K),
-                                        6: lambda: _q4.prepare_rowpack_weights(K),
-                                        7: lambda: _q4.prepare_winograd4_q4_weights(K),
-                                        8: lambda: _q4.prepare_w1d4_q4_weights(K),
-                                        9: lambda: _q4.prepare_wf4_q4_weights(K),
-                                        11: lambda: _q4.prepare_winograd43_q4_weights(K),
-                                        13: lambda: _q4.prepare_dw_q4_weights(K)}[lay]()
-                srcs[1] = key
-                out_body[name] = [name, "conv_q4", dict(entry[2], w_layout=lay)]
-            elif (entry[1] in ("convt_q4", "convt_fused", "convtranspose") and len(srcs) >= 2 and srcs[1] in wmap
-                    and _q4.convt_q4_eligible(wmap[srcs[1]].shape, **entry[2])):
-                # transposed convs: the per-phase sub-filters are made once per model (w_layout 14), not on every call
-                strides = [int(v) for v in entry[2].get("strides", (2, 2))]
-                key = "%s@convt%dx%d" % (srcs[1], strides[0], strides[1])
-                if key not in self._extra:
-                    self._extra[key] = _q4.prepare_convt_q4_weights(wmap[srcs[1]], strides)
-                srcs[1] = key
-                kind = "convt_q4" if entry[1] == "convt_q4" else "convt_fused"
-                out_body[name] = [name, kind, dict(entry[2], w_layout=14)]
-            elif entry[1] in ("conv", "conv_fused") and len(srcs) >= 2 and srcs[1] in wmap:
-                K = wmap[srcs[1]]
-                if K.ndim == 4 and K.dtype == numpy.float32 and K.shape[1] % 16 == 0:
-                    para = {k: v for k, v in entry[2].items() if k in ("group", "strides", "dilations", "pads")}
-                    lay = 1
-                    if use_wino and winograd_eligible(K.shape, **para) and shapes.get(srcs[0]) is not None:
-                        lay = self._pick_conv_algo(ConvFused, K, srcs, entry[2], shapes, wmap)
-                    key = srcs[1] + ("@tap" if lay == 1 else "@wino")
+            K = wmap[srcs[1]] if kind == "conv_q4" else wmap.get(srcs[1]) if len(srcs) >= 2 else None
+            if K is not None and (kind not in CONV_KINDS or K.dtype == numpy.float32):
+                # (an NCHW conv looks its input up by key: one on a converted copy, key@nchw, is not timed)
+                xs = shapes.get(srcs[0].split("@")[0] if kind == "conv_q4" else srcs[0])
+                got = choose(kind, K.shape, para, xs, para.get("rowpack"),
+                             lambda cands: self._pick_conv_algo(cands, K, srcs, para, shapes, q4=kind == "conv_q4"))
+                if got is not None:
+                    lay, key = got[0], srcs[1] + got[1]
                     if key not in self._extra:
-                        self._extra[key] = prepare_conv_weights(K) if lay == 1 else prepare_winograd_weights(K)
+                        self._extra[key] = LAYOUTS[lay].prepare(K, **para)
                     srcs[1] = key
-                    out_body[name] = [name, "conv_fused", dict(entry[2], w_layout=lay)]
+                    new_kind = kind if kind in ("conv_q4", "convt_q4") else "convt_fused" if kind in CONVT_KINDS else "conv_fused"
+                    out_body[name] = [name, new_kind, dict(para, w_layout=lay)]
             out_flow.append([srcs, [name], dst])
         # the row-packed stem conv whose only reader is maxpool(3x3 / s2 / p1): one kernel that writes the pooled tensor only
         # (csrc/conv_stem_pool_kernel.h); PLANER_HIP_STEM_POOL=0 keeps the two kernels
@@ -637,7 +596,7 @@ class Net:
         drop, out = set(), []
         for i, (src, names, dst) in enumerate(flow):
             entry = body[names[0]]
-            if (entry[1] == "conv_q4" and entry[2].get("w_layout") == 6 and isinstance(dst, str)
+            if (entry[1] == "conv_q4" and entry[2].get("w_layout") == ROWPACK_Q4 and isinstance(dst, str)
                     and (len(src) < 6 or src[5] == "None") and len(readers.get(dst, [])) == 1 and i != len(flow) - 1):
                 j = readers[dst][0]
                 psrc, pnames, pdst = flow[j]
@@ -649,16 +608,17 @@ class Net:
                         and [int(v) for v in pe[2].get("strides", (2, 2))] == [2, 2]
                         and [int(v) for v in pe[2].get("pads", (0, 0, 0, 0))] == [1, 1, 1, 1]
                         and int(entry[2].get("act", 0)) in (0, 1, 2) and _q4.stem_pool_eligible(tuple(xs), tuple(ks), **para)):
-                    lay, fsrc = 10, list(src[:5])
-                    if (os.environ.get("PLANER_HIP_STEM_NCHW", "1") != "0" and src[1].endswith("@rowpack")
+                    lay, fsrc, packed = STEM_POOL, list(src[:5]), suffix(ROWPACK_Q4, para)
+                    if (os.environ.get("PLANER_HIP_STEM_NCHW", "1") != "0" and src[1].endswith(packed)
                             and _q4.stem_pool_nchw_eligible(tuple(xs), tuple(ks), **para)):
                         # W % 4 == 0: the kernel reads the NCHW batch itself (no row-packed copy), filter in its own k order
-                        lay, key = 12, src[1][:-len("@rowpack")] + "@stemnchw"
+                        lay, init = STEM_POOL_NCHW, src[1][:-len(packed)]
+                        key = init + suffix(lay, para)
                         if key not in self._extra:
-                            self._extra[key] = _q4.prepare_stem_nchw_weights(dict(zip(self.inits, self.weights))[src[1][:-len("@rowpack")]])
+                            self._extra[key] = LAYOUTS[lay].prepare(dict(zip(self.inits, self.weights))[init])
                         fsrc[1] = key
                     extra = {}
-                    if lay == 12 and self._pick_mode == "throughput" and os.environ.get("PLANER_HIP_STEM_ROWS14", "1") != "0":
+                    if lay == STEM_POOL_NCHW and self._pick_mode == "throughput" and os.environ.get("PLANER_HIP_STEM_ROWS14", "1") != "0":
                         # throughput plans: strips of 14 pooled rows where that still leaves half a chip of workgroups -- 15
                         # conv-row pairs instead of 2 x 8, on half the CUs for longer (160 against 91 us alone; +0.8 ... +1.2 % on
                         # seven replicas: the other replicas' kernels take the rest of the chip)
@@ -673,30 +633,16 @@ class Net:
                 out.append([src, names, dst])
         return out
 
-    def _pick_conv_algo(self, ConvFused, K, srcs, para, shapes, wmap, q4=False):
-        """Time the direct implicit GEMM and the Winograd variants for this conv's real shape and
-        epilogue; -> w_layout 1 or 3 (NCHW), 2 / 8 / 4 / 7 / 9 (channel-quad).  Cached per shape
-        signature (and persisted, see `algo_cache`); `force_algo` bypasses the measurement."""
-        from .layer import prepare_conv_weights, prepare_winograd_weights
+    def _pick_conv_algo(self, cands, K, srcs, para, shapes, q4=False):
+        """Time the candidate w_layouts (conv_layouts.candidates) for this conv's real shape and epilogue; the first is the
+        fallback and wins ties.  Cached per shape signature (and persisted, see `algo_cache`); `force_algo` bypasses the
+        measurement."""
+        from .layer import ConvFused
         xs = tuple(shapes[srcs[0].split("@")[0]])
         has = [i < len(srcs) and srcs[i] != "None" for i in range(2, 6)]       # B, scale, shift, res
         sig = (q4, xs, tuple(K.shape), tuple(has), para.get("act", 0))
-        cands = [(1, prepare_conv_weights), (3, prepare_winograd_weights)]
-        if q4:
-            # direct, fused 1-D Winograd F(4,3) along W, 2-D Winograd pipelines with separate transform kernels, fully fused F(4x4,3x3)
-            cands = [(2, _q4.prepare_q4_weights), (8, _q4.prepare_w1d4_q4_weights)]
-            if _q4.winograd_q4_eligible(K.shape, **{k: v for k, v in para.items()
-                                                   if k in ("group", "strides", "dilations", "pads")}):
-                cands.append((4, _q4.prepare_winograd_q4_weights))
-                if os.environ.get("PLANER_HIP_WINOGRAD4", "1") != "0":
-                    cands.append((7, _q4.prepare_winograd4_q4_weights))      # F(4x4,3x3), staged
-                if os.environ.get("PLANER_HIP_WF4", "1") != "0":
-                    cands.append((9, _q4.prepare_wf4_q4_weights))            # F(4x4,3x3), one fused kernel
-                if os.environ.get("PLANER_HIP_WINOGRAD43", "1") != "0" and _q4.winograd43_eligible(xs, K.shape, 64, **{
-                        k: v for k, v in para.items() if k in ("group", "strides", "dilations", "pads")}):
-                    cands.append((11, _q4.prepare_winograd43_q4_weights))    # mixed F(4,3) x F(3,3) tiles, staged
         if self.force_algo is not None:
-            if self.force_algo not in [c[0] for c in cands]:
+            if self.force_algo not in cands:
                 raise ValueError("force_algo=%r does not apply to conv %s k%s" % (self.force_algo, xs, tuple(K.shape)))
             return self.force_algo
         self._load_algo_cache()
@@ -704,9 +650,9 @@ class Net:
         # a fraction of the CUs for longer loses an isolated timing and can win there -- the other replicas' kernels take the rest
         # of the chip (ResNet-18 layer2 at batch 32: the fused F(4x4,3x3) kernel on 128 workgroups, 63 us against 43 us staged, and
         # +1.9 % on seven replicas).  Latency plans (net(x) one call at a time) keep the isolated picks.
-        if self._pick_mode == "throughput" and self._algo_tp.get(sig) in [c[0] for c in cands]:
+        if self._pick_mode == "throughput" and self._algo_tp.get(sig) in cands:
             return self._algo_tp[sig]
-        if sig in self._algo and self._algo[sig] in [c[0] for c in cands]:      # (a stored pick this run's switches exclude is ignored)
+        if sig in self._algo and self._algo[sig] in cands:      # (a stored pick this run's switches exclude is ignored)
             return self._algo[sig]
         self.algo_misses += 1
         ctx = self.ctx
@@ -723,11 +669,12 @@ class Net:
         args = [hip.zeros((cout,), numpy.float32, ctx) if has[0] else None, chan if has[1] else None,
                 chan if has[2] else None, res]
         kw = {k: v for k, v in para.items() if k != "w_layout"}
-        best, best_ms = cands[0][0], None
-        for lay, prep in cands:
+        conv = _q4.ConvQ4 if q4 else ConvFused
+        best, best_ms = cands[0], None
+        for lay in cands:
             try:
-                Kp = prep(K)
-                run = lambda: ConvFused(x, Kp, *args, w_layout=lay, **kw)
+                Kp = LAYOUTS[lay].prepare(K)
+                run = lambda: conv(x, Kp, *args, w_layout=lay, **kw)
                 for _ in range(3):
                     run()                              # first call autotunes the MFMA plan(s)
                 ms = None

@@ -15,7 +15,7 @@ chain was, so a residual operand produced after the conv is still available.
 """
 import os
 
-from .layer import convt_phase_eligible
+from .conv_layouts import DIRECT_Q4, STAGED_LAYOUTS, convt_phase_eligible, dw_q4_eligible, q4_conv_eligible
 
 ACT_NONE, ACT_RELU, ACT_LEAKY = 0, 1, 2
 ACT_RES_AFTER = 16      # OR-ed into `act`: the residual is added after the activation
@@ -141,21 +141,17 @@ def _is4d(shapes, key):
 
 def q4_conv_ok(srcs, para, inits, shapes):
     """A conv step can take the Q4 kernel: constant 4-D filter (and constant bias / scale / shift),
-    4-D input, symmetric pads, and groups that do not split a channel quad -- or one input and one output channel per group
-    (a depthwise conv: q4.dw_q4_eligible)."""
+    4-D input, symmetric pads, and groups that do not split a channel quad (conv_layouts.q4_conv_eligible) -- or one input
+    and one output channel per group (a depthwise conv: conv_layouts.dw_q4_eligible)."""
     if len(srcs) < 2 or srcs[1] not in inits or not _is4d(shapes, srcs[1]) or not _is4d(shapes, srcs[0]):
         return False
     if any(k != "None" and k not in inits for k in srcs[2:5]):
         return False
-    cout, cin_g = shapes[srcs[1]][0], shapes[srcs[1]][1]
     group = int(para.get("group", 1))
     pads = list(para.get("pads", (0, 0, 0, 0)))
     if len(pads) == 4 and (pads[0] != pads[2] or pads[1] != pads[3]):
         return False
-    k = shapes[srcs[1]]
-    if cin_g == 1 and cout == group and k[2] <= 7 and k[3] <= 7:
-        return True
-    return group == 1 or (cin_g % 4 == 0 and (cout // group) % 4 == 0)
+    return dw_q4_eligible(shapes[srcs[1]], group) or q4_conv_eligible(shapes[srcs[1]], group)
 
 
 def _q4_pointwise_ok(kind, srcs, para, inits, shapes):
@@ -321,9 +317,6 @@ _PURE_READERS = ("conv_q4", "convt_q4", "wino4_in", "wino4_gemm", "wino4_out", "
                  "wino43_chain", "conv1x1_wino_in", "conv_q4_pair", "add_q4", "maxpool_q4",
                  "averagepool_q4", "gap_q4", "upsample_q4", "concat_q4", "upconcat_q4", "batchnorm_q4",
                  "leakyrelu_q4", "sigmoid_q4", "from_q4")
-WINO4_LAYOUT = 7
-# w_layout -> stage-kind prefix: staged F(4x4,3x3), and the mixed-tile form for maps of 7 / 14 / 21 a side (q4.Wino43*)
-STAGED_LAYOUTS = {7: "wino4", 11: "wino43"}
 
 
 def chain_winograd(body, flow, supported=lambda key: True, chain=True):
@@ -403,7 +396,7 @@ def fuse_conv1x1_wino_in(body, flow, kshape=lambda key: None, small=lambda key: 
         csrcs, cname, cdst = steps[j]
         _, ckind, cpara = kinds[cname]
         full = csrcs + ["None"] * (6 - len(csrcs))
-        if j >= i or j in drop or ckind != "conv_q4" or cpara.get("w_layout") != 2 or not isinstance(cdst, str) or full[5] != "None":
+        if j >= i or j in drop or ckind != "conv_q4" or cpara.get("w_layout") != DIRECT_Q4 or not isinstance(cdst, str) or full[5] != "None":
             continue
         k = kshape(full[1])
         if (k is None or tuple(k[2:]) != (1, 1) or k[0] % 4 or int(cpara.get("group", 1)) != 1
@@ -450,7 +443,7 @@ def pair_sibling_convs(body, flow, kshape=lambda key: None):
         srcs, name, dst = steps[i]
         _, kind, para = kinds[name]
         full = srcs + ["None"] * (6 - len(srcs))
-        return (kind == "conv_q4" and para.get("w_layout") == 2 and isinstance(dst, str) and full[5] == "None"
+        return (kind == "conv_q4" and para.get("w_layout") == DIRECT_Q4 and isinstance(dst, str) and full[5] == "None"
                 and int(para.get("group", 1)) == 1 and [int(v) for v in para.get("dilations", (1, 1))] == [1, 1]
                 and not para.get("rowpack") and not (int(para.get("act", 0)) & ~3))
 

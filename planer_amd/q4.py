@@ -16,9 +16,15 @@ import ctypes
 import numpy
 
 from . import _lib
-from .hip import DeviceArray, empty
-from .layer import (ACT_NONE, _f32, _host_values, _ptr, conv_out_hw, convt_out_hw, convt_phase_eligible, convt_q4_call,
-                    prepare_convt_weights)
+from .conv_layouts import CONVT_Q4, DIRECT_Q4, DW_Q4, LAYOUTS, ROWPACK_Q4, STEM_POOL, STEM_POOL_NCHW, WF4_Q4, WINO43_Q4
+# the packers and predicates of the Q4 layouts, importable from here
+from .conv_layouts import (dw_q4_eligible, prepare_dw_q4_weights, prepare_q4_weights, prepare_rowpack_weights,  # noqa: F401
+                           prepare_stem_nchw_weights, prepare_w1d4_q4_weights, prepare_wf4_q4_weights, prepare_winograd4_q4_weights,
+                           prepare_winograd43_q4_weights, prepare_winograd_q4_weights, q4_conv_eligible, rowpack_eligible,
+                           stem_pool_eligible, stem_pool_nchw_eligible, w1d_q4_eligible, winograd43_eligible, winograd_q4_eligible)
+from .conv_layouts import convt_phase_eligible as convt_q4_eligible, prepare_convt_weights as prepare_convt_q4_weights
+from .hip import DeviceArray, _f32, empty
+from .layer import ACT_NONE, _host_values, _ptr, conv_out_hw, convt_out_hw, convt_q4_call
 
 
 def is_q4(a):
@@ -59,60 +65,10 @@ def from_q4(xq):
     return y
 
 
-def q4_conv_eligible(k_shape, group=1, **_):
-    cout, cin_g = k_shape[0], k_shape[1]
-    return len(k_shape) == 4 and (group == 1 or (cin_g % 4 == 0 and (cout // group) % 4 == 0))
-
-
-def prepare_q4_weights(K, group=1):
-    """OIHW filters -> wq[group][tap*ceil(Cin_g/4) + cin/4][Cout/group][4] (zero padded), made once
-    per model.  The returned array keeps the logical OIHW shape; its allocation is the packed size."""
-    _f32(K)
-    cout, cin_g, kh, kw = K.shape
-    n = ctypes.c_size_t()
-    _lib.call("pl_conv2d_q4_filter_elems", cout, cin_g, kh, kw, int(group), ctypes.byref(n))
-    out = empty((n.value,), ctx=K.ctx)
-    _lib.call("pl_conv2d_prepare_q4_f32", K.ctx.handle, K.ptr, cout, cin_g, kh, kw, int(group), out.ptr)
-    out.shape = K.shape
-    return out
-
-
-def dw_q4_eligible(k_shape, group=1, strides=(1, 1), dilations=(1, 1), pads=(0, 0, 0, 0), **_):
-    """Depthwise conv with channel multiplier 1 (group == Cin == Cout, OIHW filter [C][1][kh][kw]), kh / kw up to 7, symmetric
-    pads: the VALU kernel of csrc/conv_dw_kernel.h (ConvQ4 w_layout=13).  Any stride and dilation."""
-    pads = list(pads)
-    return (len(k_shape) == 4 and k_shape[1] == 1 and k_shape[0] == group and 1 <= k_shape[2] <= 7 and 1 <= k_shape[3] <= 7
-            and (len(pads) != 4 or (pads[0] == pads[2] and pads[1] == pads[3])))
-
-
-def prepare_dw_q4_weights(K):
-    """OIHW depthwise filters [C][1][kh][kw] -> [ceil(C/4)][kh*kw][4] with zero-padded quads (ConvQ4 w_layout=13).  The
-    returned array keeps the logical OIHW shape; its allocation is the packed size."""
-    _f32(K)
-    c, cin_g, kh, kw = K.shape
-    if cin_g != 1:
-        raise ValueError("depthwise filters have one input channel per group")
-    out = empty(((c + 3) // 4 * kh * kw * 4,), ctx=K.ctx)
-    _lib.call("pl_conv2d_prepare_dw_q4_f32", K.ctx.handle, K.ptr, c, kh, kw, out.ptr)
-    out.shape = K.shape
-    return out
-
-
-def convt_q4_eligible(k_shape, group=1, strides=(2, 2), dilations=(1, 1), pads=(0, 0, 0, 0), output_padding=(0, 0), **_):
-    """A transposed conv ConvTransposeQ4 runs: group 1, dilation 1, pads within the kernel reach (layer.convt_phase_eligible)."""
-    return convt_phase_eligible(k_shape, group, strides, dilations, pads, output_padding)
-
-
-def prepare_convt_q4_weights(K, strides=(2, 2)):
-    """ConvTranspose filters [Cin][Cout][kh][kw] -> per output phase a stride-1 sub-filter in k-quad-major form
-    (ConvTransposeQ4 w_layout=14; layer.prepare_convt_weights).  The packing depends on the strides."""
-    return prepare_convt_weights(K, strides)
-
-
 def ConvTransposeQ4(xq, Kq, B=None, scale=None, shift=None, resq=None, strides=(2, 2), dilations=(1, 1), pads=(0, 0, 0, 0),
                     output_padding=(0, 0), group=1, act=ACT_NONE, alpha=0.0, w_layout=0, **_):
     """layer.ConvTranspose2d with the fused tail of ConvQ4 on Q4 tensors, by output phase (pl_conv2d_convt_q4_f32).
-    w_layout=14: Kq from prepare_convt_q4_weights() for these strides; otherwise the filter is prepared here."""
+    w_layout CONVT_Q4: Kq from prepare_convt_q4_weights() for these strides; otherwise the filter is prepared here."""
     _f32(xq, Kq, B, scale, shift, resq)
     if not is_q4(xq) or (resq is not None and not is_q4(resq)):
         raise TypeError("ConvTransposeQ4 needs Q4 activations (planer_amd.q4.to_q4)")
@@ -127,137 +83,9 @@ def ConvTransposeQ4(xq, Kq, B=None, scale=None, shift=None, resq=None, strides=(
     if resq is not None and resq.shape != y.shape:
         raise ValueError("fused residual shape %s != convtranspose output %s" % (resq.shape, y.shape))
     if y.size:
-        Kp = Kq if int(w_layout) == 14 else prepare_convt_weights(Kq, strides)
+        Kp = Kq if int(w_layout) == CONVT_Q4 else prepare_convt_q4_weights(Kq, strides)
         convt_q4_call(xq, Kp, B, y, scale, shift, resq, strides, pads, output_padding, act, alpha)
     return y
-
-
-def winograd_q4_eligible(k_shape, group=1, strides=(1, 1), dilations=(1, 1), pads=(0, 0, 0, 0), **_):
-    """3x3 / stride 1 / pad 1 / no dilation / no groups, Cin and Cout multiples of 4."""
-    cout, cin_g, kh, kw = k_shape
-    return (kh == 3 and kw == 3 and group == 1 and cin_g % 4 == 0 and cout % 4 == 0 and list(strides) == [1, 1]
-            and list(dilations) == [1, 1] and list(pads) == [1, 1, 1, 1])
-
-
-def prepare_winograd_q4_weights(K):
-    """OIHW 3x3 filters -> Winograd-domain Q4 filters [16][k-quad][Cout][4] (ConvQ4 w_layout=4)."""
-    _f32(K)
-    cout, cin, kh, kw = K.shape
-    if (kh, kw) != (3, 3) or cin % 4 or cout % 4:
-        raise ValueError("winograd Q4 filters need 3x3 kernels, Cin % 4 == 0 and Cout % 4 == 0")
-    n = ctypes.c_size_t()
-    _lib.call("pl_conv2d_winograd_q4_filter_elems", cout, cin, ctypes.byref(n))
-    out = empty((n.value,), ctx=K.ctx)
-    _lib.call("pl_conv2d_prepare_winograd_q4_f32", K.ctx.handle, K.ptr, cout, cin, out.ptr)
-    out.shape = K.shape
-    return out
-
-
-def prepare_winograd4_q4_weights(K):
-    """OIHW 3x3 filters -> Winograd F(4x4,3x3) Q4 filters [36][k-quad][Cout][4] (ConvQ4 w_layout=7)."""
-    _f32(K)
-    cout, cin, kh, kw = K.shape
-    if (kh, kw) != (3, 3) or cin % 4 or cout % 4:
-        raise ValueError("winograd Q4 filters need 3x3 kernels, Cin % 4 == 0 and Cout % 4 == 0")
-    n = ctypes.c_size_t()
-    _lib.call("pl_conv2d_winograd4_q4_filter_elems", cout, cin, ctypes.byref(n))
-    out = empty((n.value,), ctx=K.ctx)
-    _lib.call("pl_conv2d_prepare_winograd4_q4_f32", K.ctx.handle, K.ptr, cout, cin, out.ptr)
-    out.shape = K.shape
-    return out
-
-
-def winograd43_eligible(x_shape, k_shape, min_columns=0, **para):
-    """Mixed-tile Winograd (csrc/wino43_kernels.h): a 3x3 / stride 1 / pad 1 / group 1 conv on a map whose sides are 7, 14 or 21.
-    `min_columns`: the plan compiler only offers it where each of the 121 per-frequency GEMMs has that many tile columns
-    (N * (H / 7) * (W / 7)): its filters are 3.4x those of F(4x4,3x3), and with few columns per filter the GEMM lives on filter
-    bandwidth -- ResNet-18's layer4 at batch 32 (32 columns, 127 MB of filters per conv) wins 4 us per conv in isolation and
-    loses 2 % of the pipelined rate, layer3 (128 columns) wins both ways."""
-    return (len(x_shape) == 4 and x_shape[2] in (7, 14, 21) and x_shape[3] in (7, 14, 21) and winograd_q4_eligible(k_shape, **para)
-            and x_shape[0] * (x_shape[2] // 7) * (x_shape[3] // 7) >= min_columns)
-
-
-def prepare_winograd43_q4_weights(K):
-    """OIHW 3x3 filters -> mixed-tile Winograd filters [121][k-quad][Cout][4] (ConvQ4 w_layout=11)."""
-    _f32(K)
-    cout, cin, kh, kw = K.shape
-    if (kh, kw) != (3, 3) or cin % 4 or cout % 4:
-        raise ValueError("winograd Q4 filters need 3x3 kernels, Cin % 4 == 0 and Cout % 4 == 0")
-    n = ctypes.c_size_t()
-    _lib.call("pl_conv2d_winograd43_q4_filter_elems", cout, cin, ctypes.byref(n))
-    out = empty((n.value,), ctx=K.ctx)
-    _lib.call("pl_conv2d_prepare_winograd43_q4_f32", K.ctx.handle, K.ptr, cout, cin, out.ptr)
-    out.shape = K.shape
-    return out
-
-
-def prepare_wf4_q4_weights(K):
-    """OIHW 3x3 filters -> fully fused F(4x4,3x3) filters [Cout/64][Cin/4][36][4][4][16] (ConvQ4 w_layout=9)."""
-    _f32(K)
-    cout, cin, kh, kw = K.shape
-    if (kh, kw) != (3, 3) or cin % 4 or cout % 4:
-        raise ValueError("winograd Q4 filters need 3x3 kernels, Cin % 4 == 0 and Cout % 4 == 0")
-    n = ctypes.c_size_t()
-    _lib.call("pl_conv2d_wf4_filter_elems", cout, cin, ctypes.byref(n))
-    out = empty((n.value,), ctx=K.ctx)
-    _lib.call("pl_conv2d_prepare_wf4_f32", K.ctx.handle, K.ptr, cout, cin, out.ptr)
-    out.shape = K.shape
-    return out
-
-
-def rowpack_eligible(k_shape, group=1, strides=(1, 1), dilations=(1, 1), pads=(0, 0, 0, 0), **_):
-    """Convs on 1..3 input channels (the stem): group 1, no dilation, symmetric pads."""
-    cout, cin_g, kh, kw = k_shape
-    pads = list(pads)
-    return (group == 1 and cin_g < 4 and list(dilations) == [1, 1] and len(pads) == 4
-            and pads[0] == pads[2] and pads[1] == pads[3])
-
-
-def prepare_rowpack_weights(K):
-    """OIHW filters with Cin < 4 -> row-packed [kh*ceil(kw*Cin/4)][Cout][4] (ConvQ4 w_layout=6)."""
-    _f32(K)
-    cout, cin, kh, kw = K.shape
-    n = ctypes.c_size_t()
-    _lib.call("pl_conv2d_rowpack_filter_elems", cout, cin, kh, kw, ctypes.byref(n))
-    out = empty((n.value,), ctx=K.ctx)
-    _lib.call("pl_conv2d_prepare_rowpack_f32", K.ctx.handle, K.ptr, cout, cin, kh, kw, out.ptr)
-    out.shape = K.shape
-    return out
-
-
-def prepare_stem_nchw_weights(K):
-    """OIHW stem filters [Cout][3][7][7] -> [48][Cout][4] in the k order of the stem + max-pool kernel that reads the NCHW
-    input itself (ConvPoolQ4 w_layout=12, csrc/conv_stem_pool_kernel.h)."""
-    _f32(K)
-    cout, cin, kh, kw = K.shape
-    if (cin, kh, kw) != (3, 7, 7):
-        raise ValueError("the NCHW stem kernel takes [Cout][3][7][7] filters")
-    n = ctypes.c_size_t()
-    _lib.call("pl_conv2d_stem_nchw_filter_elems", cout, ctypes.byref(n))
-    out = empty((n.value,), ctx=K.ctx)
-    _lib.call("pl_conv2d_prepare_stem_nchw_f32", K.ctx.handle, K.ptr, cout, out.ptr)
-    out.shape = K.shape
-    return out
-
-
-def prepare_w1d4_q4_weights(K):
-    """OIHW 3x3 filters -> fused 1-D Winograd F(4,3) filters [6][row*Cin/4 + cin/4][Cout][4] (w_layout=8)."""
-    _f32(K)
-    cout, cin, kh, kw = K.shape
-    if (kh, kw) != (3, 3) or cin % 4:
-        raise ValueError("1-D winograd filters need 3x3 kernels and Cin % 4 == 0")
-    n = ctypes.c_size_t()
-    _lib.call("pl_conv2d_w1d4_q4_filter_elems", cout, cin, ctypes.byref(n))
-    out = empty((n.value,), ctx=K.ctx)
-    _lib.call("pl_conv2d_prepare_w1d4_q4_f32", K.ctx.handle, K.ptr, cout, cin, out.ptr)
-    out.shape = K.shape
-    return out
-
-
-def w1d_q4_eligible(k_shape, group=1, strides=(1, 1), dilations=(1, 1), pads=(0, 0, 0, 0), **_):
-    cout, cin_g, kh, kw = k_shape
-    return (kh == 3 and kw == 3 and group == 1 and cin_g % 4 == 0 and list(strides) == [1, 1]
-            and list(dilations) == [1, 1] and list(pads) == [1, 1, 1, 1])
 
 
 def pack_rows(x, geom=None, src_ptr=None, ctx=None):
@@ -277,13 +105,12 @@ def pack_rows(x, geom=None, src_ptr=None, ctx=None):
 
 
 def ConvQ4(xq, Kq, B=None, scale=None, shift=None, resq=None, group=1, strides=(1, 1),
-           dilations=(1, 1), pads=(0, 0, 0, 0), act=ACT_NONE, alpha=0.0, w_layout=2, **_):
-    """layer.ConvFused on Q4 tensors: act((conv(x,K)+B)*scale + shift + res), all activations Q4.
-    w_layout=2: Kq from prepare_q4_weights(); w_layout=4: Winograd filters from
-    prepare_winograd_q4_weights(); 6 row-packed stem, 7 staged / 9 fused F(4x4,3x3), 8 fused 1-D F(4,3), 13 depthwise
-    (prepare_dw_q4_weights)."""
+           dilations=(1, 1), pads=(0, 0, 0, 0), act=ACT_NONE, alpha=0.0, w_layout=DIRECT_Q4, **_):
+    """layer.ConvFused on Q4 tensors: act((conv(x,K)+B)*scale + shift + res), all activations Q4.  Kq holds the filter
+    prepared for `w_layout` (conv_layouts.LAYOUTS): the direct kernel, the row-packed stem (NCHW input), depthwise, or one of
+    the same-signature Winograd / 1-D F(4,3) kernels."""
     _f32(xq, Kq, B, scale, shift, resq)
-    if w_layout == 6:
+    if w_layout == ROWPACK_Q4:
         # row-packed stem: the input is the reference's NCHW tensor, the output is Q4
         if is_q4(xq) or (resq is not None and not is_q4(resq)):
             raise TypeError("row-packed ConvQ4 takes an NCHW input (and a Q4 residual)")
@@ -319,28 +146,22 @@ def ConvQ4(xq, Kq, B=None, scale=None, shift=None, resq=None, group=1, strides=(
     y = _new_q4(n, cout, ho, wo, xq.ctx)
     if resq is not None and resq.shape != y.shape:
         raise ValueError("fused residual shape %s != conv output %s" % (resq.shape, y.shape))
-    if w_layout == 8:
-        if not w1d_q4_eligible(Kq.shape, group, strides, dilations, pads):
-            raise ValueError("1-D winograd filters serve 3x3 / stride 1 / pad 1 / group 1 convs only")
-        _lib.call("pl_conv2d_w1d4_q4_f32", xq.ctx.handle, xq.ptr, n, cin, h, w, Kq.ptr, cout, _ptr(B), y.ptr,
+    lay = LAYOUTS.get(w_layout)
+    if lay is not None and lay.kernel:
+        # the Winograd families and the fused 1-D F(4,3) share one signature
+        if not lay.eligible(Kq.shape, (n, cin, h, w), group=group, strides=strides, dilations=dilations, pads=pads):
+            raise ValueError("w_layout %d (%s) serves 3x3 / stride 1 / pad 1 / group 1 convs only%s"
+                             % (w_layout, lay.name, ", on maps whose sides are 7, 14 or 21" if w_layout == WINO43_Q4 else ""))
+        if w_layout == WF4_Q4 and any(a is not None and a.ptr % 16 for a in (B, scale, shift)):
+            raise ValueError("the fused F(4x4,3x3) kernel reads bias / scale / shift as 16-byte quads: misaligned parameter")
+        _lib.call(lay.kernel, xq.ctx.handle, xq.ptr, n, cin, h, w, Kq.ptr, cout, _ptr(B), y.ptr,
                   _ptr(scale), _ptr(shift), _ptr(resq), int(act), float(alpha))
         return y
-    if w_layout == 13:
+    if w_layout == DW_Q4:
         if not dw_q4_eligible(Kq.shape, group, strides, dilations, pads):
             raise ValueError("depthwise Q4 filters serve group == Cin == Cout convs with kh, kw <= 7 and symmetric pads")
         _lib.call("pl_conv2d_dw_q4_f32", xq.ctx.handle, xq.ptr, n, cin, h, w, Kq.ptr, kh, kw, _ptr(B), y.ptr,
                   strides[0], strides[1], dilations[0], dilations[1], pads[0], pads[1], pads[2], pads[3],
-                  _ptr(scale), _ptr(shift), _ptr(resq), int(act), float(alpha))
-        return y
-    if w_layout == 11 and (h not in (7, 14, 21) or w not in (7, 14, 21)):
-        raise ValueError("mixed-tile winograd filters serve maps whose sides are 7, 14 or 21")
-    if w_layout in (4, 7, 9, 11):
-        if not winograd_q4_eligible(Kq.shape, group, strides, dilations, pads):
-            raise ValueError("winograd Q4 filters serve 3x3 / stride 1 / pad 1 / group 1 convs only")
-        if w_layout == 9 and any(a is not None and a.ptr % 16 for a in (B, scale, shift)):
-            raise ValueError("the fused F(4x4,3x3) kernel reads bias / scale / shift as 16-byte quads: misaligned parameter")
-        _lib.call({4: "pl_conv2d_winograd_q4_f32", 7: "pl_conv2d_winograd4_q4_f32", 9: "pl_conv2d_wf4_q4_f32",
-                   11: "pl_conv2d_winograd43_q4_f32"}[w_layout], xq.ctx.handle, xq.ptr, n, cin, h, w, Kq.ptr, cout, _ptr(B), y.ptr,
                   _ptr(scale), _ptr(shift), _ptr(resq), int(act), float(alpha))
         return y
     _lib.call("pl_conv2d_q4_f32", xq.ctx.handle, xq.ptr, n, cin, h, w, Kq.ptr, cout, kh, kw,
@@ -350,30 +171,8 @@ def ConvQ4(xq, Kq, B=None, scale=None, shift=None, resq=None, group=1, strides=(
     return y
 
 
-def stem_pool_eligible(x_shape, k_shape, group=1, strides=(1, 1), dilations=(1, 1), pads=(0, 0, 0, 0), **_):
-    """Whether the row-packed conv + maxpool(3x3 / s2 / p1) kernel (csrc/conv_stem_pool_kernel.h) takes this conv."""
-    if len(x_shape) != 4 or int(group) != 1 or list(dilations) != [1, 1] or len(pads) != 4 or pads[0] != pads[2] or pads[1] != pads[3]:
-        return False
-    cout, cin, kh, kw = k_shape
-    ok = ctypes.c_int()
-    _lib.call("pl_conv2d_rowpacked_pool_supported", int(cin), int(x_shape[2]), int(x_shape[3]), int(cout), int(kh), int(kw),
-              int(strides[0]), int(strides[1]), int(pads[0]), int(pads[1]), ctypes.byref(ok))
-    return bool(ok.value) and x_shape[1] == cin
-
-
-def stem_pool_nchw_eligible(x_shape, k_shape, group=1, strides=(1, 1), dilations=(1, 1), pads=(0, 0, 0, 0), **_):
-    """Whether the stem + max-pool kernel can read this NCHW input itself (W % 4 == 0 on top of stem_pool_eligible)."""
-    if not stem_pool_eligible(x_shape, k_shape, group, strides, dilations, pads):
-        return False
-    cout, cin, kh, kw = k_shape
-    ok = ctypes.c_int()
-    _lib.call("pl_conv2d_stem_pool_nchw_supported", int(cin), int(x_shape[2]), int(x_shape[3]), int(cout), int(kh), int(kw),
-              int(strides[0]), int(strides[1]), int(pads[0]), int(pads[1]), ctypes.byref(ok))
-    return bool(ok.value)
-
-
 def ConvPoolQ4(x, Kq, B=None, scale=None, shift=None, group=1, strides=(1, 1), dilations=(1, 1), pads=(0, 0, 0, 0),
-               act=ACT_NONE, alpha=0.0, w_layout=10, out=None, src_ptr=None, ctx=None, strip_rows=0, **_):
+               act=ACT_NONE, alpha=0.0, w_layout=STEM_POOL, out=None, src_ptr=None, ctx=None, strip_rows=0, **_):
     """Row-packed stem conv (ConvQ4 w_layout 6: NCHW input, filter from prepare_rowpack_weights) with its fused tail, followed
     by layer.Maxpool(w=(3, 3), strides=(2, 2), pads=(1, 1, 1, 1)) (layer.py:71-72), in ONE kernel: only the pooled Q4 tensor is
     written.  Emitted by the plan compiler (Net._fuse_stem_pool) where the max-pool is the conv's only reader.
@@ -381,7 +180,7 @@ def ConvPoolQ4(x, Kq, B=None, scale=None, shift=None, group=1, strides=(1, 1), d
     copy.  A plan's static input then carries `x.prefed = (feed, pooled)`: whoever feeds the plan runs this kernel from the
     caller's batch straight into `pooled` (`out` / `src_ptr` / `ctx` below), and the captured pass starts behind it."""
     _f32(x, Kq, B, scale, shift)
-    if w_layout == 12 and out is None and getattr(x, "prefed", None) is not None:
+    if w_layout == STEM_POOL_NCHW and out is None and getattr(x, "prefed", None) is not None:
         return x.prefed[1]                         # a plan's static input: the feed has already run this step
     if is_q4(x) or not stem_pool_eligible(x.shape, Kq.shape, group, strides, dilations, pads):
         raise NotImplementedError("conv + maxpool in one kernel: NCHW 3-channel input, 7x7 / stride 2 / pad 3")
@@ -392,7 +191,7 @@ def ConvPoolQ4(x, Kq, B=None, scale=None, shift=None, group=1, strides=(1, 1), d
     pads, strides = [int(p) for p in pads], [int(s) for s in strides]
     ho, wo = conv_out_hw(h, w, kh, kw, strides, [1, 1], pads)
     cx = ctx or x.ctx
-    if w_layout == 12:
+    if w_layout == STEM_POOL_NCHW:
         xptr = x.ptr if src_ptr is None else src_ptr
         if w % 4 or xptr % 16:
             raise NotImplementedError("the NCHW stem + max-pool kernel needs W % 4 == 0 and a 16-byte aligned input")
