@@ -72,7 +72,7 @@ __host__ __device__ constexpr bool sp_nchw_real(int u, int kk) { return u < 10 |
 typedef float sp_f32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ float4 sp_max4(float4 a, float4 b) {
-    return make_float4(fmaxf(a.x, b.x), fmaxf(a.y, b.y), fmaxf(a.z, b.z), fmaxf(a.w, b.w));
+    return make_float4(max_nan(a.x, b.x), max_nan(a.y, b.y), max_nan(a.z, b.z), max_nan(a.w, b.w));
 }
 template <int SP_NB, bool NCHW>
 __global__ void __launch_bounds__(512) conv_stem_pool_kernel(const StemPoolArgs p) {
@@ -214,7 +214,7 @@ __global__ void __launch_bounds__(512) conv_stem_pool_kernel(const StemPoolArgs 
             const int prev15 = nb > 0 ? __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, pv[e]), 0x121, 0xf, 0xf, false) : 0;   // row_ror:1
             const float left = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(prev15, c, 0x111, 0xf, 0xf, false));              // row_shr:1
             const float right = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, c, 0x101, 0xf, 0xf, false));                  // row_shl:1
-            mo[e] = fmaxf(fmaxf(left, cv[e]), right);
+            mo[e] = max_nan(max_nan(left, cv[e]), right);
         }
         vprev = v;
         float4 *hp = HP + (k & 3) * SP_HP_CELLS + (mb * 4 + kk) * SP_PC;

@@ -40,6 +40,11 @@ inline Epilogue make_epilogue(const float *bias, const float *scale, const float
     return Epilogue{bias, scale, shift, res, act_code & 15, (float)alpha, (float)(1.0 - alpha), (act_code >> 4) & 1};
 }
 
+// np.maximum / np.minimum: a NaN operand propagates (fmaxf / fminf return the other operand), and -0 < +0.  gfx950
+// has v_maximum3_f32 / v_minimum3_f32, so these cost what fmaxf / fminf do.
+__device__ __forceinline__ float max_nan(float a, float b) { return __builtin_elementwise_maximum(a, b); }
+__device__ __forceinline__ float min_nan(float a, float b) { return __builtin_elementwise_minimum(a, b); }
+
 __device__ __forceinline__ float relu_ref(float v) {
     return v > 0.f ? v : __fmul_rn(v, 0.f);  // x*(x>0): negatives -> -0, NaN stays
 }

@@ -78,7 +78,9 @@ __global__ void __launch_bounds__(TPB) erf_lut_kernel(float *x, const float *lut
         v = __fmul_rn(v, v > 0.f ? 1.f : 0.f);   // x *= x>0
         v = __fmul_rn(v, 256.f);                 // x *= 256
         x[i] = v;
-        y[i] = lut[(int)(short)(int)v];
+        // a NaN (x NaN or +-inf: inf * 0) reads entry 0, as numpy's astype('int16') gives 0 for it; spelt out because
+        // converting a NaN to int is undefined in C++
+        y[i] = lut[v == v ? (int)(short)(int)v : 0];
     }
 }
 

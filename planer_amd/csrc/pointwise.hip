@@ -153,7 +153,7 @@ __global__ void __launch_bounds__(TPB) pool2d_kernel(const float *x, float *y, u
             for (int q = 0; q < kw; ++q) {
                 int wi = w0 + q;
                 float v = (hok && (unsigned)wi < (unsigned)W) ? xp[(size_t)hi * W + wi] : 0.f;
-                acc = MODE == 0 ? fmaxf(v, acc) : acc + v;
+                acc = MODE == 0 ? max_nan(v, acc) : acc + v;
             }
         }
         if (MODE == 1) acc = __fdiv_rn(acc, (float)(kh * kw));
@@ -184,13 +184,13 @@ __global__ void __launch_bounds__(TPB) maxpool_k3s2p1_x4(const float *x, float *
             const float4 a = *reinterpret_cast<const float4 *>(rp);
             const float4 b = *reinterpret_cast<const float4 *>(rp + 4);
             const float l = q ? rp[-1] : 0.f;               // column -1 is padding
-            acc.x = fmaxf(acc.x, fmaxf(l, fmaxf(a.x, a.y)));
-            acc.y = fmaxf(acc.y, fmaxf(a.y, fmaxf(a.z, a.w)));
-            acc.z = fmaxf(acc.z, fmaxf(a.w, fmaxf(b.x, b.y)));
-            acc.w = fmaxf(acc.w, fmaxf(b.y, fmaxf(b.z, b.w)));
+            acc.x = max_nan(acc.x, max_nan(l, max_nan(a.x, a.y)));
+            acc.y = max_nan(acc.y, max_nan(a.y, max_nan(a.z, a.w)));
+            acc.z = max_nan(acc.z, max_nan(a.w, max_nan(b.x, b.y)));
+            acc.w = max_nan(acc.w, max_nan(b.y, max_nan(b.z, b.w)));
         }
         if (top_pad) {
-            acc.x = fmaxf(acc.x, 0.f); acc.y = fmaxf(acc.y, 0.f); acc.z = fmaxf(acc.z, 0.f); acc.w = fmaxf(acc.w, 0.f);
+            acc.x = max_nan(acc.x, 0.f); acc.y = max_nan(acc.y, 0.f); acc.z = max_nan(acc.z, 0.f); acc.w = max_nan(acc.w, 0.f);
         }
         *reinterpret_cast<float4 *>(y + (size_t)row * (Wo4 * 4) + q * 4) = acc;
     }
@@ -265,7 +265,7 @@ __global__ void __launch_bounds__(TPB) splitk_reduce_kernel(const float *ws, int
 // every thread handles one pixel of one channel quad, i.e. one float4 per tap.  Padding lanes of
 // the last quad stay zero: max(-1e4, 0, ...) = 0, 0-sums, and the affine kernel writes them as 0.
 __device__ __forceinline__ float4 f4max(float4 a, float4 b) {
-    return make_float4(fmaxf(a.x, b.x), fmaxf(a.y, b.y), fmaxf(a.z, b.z), fmaxf(a.w, b.w));
+    return make_float4(max_nan(a.x, b.x), max_nan(a.y, b.y), max_nan(a.z, b.z), max_nan(a.w, b.w));
 }
 __device__ __forceinline__ float4 f4add(float4 a, float4 b) {
     return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
@@ -435,8 +435,8 @@ struct OpMath {
             case 2: return tanhf(x);
             case 3: return sqrtf(x);   // correctly rounded (hipcc default)
             case 4: return __fdiv_rn(1.f, x);
-            case 5: return fmaxf(fminf(__fadd_rn(__fmul_rn(x, p0), p1), 1.f), 0.f);   // layer.py:66-69
-            default: return fmaxf(fminf(x, p1), p0);                                   // layer.py:250-251
+            case 5: return max_nan(min_nan(__fadd_rn(__fmul_rn(x, p0), p1), 1.f), 0.f);   // layer.py:66-69
+            default: return max_nan(min_nan(x, p1), p0);                                     // layer.py:250-251
         }
     }
 };
@@ -524,17 +524,18 @@ __global__ void __launch_bounds__(TPB) upsample_linear_kernel(const float *x, fl
             c1 = min(q, p.W - 1);
         }
         const float *w = p.w + a * p.fw + b;
+        // the chain starts from +0 like the oracle's matrix product: an all -0 neighbourhood gives +0, not -0
         float v;
         if (p.terms == 4) {
-            v = __fmul_rn(xp[(size_t)r0 * p.W + c0], w[0]);
+            v = __fmaf_rn(xp[(size_t)r0 * p.W + c0], w[0], 0.f);
             v = __fmaf_rn(xp[(size_t)r0 * p.W + c1], w[kk], v);
             v = __fmaf_rn(xp[(size_t)r1 * p.W + c0], w[2 * kk], v);
             v = __fmaf_rn(xp[(size_t)r1 * p.W + c1], w[3 * kk], v);
         } else if (p.fw > 1) {
-            v = __fmul_rn(xp[(size_t)r0 * p.W + c0], w[0]);
+            v = __fmaf_rn(xp[(size_t)r0 * p.W + c0], w[0], 0.f);
             v = __fmaf_rn(xp[(size_t)r0 * p.W + c1], w[kk], v);
         } else {
-            v = __fmul_rn(xp[(size_t)r0 * p.W + c0], w[0]);
+            v = __fmaf_rn(xp[(size_t)r0 * p.W + c0], w[0], 0.f);
             v = __fmaf_rn(xp[(size_t)r1 * p.W + c0], w[kk], v);
         }
         y[i] = v;
@@ -593,11 +594,11 @@ __global__ void __launch_bounds__(TPB) reduce_rows_kernel(const float *x, float 
         float v = op == 2 ? -INFINITY : op == 3 ? INFINITY : 0.f;
         for (int i = lane; i < cols; i += 64) {
             const float t = xp[i];
-            v = op == 2 ? fmaxf(v, t) : op == 3 ? fminf(v, t) : v + t;
+            v = op == 2 ? max_nan(v, t) : op == 3 ? min_nan(v, t) : v + t;
         }
         for (int off = 32; off > 0; off >>= 1) {
             const float t = __shfl_xor(v, off, 64);
-            v = op == 2 ? fmaxf(v, t) : op == 3 ? fminf(v, t) : v + t;
+            v = op == 2 ? max_nan(v, t) : op == 3 ? min_nan(v, t) : v + t;
         }
         if (lane == 0) y[r] = op == 1 ? __fdiv_rn(v, (float)cols) : v;
     }

@@ -19,7 +19,7 @@ import numpy
 from . import _lib
 from .conv_layouts import (CONVT_Q4, convt_phase_eligible, prepare_conv_weights, prepare_convt_weights,  # noqa: F401
                            prepare_winograd_weights, winograd_eligible)
-from .hip import DeviceArray, _f32, asarray, empty
+from .hip import DeviceArray, _f32, asarray, empty, zeros
 
 ACT_NONE, ACT_RELU, ACT_LEAKY = _lib.ACT_NONE, _lib.ACT_RELU, _lib.ACT_LEAKY
 
@@ -54,6 +54,12 @@ def _host_values(t):
     if isinstance(t, DeviceArray):
         return t.host if t.host is not None else t.get()
     return numpy.asarray(t)
+
+
+def _full(shape, value, ctx):
+    """A tensor holding one value everywhere, for the empty extents numpy answers without arithmetic (the mean of an empty
+    slice is NaN): a host upload, no kernel launch -- the row kernels need a non-empty row."""
+    return empty(shape, ctx=ctx).set(numpy.full(shape, value, numpy.float32))
 
 
 def conv_out_hw(h, w, kh, kw, strides, dilations, pads):
@@ -100,6 +106,8 @@ def Dense(x, K, B, shp=None):
     _f32(x, K, B)
     m, k = x.shape
     n = K.shape[0]
+    if k == 0:                                          # numpy: an empty sum is +0, so every row is 0 + bias
+        return zeros((m, n), ctx=x.ctx) if B is None else _full((m, n), _host_values(B).reshape(1, n) + numpy.float32(0), x.ctx)
     y = empty((m, n), ctx=x.ctx)
     _lib.call("pl_gemm_f32", x.ctx.handle, x.ptr, m, k, K.ptr, n, 1, _ptr(B), y.ptr)
     return y
@@ -115,6 +123,12 @@ def MatMul(x, y):
     if y.shape[-2] != k:
         raise ValueError("matmul: inner dimensions differ: %s @ %s" % (x.shape, y.shape))
     n = y.shape[-1]
+    if k == 0:                                          # numpy: an empty sum is 0 (pl_gemm_f32 needs K > 0)
+        try:
+            lead = numpy.broadcast_shapes(x.shape[:-2], y.shape[:-2])
+        except ValueError:
+            raise ValueError("matmul: stacks %s and %s do not broadcast" % (x.shape, y.shape)) from None
+        return zeros(tuple(lead) + (m, n), ctx=x.ctx)
     if x.ndim == 2 and y.ndim == 2:
         out = empty((m, n), ctx=x.ctx)
         _lib.call("pl_gemm_f32", x.ctx.handle, x.ptr, m, k, y.ptr, n, 0, None, out.ptr)
@@ -143,9 +157,11 @@ def BatchNorm(x, K, B):
     c = x.shape[1]
     if K.size != c or B.size != c:
         raise ValueError("batchnorm: K/B must hold one value per channel")
-    inner = x.size // (x.shape[0] * c) if x.size else 1
     y = empty(x.shape, ctx=x.ctx)
-    _lib.call("pl_scale_shift_f32", x.ctx.handle, x.ptr, y.ptr, K.ptr, B.ptr, x.shape[0], c, max(inner, 1))
+    if not x.size:                                      # an empty x: nothing to scale (a clamped extent would write N*C)
+        return y
+    inner = x.size // (x.shape[0] * c)
+    _lib.call("pl_scale_shift_f32", x.ctx.handle, x.ptr, y.ptr, K.ptr, B.ptr, x.shape[0], c, inner)
     return y
 
 
@@ -219,9 +235,11 @@ def GlobalAveragePool(x):
     """layer.GlobalAveragePool (layer.py:77-78): mean over H,W, keepdims."""
     _f32(x)
     n, c = x.shape[:2]
-    inner = x.size // (n * c) if x.size else 1
+    inner = int(numpy.prod(x.shape[2:], dtype=numpy.int64))
+    if inner == 0:                                      # numpy: the mean of an empty slice is NaN
+        return _full((n, c) + (1,) * (x.ndim - 2), numpy.nan, x.ctx)
     y = empty((n, c) + (1,) * (x.ndim - 2), ctx=x.ctx)
-    _lib.call("pl_gap_f32", x.ctx.handle, x.ptr, y.ptr, n * c, max(inner, 1))
+    _lib.call("pl_gap_f32", x.ctx.handle, x.ptr, y.ptr, n * c, inner)
     return y
 
 
@@ -498,11 +516,17 @@ def _reduce(x, axes, keepdims, op):
     if any(not 0 <= a < nd for a in axes):
         raise ValueError("reduction: axis out of range")
     kept = [d for d in range(nd) if d not in axes]
-    src = x if axes == list(range(nd - len(axes), nd)) else Transpose(x, kept + axes)
     cols = int(numpy.prod([x.shape[a] for a in axes], dtype=numpy.int64))
-    rows = x.size // cols if cols else 0
+    if cols == 0:                                       # numpy over an empty axis: sum 0, mean NaN, max / min raise
+        if op >= 2:
+            raise ValueError("zero-size array to reduction operation %s which has no identity" % ("maximum", "minimum")[op - 2])
+        out = tuple(x.shape[d] for d in kept)
+        y = zeros(out, ctx=x.ctx) if op == 0 else _full(out, numpy.nan, x.ctx)
+        return y.reshape([1 if d in axes else x.shape[d] for d in range(nd)]) if keepdims else y
+    src = x if axes == list(range(nd - len(axes), nd)) else Transpose(x, kept + axes)
+    rows = x.size // cols
     y = empty(tuple(x.shape[d] for d in kept), ctx=x.ctx)
-    _lib.call("pl_reduce_f32", x.ctx.handle, src.ptr, y.ptr, rows, max(cols, 1), op)
+    _lib.call("pl_reduce_f32", x.ctx.handle, src.ptr, y.ptr, rows, cols, op)
     if keepdims:
         y = y.reshape([1 if d in axes else x.shape[d] for d in range(nd)])
     return y
@@ -994,7 +1018,9 @@ def InstanceNormalization(x, s, bias, epsilon=1e-5):
     if s.size != c or bias.size != c:
         raise ValueError("instancenormalization: one scale / bias value per channel")
     inner = int(numpy.prod(x.shape[2:], dtype=numpy.int64))
-    _lib.call("pl_instancenorm_f32", x.ctx.handle, x.ptr, s.ptr, bias.ptr, x.shape[0] * c, c, max(inner, 1), float(epsilon))
+    if inner == 0 or x.size == 0:                       # numpy leaves an empty x as it is; the kernel would write N*C values
+        return x
+    _lib.call("pl_instancenorm_f32", x.ctx.handle, x.ptr, s.ptr, bias.ptr, x.shape[0] * c, c, inner, float(epsilon))
     return x
 
 

@@ -24,7 +24,7 @@ from .conv_layouts import (dw_q4_eligible, prepare_dw_q4_weights, prepare_q4_wei
                            stem_pool_eligible, stem_pool_nchw_eligible, w1d_q4_eligible, winograd43_eligible, winograd_q4_eligible)
 from .conv_layouts import convt_phase_eligible as convt_q4_eligible, prepare_convt_weights as prepare_convt_q4_weights
 from .hip import DeviceArray, _f32, empty
-from .layer import ACT_NONE, _host_values, _ptr, conv_out_hw, convt_out_hw, convt_q4_call
+from .layer import ACT_NONE, _full, _host_values, _ptr, conv_out_hw, convt_out_hw, convt_q4_call
 
 
 def is_q4(a):
@@ -422,6 +422,8 @@ def GlobalAveragePoolQ4(xq):
     """layer.GlobalAveragePool (layer.py:77-78): Q4 in, plain (N, C, 1, 1) out."""
     _f32(xq)
     n, c, h, w = logical_shape(xq)
+    if h * w == 0:                                      # numpy: the mean of an empty slice is NaN
+        return _full((n, c, 1, 1), numpy.nan, xq.ctx)
     y = empty((n, c, 1, 1), ctx=xq.ctx)
     _lib.call("pl_gap_q4_f32", xq.ctx.handle, xq.ptr, y.ptr, n, c, h * w)
     return y
