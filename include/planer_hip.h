@@ -279,6 +279,9 @@ int pl_conv2d_rowpacked_pool_q4_f32(pl_ctx *ctx, const float *xp, int N, int Cin
 int pl_conv2d_stem_pool_nchw_supported(int Cin, int H, int W, int Cout, int kh, int kw, int sh, int sw, int pt,
                                        int pl, int *ok);
 int pl_conv2d_stem_nchw_filter_elems(int Cout, size_t *elems);
+/* The k order of that filter (host query, no device): tab[4 q + j] = 8 rho + kw + 1 for element j of k-quad q, rho = 3 * filter
+ * row + channel, kw = -1 a zero filter value; -1 where the slot holds no tap.  37 quads (K = 148): n >= 148. */
+int pl_conv2d_stem_nchw_korder(int *tab, int n);
 int pl_conv2d_prepare_stem_nchw_f32(pl_ctx *ctx, const float *w, int Cout, float *out);
 int pl_conv2d_stem_pool_nchw_q4_f32(pl_ctx *ctx, const float *x, int N, int H, int W, const float *wq, int Cout,
                                     const float *bias, float *yq, const float *scale, const float *shift,

@@ -1757,6 +1757,14 @@ int pl_conv2d_stem_nchw_filter_elems(int Cout, size_t *elems) {
     return PL_OK;
 }
 
+// The NCHW stem's k order as the filter pack lays it out: tab[4 q + j] = 8 rho + kw + 1 for element j of k-quad q (rho = 3 fr + c,
+// kw = -1 is a zero filter value), -1 for a slot without a tap; quads 0 .. SP_NCHW_QUADS - 1.  A host query (tests).
+int pl_conv2d_stem_nchw_korder(int *tab, int n) {
+    PL_REQUIRE(tab && n >= 4 * SP_NCHW_QUADS, PL_EINVAL, "pl_conv2d_stem_nchw_korder: need %d entries", 4 * SP_NCHW_QUADS);
+    for (int i = 0; i < 4 * SP_NCHW_QUADS; ++i) tab[i] = sp_nchw_quad_tap(i >> 2, i & 3);
+    return PL_OK;
+}
+
 int pl_conv2d_prepare_stem_nchw_f32(pl_ctx *ctx, const float *w, int Cout, float *out) {
     PL_REQUIRE(ctx && w && out, PL_EINVAL, "pl_conv2d_prepare_stem_nchw_f32: null pointer");
     PL_REQUIRE(Cout > 0, PL_EINVAL, "pl_conv2d_prepare_stem_nchw_f32: bad shape");
@@ -1819,8 +1827,9 @@ int pl_conv2d_stem_pool_nchw_q4_f32(pl_ctx *ctx, const float *x, int N, int H, i
     char buf[112];
     snprintf(buf, sizeof buf, "stem+maxpool(nchw) 64co x 2 rows x %dpx, strips=%d of %d rows, chunks=%d blocks=%lld", 16 * nb, a.strips, a.prows, a.chunks, blocks);
     ctx->last_plan = buf;
+    // executed MFMA work: 2 x steps conv rows per strip, 16 nb columns per chunk, K = 148 (sp_nchw_tap)
     ctx->last_gemm[0] = 1; ctx->last_gemm[1] = (long long)a.cout_blocks * 64;
-    ctx->last_gemm[2] = (long long)N * a.strips * a.chunks * 2 * a.steps * 16 * nb; ctx->last_gemm[3] = 16 * SP_GROUPS;
+    ctx->last_gemm[2] = (long long)N * a.strips * a.chunks * 2 * a.steps * 16 * nb; ctx->last_gemm[3] = 4 * SP_NCHW_QUADS;
     return PL_OK;
 }
 

@@ -35,12 +35,15 @@
 // kernel of its own: 40 MB moved to re-lay a 19 MB batch).  The row buffer then holds one row per (input row, channel):
 // [4 zeros | the row's pixels from column 2 x0 - 4 on], whole 16-byte cells of the NCHW row landing by LDS-DMA where the
 // packed rows did (W % 4 == 0 keeps every cell inside or outside its row; cells outside arrive as zeros through the range
-// check: they are the conv's padding).  K is ordered for it: a k-quad = four consecutive taps kw = 4 half - 1 .. 4 half + 2
-// of one (filter row, channel) -- tap -1 is a zero filter value, so the seven taps of a row take two quads that start on
-// 16-byte cells; conv column l reads its quad at float 2 l + 4 half of the LDS row (8-byte aligned pairs, as before).  The 42
-// real quads + 2 zero quads are grouped so that the two quads a half-wave reads together (lanes 0-31: kk = 0, 1) sit two LDS
-// rows apart: a row is 32 NB + 16 floats, two rows = 32 banks (mod 64) -- conflict-free like the packed layout.  Filter packed
-// by pl_conv2d_prepare_stem_nchw_f32 in that order; everything behind the fragment reads is the same code.
+// check: they are the conv's padding).  Tap kw of (filter row, channel) rho = 3 fr + c for conv column l sits at float
+// 2 l + kw + 1 of LDS row rho: the aligned pairs (kw 1, 2), (3, 4), (5, 6) are ds_read_b64 fragments, kw 0 is a ds_read_b32
+// on its own.  K = 148 (147 taps + 1 zero), ordered by sp_nchw_tap: 9 groups of 4 k-quads and one tail MFMA of 4 taps.
+// The lane quarters kk = 0..3 of a group read rows rho0 + 0, 2, 1, 3 (blocks of 4 rows): the quarters a half-wave reads
+// together (kk = 0, 1 and 2, 3) sit two LDS rows apart, and a row is 32 NB + 16 floats, so two rows = 32 banks (mod 64) --
+// conflict-free for the b64 reads.  Groups 0-6 are two pairs per quad (2 x b64), groups 7 and 8 a pair and two kw-0 taps
+// (b64 + 2 x b32; group 8's pairs are row 20's, and its last quarter takes (kw -1, 0) of row 20, the one zero), the tail one
+// kw-0 tap per lane (b32).  The b32 reads of kw 0 are all odd floats: 2-way conflicts that the 37 instead of 44 MFMAs pay for.
+// Filter packed by pl_conv2d_prepare_stem_nchw_f32 in that order; everything behind the fragment reads is the same code.
 struct StemPoolArgs {
     const float *xp;       // row-packed image [N][Hp][rowf] (zero border included); NCHW: the input tensor [N][3][H][W]
     const float *wq;       // [Qpad][Cout][4] row-packed filter
@@ -60,14 +63,24 @@ constexpr int SP_NB_MAX = 7;                     // 16-pixel blocks per conv row
 constexpr int SP_KH = 7, SP_RQ = 6;              // filter rows, k-quads per filter row (kw * Cin = 21 floats -> 6 quads)
 constexpr int SP_GROUPS = (SP_KH * SP_RQ + 3) / 4;      // 11 groups of 4 k-quads (42 real + 2 zero quads)
 constexpr int SP_XROWS = 9;                      // input rows under a conv-row pair: 2 r .. 2 r + 8
-constexpr int SP_W_FLOATS = 4 * SP_GROUPS * 64 * 4;             // 44 quads x 64 channels x 4
 constexpr int SP_PROWS = 7;                      // pooled rows per strip
 constexpr int sp_xrow(int nb) { return 96 * nb + 32; }          // floats per staged input row: 6 per conv column + the last window's quads
 constexpr int sp_xrow_nchw(int nb) { return 32 * nb + 16; }     // NCHW: floats per staged (input row, channel): 2 per conv column + 4 left + the last window's quad
-// NCHW k order: group u reads (filter row, channel) pairs rho = 3 fr + c two apart -- kk = 0 / 2: rho_a (taps half 0 / 1), kk = 1 / 3:
-// rho_b = rho_a + 2; group 10 pairs rho 20 with a zero-filter quad that reads row 18
-__host__ __device__ constexpr int sp_nchw_rho(int u, int kk) { return u < 10 ? 4 * (u >> 1) + (u & 1) + 2 * (kk & 1) : ((kk & 1) ? 18 : 20); }
-__host__ __device__ constexpr bool sp_nchw_real(int u, int kk) { return u < 10 || !(kk & 1); }
+// NCHW k order: (group u, lane quarter kk, element j) -> 8 rho + kw + 1 (rho = 3 fr + c, kw = -1 .. 6; kw + 1 is the tap's float
+// offset in its LDS row), or -1 where the slot holds no tap.  Element j feeds MFMA j of the group; the tail (u = 9) is one MFMA,
+// element 0 of each quarter.  Quarter kk reads block rows 4 b + (0, 2, 1, 3)[kk].  kw = -1 is a zero filter value.
+constexpr int SP_NCHW_GROUPS = 9, SP_NCHW_QUADS = 37;     // 36 quads in groups + the tail's 4 taps: K = 148
+__host__ __device__ constexpr int sp_nchw_tap(int u, int kk, int j) {
+    const int d = 2 * (kk & 1) + (kk >> 1);
+    if (u < 7 || (u == 7 && j < 2)) {                    // pair slot s = 2 u + j / 2: block s / 3, taps kw = f - 1, f
+        const int s = 2 * u + (j >> 1), b = s / 3, f = 2 * (s % 3) + 2;
+        return 8 * (4 * b + d) + f + (j & 1);
+    }
+    if (u == 8 && j < 2) return 8 * 20 + (kk == 3 ? 0 : 2 * kk + 2) + (j & 1);   // row 20's pairs; (kw -1, 0) in quarter 3
+    if (u < 9) return 8 * (4 * (2 * (u - 7) + (j - 2)) + d) + 1;                 // kw 0 of blocks 0, 1 (u = 7), 2, 3 (u = 8)
+    if (u == 9 && j == 0) return 8 * (16 + d) + 1;                                // kw 0 of block 4
+    return -1;
+}
 
 typedef float sp_f32x4 __attribute__((ext_vector_type(4)));
 
@@ -80,9 +93,11 @@ __global__ void __launch_bounds__(512) conv_stem_pool_kernel(const StemPoolArgs 
     constexpr int SP_PXF = NCHW ? 32 : 96;           // floats of a staged row per 16-column pixel block
     constexpr int SP_PC = 8 * SP_NB;                 // pooled columns a workgroup's conv columns hold
     constexpr int SP_HP_CELLS = 16 * SP_PC;          // one horizontally pooled conv row: 16 channel quads x SP_PC columns
+    constexpr int SP_NQ = NCHW ? SP_NCHW_QUADS : 4 * SP_GROUPS;   // filter k-quads in LDS
+    constexpr int SP_NG = NCHW ? SP_NCHW_GROUPS + 1 : SP_GROUPS;  // k steps: groups of 4 k-quads (+ the NCHW order's tail MFMA)
     // separate LDS objects: an LDS-DMA into one row buffer must not hold up the fragment reads of the other (the compiler
     // orders LDS-DMA against later LDS accesses object by object)
-    __shared__ __attribute__((aligned(16))) float Wf[SP_W_FLOATS];
+    __shared__ __attribute__((aligned(16))) float Wf[SP_NQ * 256];
     __shared__ __attribute__((aligned(16))) float X0[SP_X_FLOATS], X1[SP_X_FLOATS];
     __shared__ __attribute__((aligned(16))) float4 HP[4 * SP_HP_CELLS];
     typedef __attribute__((address_space(3))) float lds_float;
@@ -110,8 +125,8 @@ __global__ void __launch_bounds__(512) conv_stem_pool_kernel(const StemPoolArgs 
     const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.wq), 0, p.w_bytes, 0x00020000);
     constexpr int OOB = (int)0x80000000;
 
-    // ---- the filter block: [44 quads][64 channels] cells of 16 bytes, 44 pieces of 64 cells ----
-    for (int pc = wave; pc < 4 * SP_GROUPS; pc += 8) {     // piece pc = k-quad pc (64 channels = 64 cells)
+    // ---- the filter block: [SP_NQ quads][64 channels] cells of 16 bytes, SP_NQ pieces of 64 cells ----
+    for (int pc = wave; pc < SP_NQ; pc += 8) {     // piece pc = k-quad pc (64 channels = 64 cells)
         const int co = co0 + lane;
         const int off = co < p.Cout ? (int)(((unsigned)pc * (unsigned)p.Cout + (unsigned)co) << 4) : OOB;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(wrsrc, (lds_float *)(Wf + pc * 256), 16, off, 0, 0, 0);
@@ -146,15 +161,18 @@ __global__ void __launch_bounds__(512) conv_stem_pool_kernel(const StemPoolArgs 
     };
     load_rows(0, std::false_type{});
 
-    // per-lane fragment offsets: group u, this lane's k-quad q = 4 u + kk -> (filter row, quad of the row); the two padding
-    // quads (q = 42, 43: zero filter values) read the data of quads 0, 1
-    int boff[SP_GROUPS];
+    // per-lane fragment offsets.  Row-packed: group u, this lane's k-quad q = 4 u + kk -> (filter row, quad of the row); the two
+    // padding quads (q = 42, 43: zero filter values) read the data of quads 0, 1.  NCHW: xb + the slot's offset for quarter 0
+    // (sp_nchw_tap: rows of a slot differ between quarters by (0, 2, 1, 3)[kk] alone), except group 8's pairs (x8).
+    int boff[NCHW ? 1 : SP_GROUPS];
+    int xb = 0, x8 = 0;
+    if constexpr (NCHW) {
+        xb = (6 * rsel + 2 * (kk & 1) + (kk >> 1)) * SP_XROW + 2 * li;            // + 32 nb per pixel block
+        const int t8 = 8 * 20 + (kk == 3 ? 0 : 2 * kk + 2);                       // = sp_nchw_tap(8, kk, 0)
+        x8 = (6 * rsel + (t8 >> 3)) * SP_XROW + (t8 & 7) + 2 * li;
+    } else {
 #pragma unroll
-    for (int u = 0; u < SP_GROUPS; ++u) {
-        if constexpr (NCHW) {
-            const int rho = (kk & 1) ? sp_nchw_rho(u, 1) : sp_nchw_rho(u, 0);
-            boff[u] = (6 * rsel + rho) * SP_XROW + 4 * (kk >> 1) + 2 * li;       // + 32 nb per pixel block
-        } else {
+        for (int u = 0; u < SP_GROUPS; ++u) {
             int q = 4 * u + kk;
             if (q >= SP_KH * SP_RQ) q -= SP_KH * SP_RQ;
             const int fr = q / SP_RQ, jq = q - fr * SP_RQ;
@@ -162,6 +180,7 @@ __global__ void __launch_bounds__(512) conv_stem_pool_kernel(const StemPoolArgs 
         }
     }
     const int aoff = (kk * 64 + mb * 16 + li) * 4;                          // + 1024 u: quad 4 u + kk, channel 16 mb + li
+    const int atail = 256 * SP_NCHW_GROUPS * 4 + (mb * 16 + li) * 4 + kk;  // NCHW tail: element kk of quad 36, channel 16 mb + li
 
     // tail parameters of this lane's channel quad (a lane of the 16x16 C layout holds rows 4 (lane / 16) .. + 3 of its column)
     const int cq = (int)cob * 16 + mb * 4 + kk;
@@ -256,27 +275,52 @@ __global__ void __launch_bounds__(512) conv_stem_pool_kernel(const StemPoolArgs 
         float4 fa[2];
         float2 fb0[2][SP_NB], fb1[2][SP_NB];
         auto fetch = [&](int u, int set) {
-            fa[set] = *reinterpret_cast<const float4 *>(Wf + aoff + 1024 * u);
+            if constexpr (NCHW) {
+                // slot offsets of quarter 0 (compile-time constants once u is unrolled: immediate offsets on xb)
+                constexpr auto so = [](int t) { return (t >> 3) * SP_XROW + (t & 7); };
+                const int s0 = so(sp_nchw_tap(u, 0, 0)), s2 = so(sp_nchw_tap(u, 0, 2)), s3 = so(sp_nchw_tap(u, 0, 3));
+                if (u < SP_NCHW_GROUPS) fa[set] = *reinterpret_cast<const float4 *>(Wf + aoff + 1024 * u);
+                else fa[set].x = Wf[atail];
 #pragma unroll
-            for (int nb = 0; nb < SP_NB; ++nb) {
-                const float *src = Xb + boff[u] + SP_PXF * nb;
-                fb0[set][nb] = *reinterpret_cast<const float2 *>(src);
-                fb1[set][nb] = *reinterpret_cast<const float2 *>(src + 2);
+                for (int nb = 0; nb < SP_NB; ++nb) {
+                    const float *src = Xb + SP_PXF * nb;
+                    if (u < 7) {                                       // two pairs
+                        fb0[set][nb] = *reinterpret_cast<const float2 *>(src + xb + s0);
+                        fb1[set][nb] = *reinterpret_cast<const float2 *>(src + xb + s2);
+                    } else if (u < SP_NCHW_GROUPS) {                   // a pair and two kw-0 taps
+                        fb0[set][nb] = *reinterpret_cast<const float2 *>(src + (u == 8 ? x8 : xb + s0));
+                        fb1[set][nb].x = src[xb + s2];
+                        fb1[set][nb].y = src[xb + s3];
+                    } else {                                           // the tail: one kw-0 tap
+                        fb0[set][nb].x = src[xb + s0];
+                    }
+                }
+            } else {
+                fa[set] = *reinterpret_cast<const float4 *>(Wf + aoff + 1024 * u);
+#pragma unroll
+                for (int nb = 0; nb < SP_NB; ++nb) {
+                    const float *src = Xb + boff[u] + SP_PXF * nb;
+                    fb0[set][nb] = *reinterpret_cast<const float2 *>(src);
+                    fb1[set][nb] = *reinterpret_cast<const float2 *>(src + 2);
+                }
             }
         };
         fetch(0, 0);
 #pragma unroll
-        for (int u = 0; u < SP_GROUPS; ++u) {
+        for (int u = 0; u < SP_NG; ++u) {
             const int set = u & 1;
-            if (u + 1 < SP_GROUPS) fetch(u + 1, set ^ 1);
+            const bool tail = NCHW && u == SP_NCHW_GROUPS;            // one MFMA: element 0 of each quarter
+            if (u + 1 < SP_NG) fetch(u + 1, set ^ 1);
 #pragma unroll
             for (int nb = 0; nb < SP_NB; ++nb) acc[nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[set].x, fb0[set][nb].x, acc[nb], 0, 0, 0);
+            if (!tail) {
 #pragma unroll
-            for (int nb = 0; nb < SP_NB; ++nb) acc[nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[set].y, fb0[set][nb].y, acc[nb], 0, 0, 0);
+                for (int nb = 0; nb < SP_NB; ++nb) acc[nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[set].y, fb0[set][nb].y, acc[nb], 0, 0, 0);
 #pragma unroll
-            for (int nb = 0; nb < SP_NB; ++nb) acc[nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[set].z, fb1[set][nb].x, acc[nb], 0, 0, 0);
+                for (int nb = 0; nb < SP_NB; ++nb) acc[nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[set].z, fb1[set][nb].x, acc[nb], 0, 0, 0);
 #pragma unroll
-            for (int nb = 0; nb < SP_NB; ++nb) acc[nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[set].w, fb1[set][nb].y, acc[nb], 0, 0, 0);
+                for (int nb = 0; nb < SP_NB; ++nb) acc[nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[set].w, fb1[set][nb].y, acc[nb], 0, 0, 0);
+            }
             // what rides along: the previous step's tail (two pixel blocks per group, groups 0-3), the hand-over barrier, the
             // pooled row (groups 4, 5) -- early enough for its stores to be complete when the step's closing barrier asks
             // (vmcnt counts stores: issued in groups 8-9 they cost ~1 us of exposed latency per step)
@@ -307,22 +351,21 @@ __global__ void __launch_bounds__(512) conv_stem_pool_kernel(const StemPoolArgs 
     else drain(accA);
 }
 
-// OIHW stem filter [Cout][3][7][7] -> [k-quad q][Cout][4] in the NCHW kernel's k order: quad q = 4 u + kk holds taps
-// kw = 4 (kk >> 1) - 1 .. + 3 of (filter row, channel) rho = sp_nchw_rho(u, kk); tap -1, the padding quad of group 10 and
-// quads 44 .. 47 are zeros.
+// OIHW stem filter [Cout][3][7][7] -> [k-quad q][Cout][4] in the NCHW kernel's k order: element j of quad q = 4 u + kk (u < 9)
+// holds tap sp_nchw_tap(u, kk, j), element kk of quad 36 the tail's sp_nchw_tap(9, kk, 0); tap kw = -1 and quads 37 .. 47 are zeros.
+__host__ __device__ constexpr int sp_nchw_quad_tap(int q, int j) {
+    return q < 4 * SP_NCHW_GROUPS ? sp_nchw_tap(q >> 2, q & 3, j) : q == 4 * SP_NCHW_GROUPS ? sp_nchw_tap(SP_NCHW_GROUPS, j, 0) : -1;
+}
 __global__ void __launch_bounds__(256) pack_filter_stem_nchw_kernel(const float *w, float4 *out, unsigned total, int Cout) {
     const unsigned i = blockIdx.x * 256u + threadIdx.x;
     if (i >= total) return;
     const int q = (int)(i / (unsigned)Cout), co = (int)(i - (unsigned)q * (unsigned)Cout);
     float v[4] = {0.f, 0.f, 0.f, 0.f};
-    const int u = q >> 2, kk = q & 3;
-    if (u < SP_GROUPS && sp_nchw_real(u, kk)) {
-        const int rho = sp_nchw_rho(u, kk), fr = rho / 3, c = rho - 3 * fr, half = kk >> 1;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int kw = 4 * half + j - 1;
-            if (kw >= 0 && kw < 7) v[j] = w[((co * 3 + c) * SP_KH + fr) * 7 + kw];
-        }
+    for (int j = 0; j < 4; ++j) {
+        const int t = sp_nchw_quad_tap(q, j);
+        const int rho = t >> 3, kw = (t & 7) - 1, fr = rho / 3, c = rho - 3 * fr;
+        if (t >= 0 && kw >= 0) v[j] = w[((co * 3 + c) * SP_KH + fr) * 7 + kw];
     }
     out[i] = make_float4(v[0], v[1], v[2], v[3]);
 }
