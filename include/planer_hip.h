@@ -565,6 +565,10 @@ int pl_splitk_reduce_f32(pl_ctx *ctx, const float *ws, int splits, float *y,
                          int N, int C, int inner, const float *bias,
                          const float *scale, const float *shift,
                          const float *res, int act, double alpha);
+/* The streaming kernels launch at most 8 blocks of 256 threads per CU and stride over the rest; those that count in 32 bits
+ * accept `total` work items only if no counter can wrap: total + blocks * 256 <= 2^32.  *ok = that verdict for a device of
+ * cu_count CUs (<= 0: 256).  Host query, no device. */
+int pl_stream_loop32_ok(size_t total, int cu_count, int *ok);
 
 /* ---- multi-GPU (RCCL over xGMI): one process per GPU -------------------- */
 /* The reference has no distributed code.  The forward pass shards by batch

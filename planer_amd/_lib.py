@@ -174,6 +174,7 @@ SIGNATURES = {
     "pl_tile_accumulate_f32": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I],
     "pl_tile_normalise_f32": [_P, _P, _P, _I, _I, _I],
     "pl_splitk_reduce_f32": [_P, _P, _I, _P, _I, _I, _I, _P, _P, _P, _P, _I, c_double],
+    "pl_stream_loop32_ok": [_Z, _I, POINTER(c_int)],
     "pl_comm_unique_id": [_P],
     "pl_comm_init_rank": [_P, _I, _I, _P],
     "pl_comm_bcast": [_P, _P, _Z, _I],

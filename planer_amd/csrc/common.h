@@ -122,3 +122,12 @@ static inline int pl_experiment(const char *key, int dflt) {
 }
 
 static inline unsigned cdiv(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
+
+// The streaming launch of pointwise.hip and head_ops.hip: blocks of PL_STREAM_TPB threads, at most 8 per CU, and a grid-stride
+// loop over the rest (pointwise.hip defines both).
+constexpr int PL_STREAM_TPB = 256;
+unsigned pl_stream_grid(int cu_count, size_t work_items);
+// Does `for (unsigned i = first; i < total; i += stride)` of that launch end?  Only if no thread's i can wrap past 2^32 to a value
+// below total again: total + stride <= 2^32.  (On 256 CUs the stride is 2^19 and divides 2^32, so a wrapped loop never ends.)
+// Every entry point whose kernel counts in 32 bits up to a guard of 2^32 asks this instead of `total < 2^32`.
+bool pl_loop32_ok(int cu_count, size_t total);

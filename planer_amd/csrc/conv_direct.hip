@@ -802,6 +802,10 @@ int run_plan(pl_ctx *ctx, const ConvArgs &a0, const Plan &pl, bool avec, float *
         char buf[96];
         snprintf(buf, sizeof buf, "%s tiles=%d dp=%d split=%d occ=%d", ci.name, T, t1, s2, pl.occ);
         ctx->last_plan = buf;
+        // a Q4 output of 2 GiB or more: store_tile_q4 addresses it by pointer, not through a buffer descriptor.  A label of the
+        // host's choice (the same `!y_bytes` the kernel branches on), not evidence of what the kernel did: tests that assert it
+        // compare the output as well
+        if (ci.tap == 2 && !ci.ks && !a.ph_sh && !a.y_bytes) ctx->last_plan += " ptrtail";
         // what the matrix cores execute: whole tiles and whole K chunks
         const int kq = ci.tap == 2 ? a.Qtot * 4 : a.K;
         ctx->last_gemm[0] = a.groups;
@@ -1984,7 +1988,8 @@ static int q4_convert(pl_ctx *ctx, const float *x, float *y, int N, int C, int H
     PL_REQUIRE(N >= 0 && C > 0 && HW > 0, PL_EINVAL, "q4 layout conversion: bad shape");
     const int Cq = (C + 3) / 4;
     const size_t total = (size_t)N * Cq * HW;
-    PL_REQUIRE(total < (1ull << 29), PL_EUNSUPPORTED, "q4 layout conversion: tensor above 2 GiB");
+    // `total` counts pixel quads of 16 bytes; the kernels index quads in 32 bits and every float offset in 64
+    PL_REQUIRE(total < (1ull << 29), PL_EUNSUPPORTED, "q4 layout conversion: Q4 tensor of 2^29 pixel quads (8 GiB) or more");
     PL_REQUIRE((reinterpret_cast<uintptr_t>(to_q4 ? y : x) & 15u) == 0, PL_EINVAL,
                "q4 layout conversion: Q4 tensor must be 16-byte aligned");
     if (total == 0) return PL_OK;

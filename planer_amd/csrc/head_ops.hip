@@ -8,14 +8,9 @@
 
 namespace {
 
-constexpr int TPB = 256;
+constexpr int TPB = PL_STREAM_TPB;
 
-inline unsigned stream_grid(pl_ctx *ctx, size_t work_items) {
-    size_t blocks = (work_items + TPB - 1) / TPB;
-    size_t cap = (size_t)(ctx->cu_count > 0 ? ctx->cu_count : 256) * 8;
-    if (blocks > cap) blocks = cap;
-    return blocks ? (unsigned)blocks : 1u;
-}
+inline unsigned stream_grid(pl_ctx *ctx, size_t work_items) { return pl_stream_grid(ctx->cu_count, work_items); }
 
 // layer.Equal / Greater / GreaterOrEqual (layer.py:204, 228, 232): numpy comparison -> bool bytes
 __global__ void __launch_bounds__(TPB) compare_kernel(const float *a, const float *b, unsigned char *y, size_t n, int op,
@@ -89,22 +84,23 @@ __global__ void __launch_bounds__(TPB) erf_lut_kernel(float *x, const float *lut
 __global__ void __launch_bounds__(TPB) instancenorm_kernel(float *x, const float *s, const float *b, int rows, int C,
                                                            int inner, float eps) {
     const int lane = threadIdx.x & 63;
-    const int wpb = TPB / 64;
-    for (int row = blockIdx.x * wpb + (threadIdx.x >> 6); row < rows; row += gridDim.x * wpb) {
+    const unsigned wpb = TPB / 64;
+    // unsigned: rows <= 2^31 - 1, so row + gridDim.x * wpb cannot wrap (a signed counter overflowed near 2^31 rows)
+    for (unsigned row = blockIdx.x * wpb + (threadIdx.x >> 6); row < (unsigned)rows; row += gridDim.x * wpb) {
         float *p = x + (size_t)row * inner;
         float sum = 0.f;
-        for (int i = lane; i < inner; i += 64) sum += p[i];
+        for (unsigned i = lane; i < (unsigned)inner; i += 64) sum += p[i];
         for (int o = 32; o; o >>= 1) sum += __shfl_xor(sum, o);
         const float mean = sum / (float)inner;
         float sq = 0.f;
-        for (int i = lane; i < inner; i += 64) {
+        for (unsigned i = lane; i < (unsigned)inner; i += 64) {
             const float d = p[i] - mean;
             sq += d * d;
         }
         for (int o = 32; o; o >>= 1) sq += __shfl_xor(sq, o);
         const float dev = powf(sq / (float)inner + eps, 0.5f);
-        const float sc = s[row % C], k = __fdiv_rn(sc, dev), off = __fsub_rn(b[row % C], __fdiv_rn(__fmul_rn(sc, mean), dev));
-        for (int i = lane; i < inner; i += 64) p[i] = __fadd_rn(__fmul_rn(p[i], k), off);
+        const float sc = s[row % (unsigned)C], k = __fdiv_rn(sc, dev), off = __fsub_rn(b[row % (unsigned)C], __fdiv_rn(__fmul_rn(sc, mean), dev));
+        for (unsigned i = lane; i < (unsigned)inner; i += 64) p[i] = __fadd_rn(__fmul_rn(p[i], k), off);
     }
 }
 
@@ -310,9 +306,10 @@ __global__ void __launch_bounds__(TPB) topk_select_kernel(const float *x, float 
 __device__ __forceinline__ float ref_sigmoid(float v) { return __fdiv_rn(1.f, __fadd_rn(expf(-v), 1.f)); }
 __global__ void __launch_bounds__(TPB) lstm_cell_kernel(const float *gx, const float *gh, const float *b, const float *c_prev,
                                                         float *h, float *c, int N, int H) {
-    const int total = N * H;
-    for (int i = blockIdx.x * TPB + threadIdx.x; i < total; i += gridDim.x * TPB) {
-        const int n = i / H, j = i - n * H;
+    // unsigned: total < 2^31 (host check) and the stride is at most 2^20, so i + stride stays below 2^32 (a signed i overflowed)
+    const unsigned total = (unsigned)N * (unsigned)H, stride = gridDim.x * TPB;
+    for (unsigned i = blockIdx.x * TPB + threadIdx.x; i < total; i += stride) {
+        const int n = (int)(i / (unsigned)H), j = (int)(i - (unsigned)n * (unsigned)H);
         float g[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) {

@@ -8,14 +8,10 @@
 
 namespace {
 
-constexpr int TPB = 256;
+constexpr int TPB = PL_STREAM_TPB;
 
-inline unsigned stream_grid(pl_ctx *ctx, size_t work_items) {
-    size_t blocks = (work_items + TPB - 1) / TPB;
-    size_t cap = (size_t)(ctx->cu_count > 0 ? ctx->cu_count : 256) * 8;
-    if (blocks > cap) blocks = cap;
-    return blocks ? (unsigned)blocks : 1u;
-}
+inline unsigned stream_grid(pl_ctx *ctx, size_t work_items) { return pl_stream_grid(ctx->cu_count, work_items); }
+inline bool loop32_ok(pl_ctx *ctx, size_t total) { return pl_loop32_ok(ctx->cu_count, total); }
 
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
@@ -90,7 +86,9 @@ __global__ void __launch_bounds__(TPB) affine_plane(const float *x, float *y, co
     const float t = shift ? shift[c] : 0.f;
     const float *xp = x + (size_t)plane * inner;
     float *yp = y + (size_t)plane * inner;
-    for (int i = blockIdx.x * TPB + threadIdx.x; i < inner; i += gridDim.x * TPB) {
+    // unsigned: inner < 2^31 and the stride is about inner / 4, so i + stride stays below 2^32 (a signed i overflowed)
+    const unsigned stride = gridDim.x * TPB;
+    for (unsigned i = blockIdx.x * TPB + threadIdx.x; i < (unsigned)inner; i += stride) {
         float v = xp[i];
         if (HAS_SCALE) v = __fmul_rn(v, s);
         yp[i] = __fadd_rn(v, t);
@@ -235,12 +233,12 @@ __global__ void __launch_bounds__(TPB) copy2d_scalar(float *dst, size_t dst_pitc
 // ---- global average pool: one wave64 per (n,c) row ------------------------------
 __global__ void __launch_bounds__(TPB) gap_kernel(const float *x, float *y, int rows, int inner, float inv) {
     const int lane = threadIdx.x & 63;
-    const int wave = (blockIdx.x * TPB + threadIdx.x) >> 6;
-    const int nwaves = (gridDim.x * TPB) >> 6;
-    for (int r = wave; r < rows; r += nwaves) {
+    const unsigned wave = (blockIdx.x * TPB + threadIdx.x) >> 6;
+    const unsigned nwaves = (gridDim.x * TPB) >> 6;
+    for (unsigned r = wave; r < (unsigned)rows; r += nwaves) {      // unsigned: rows <= 2^31 - 1, so r + nwaves cannot wrap
         const float *xp = x + (size_t)r * inner;
         float s = 0.f;
-        for (int i = lane; i < inner; i += 64) s += xp[i];
+        for (unsigned i = lane; i < (unsigned)inner; i += 64) s += xp[i];
         for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
         if (lane == 0) y[r] = s * inv;
     }
@@ -383,18 +381,18 @@ __global__ void __launch_bounds__(TPB) concat2_q4_kernel(const float4 *a, const 
 __global__ void __launch_bounds__(TPB) gap_q4_kernel(const float4 *x, float *y, int rows, int Cq, int C, int inner,
                                                      float inv) {
     const int lane = threadIdx.x & 63;
-    const int wave = (blockIdx.x * TPB + threadIdx.x) >> 6;
-    const int nwaves = (gridDim.x * TPB) >> 6;
-    for (int r = wave; r < rows; r += nwaves) {
+    const unsigned wave = (blockIdx.x * TPB + threadIdx.x) >> 6;
+    const unsigned nwaves = (gridDim.x * TPB) >> 6;
+    for (unsigned r = wave; r < (unsigned)rows; r += nwaves) {      // unsigned: rows <= 2^31 - 1, so r + nwaves cannot wrap
         const float4 *xp = x + (size_t)r * inner;
         float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-        for (int i = lane; i < inner; i += 64) s = f4add(s, xp[i]);
+        for (unsigned i = lane; i < (unsigned)inner; i += 64) s = f4add(s, xp[i]);
         for (int off = 32; off > 0; off >>= 1) {
             s.x += __shfl_down(s.x, off, 64); s.y += __shfl_down(s.y, off, 64);
             s.z += __shfl_down(s.z, off, 64); s.w += __shfl_down(s.w, off, 64);
         }
         if (lane == 0) {
-            const int n = r / Cq, cq = r - n * Cq;
+            const int n = (int)(r / (unsigned)Cq), cq = (int)(r - (unsigned)n * (unsigned)Cq);
             float *yp = y + (size_t)n * C + cq * 4;
             const int left = C - cq * 4;
             yp[0] = s.x * inv;
@@ -567,18 +565,18 @@ __global__ void __launch_bounds__(TPB) resize_planes_kernel(const float *x, floa
 // y = x - max; s = sum(exp(y)); out = exp(y - log s)  (or y - log s)
 __global__ void __launch_bounds__(TPB) softmax_kernel(const float *x, float *y, int rows, int cols, int logmode) {
     const int lane = threadIdx.x & 63;
-    const int wave = (blockIdx.x * TPB + threadIdx.x) >> 6, nwaves = (gridDim.x * TPB) >> 6;
-    for (int r = wave; r < rows; r += nwaves) {
+    const unsigned wave = (blockIdx.x * TPB + threadIdx.x) >> 6, nwaves = (gridDim.x * TPB) >> 6;
+    for (unsigned r = wave; r < (unsigned)rows; r += nwaves) {      // unsigned: rows <= 2^31 - 1, so r + nwaves cannot wrap
         const float *xp = x + (size_t)r * cols;
         float *yp = y + (size_t)r * cols;
         float m = -INFINITY;
-        for (int i = lane; i < cols; i += 64) m = fmaxf(m, xp[i]);
+        for (unsigned i = lane; i < (unsigned)cols; i += 64) m = fmaxf(m, xp[i]);
         for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
         float s = 0.f;
-        for (int i = lane; i < cols; i += 64) s += expf(__fsub_rn(xp[i], m));
+        for (unsigned i = lane; i < (unsigned)cols; i += 64) s += expf(__fsub_rn(xp[i], m));
         for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
         const float ls = logf(s);
-        for (int i = lane; i < cols; i += 64) {
+        for (unsigned i = lane; i < (unsigned)cols; i += 64) {
             const float t = __fsub_rn(__fsub_rn(xp[i], m), ls);
             yp[i] = logmode ? t : expf(t);
         }
@@ -588,11 +586,11 @@ __global__ void __launch_bounds__(TPB) softmax_kernel(const float *x, float *y, 
 // reduce over the trailing `cols` elements of each row: 0 sum, 1 mean, 2 max, 3 min
 __global__ void __launch_bounds__(TPB) reduce_rows_kernel(const float *x, float *y, int rows, int cols, int op) {
     const int lane = threadIdx.x & 63;
-    const int wave = (blockIdx.x * TPB + threadIdx.x) >> 6, nwaves = (gridDim.x * TPB) >> 6;
-    for (int r = wave; r < rows; r += nwaves) {
+    const unsigned wave = (blockIdx.x * TPB + threadIdx.x) >> 6, nwaves = (gridDim.x * TPB) >> 6;
+    for (unsigned r = wave; r < (unsigned)rows; r += nwaves) {      // unsigned: rows <= 2^31 - 1, so r + nwaves cannot wrap
         const float *xp = x + (size_t)r * cols;
         float v = op == 2 ? -INFINITY : op == 3 ? INFINITY : 0.f;
-        for (int i = lane; i < cols; i += 64) {
+        for (unsigned i = lane; i < (unsigned)cols; i += 64) {
             const float t = xp[i];
             v = op == 2 ? max_nan(v, t) : op == 3 ? min_nan(v, t) : v + t;
         }
@@ -720,14 +718,32 @@ __global__ void __launch_bounds__(TPB) tile_normalise_kernel(float *buf, const f
 
 }  // namespace
 
+unsigned pl_stream_grid(int cu_count, size_t work_items) {
+    size_t blocks = (work_items + PL_STREAM_TPB - 1) / PL_STREAM_TPB;
+    size_t cap = (size_t)(cu_count > 0 ? cu_count : 256) * 8;
+    if (blocks > cap) blocks = cap;
+    return blocks ? (unsigned)blocks : 1u;
+}
+
+bool pl_loop32_ok(int cu_count, size_t total) {
+    return total < (1ull << 32) && total + (size_t)pl_stream_grid(cu_count, total) * PL_STREAM_TPB <= (1ull << 32);
+}
+
 extern "C" {
+
+// pl_loop32_ok for (total, cu_count); cu_count <= 0 stands for the 256 CUs assumed before a context exists.  A host query (tests).
+int pl_stream_loop32_ok(size_t total, int cu_count, int *ok) {
+    PL_REQUIRE(ok, PL_EINVAL, "pl_stream_loop32_ok: null argument");
+    *ok = pl_loop32_ok(cu_count, total) ? 1 : 0;
+    return PL_OK;
+}
 
 int pl_resize_hwc_f32(pl_ctx *ctx, const float *x, float *y, int H, int W, int C, int OH, int OW, const int *ra,
                       const float *rs, const int *ca, const float *cs) {
     PL_REQUIRE(ctx && x && y && ra && rs && ca && cs, PL_EINVAL, "pl_resize_hwc_f32: null argument");
     PL_REQUIRE(H > 1 && W > 1 && C > 0 && OH > 0 && OW > 0, PL_EINVAL, "pl_resize_hwc_f32: bad shape (needs H, W >= 2)");
     const size_t total = (size_t)OH * OW * C;
-    PL_REQUIRE(total < (1ull << 32) && (size_t)H * W * C < (1ull << 32), PL_EUNSUPPORTED, "resize: image too large");
+    PL_REQUIRE(loop32_ok(ctx, total) && (size_t)H * W * C < (1ull << 32), PL_EUNSUPPORTED, "resize: image too large");
     CtxGuard g(ctx);
     resize_hwc_kernel<<<stream_grid(ctx, total), TPB, 0, ctx->stream>>>(x, y, (unsigned)total, W, C, OW, ra, rs, ca, cs,
                                                                      FastDiv(C), FastDiv(OW));
@@ -741,7 +757,7 @@ int pl_tile_accumulate_f32(pl_ctx *ctx, const float *rst, float *buf, float *cou
     PL_REQUIRE(h > 0 && w > 0 && C > 0 && r0 >= 0 && c0 >= 0 && r0 + h <= OH && c0 + w <= OW && margin >= 0, PL_EINVAL,
                "pl_tile_accumulate_f32: window outside the output");
     const size_t total = (size_t)h * w * C;
-    PL_REQUIRE(total < (1ull << 32), PL_EUNSUPPORTED, "tile: window too large");
+    PL_REQUIRE(loop32_ok(ctx, total), PL_EUNSUPPORTED, "tile: window too large");
     CtxGuard g(ctx);
     tile_accumulate_kernel<<<stream_grid(ctx, total), TPB, 0, ctx->stream>>>(rst, buf, count, (unsigned)total, h, w, C, r0,
                                                                           c0, OW, margin, FastDiv(C), FastDiv(w));
@@ -752,7 +768,7 @@ int pl_tile_accumulate_f32(pl_ctx *ctx, const float *rst, float *buf, float *cou
 int pl_tile_normalise_f32(pl_ctx *ctx, float *buf, const float *count, int OH, int OW, int C) {
     PL_REQUIRE(ctx && buf && count && OH > 0 && OW > 0 && C > 0, PL_EINVAL, "pl_tile_normalise_f32: bad argument");
     const size_t total = (size_t)OH * OW * C;
-    PL_REQUIRE(total < (1ull << 32), PL_EUNSUPPORTED, "tile: image too large");
+    PL_REQUIRE(loop32_ok(ctx, total), PL_EUNSUPPORTED, "tile: image too large");
     CtxGuard g(ctx);
     tile_normalise_kernel<<<stream_grid(ctx, total), TPB, 0, ctx->stream>>>(buf, count, (unsigned)total, FastDiv(C));
     PL_LAUNCH_CHECK();
@@ -840,7 +856,7 @@ int pl_upsample_linear_f32(pl_ctx *ctx, const float *x, float *y, int NC, int H,
     PL_REQUIRE(fh * fw <= 64, PL_EUNSUPPORTED, "pl_upsample_linear_f32: fh * fw <= 64 supported, got %d", fh * fw);
     const size_t total = (size_t)NC * H * fh * W * fw;
     if (!total) return PL_OK;
-    PL_REQUIRE(total < (1ull << 32), PL_EUNSUPPORTED, "upsample: tensor too large");
+    PL_REQUIRE(loop32_ok(ctx, total), PL_EUNSUPPORTED, "upsample: tensor too large");
     UpLinArgs p;
     p.H = H; p.W = W; p.fh = fh; p.fw = fw;
     p.terms = (fh > 1 && fw > 1) ? 4 : 2;
@@ -858,7 +874,7 @@ int pl_resize_linear_f32(pl_ctx *ctx, const float *x, float *y, int NC, int H, i
     PL_REQUIRE(NC >= 0 && H > 1 && W > 1 && OH > 0 && OW > 0, PL_EINVAL, "pl_resize_linear_f32: bad shape (needs H, W >= 2)");
     const size_t total = (size_t)NC * OH * OW;
     if (!total) return PL_OK;
-    PL_REQUIRE(total < (1ull << 32) && (size_t)NC * H * W < (1ull << 32), PL_EUNSUPPORTED, "resize: tensor too large");
+    PL_REQUIRE(loop32_ok(ctx, total) && (size_t)NC * H * W < (1ull << 32), PL_EUNSUPPORTED, "resize: tensor too large");
     CtxGuard g(ctx);
     resize_planes_kernel<<<stream_grid(ctx, total), TPB, 0, ctx->stream>>>(x, y, (unsigned)total, H, W, ra, rs, ca, cs,
                                                                        FastDiv(OW), FastDiv(OH));
@@ -896,7 +912,7 @@ int pl_transpose_f32(pl_ctx *ctx, const float *x, float *y, int ndim, const int 
         total *= (size_t)shape[d];
     }
     if (!total) return PL_OK;
-    PL_REQUIRE(total < (1ull << 32), PL_EUNSUPPORTED, "transpose: tensor too large");
+    PL_REQUIRE(loop32_ok(ctx, total), PL_EUNSUPPORTED, "transpose: tensor too large");
     PermArgs p;
     p.ndim = ndim;
     for (int d = 0; d < ndim; ++d) {
@@ -955,7 +971,7 @@ int pl_pool2d_f32(pl_ctx *ctx, const float *x, float *y, int NC, int H, int W, i
     PL_REQUIRE(Ho > 0 && Wo > 0, PL_EINVAL, "pl_pool2d_f32: empty output");
     size_t total = (size_t)NC * Ho * Wo;
     if (!total) return PL_OK;
-    PL_REQUIRE(total < (1ull << 32) && (size_t)NC * H * W < (1ull << 32), PL_EUNSUPPORTED, "pool: tensor too large");
+    PL_REQUIRE(loop32_ok(ctx, total) && (size_t)NC * H * W < (1ull << 32), PL_EUNSUPPORTED, "pool: tensor too large");
     CtxGuard g(ctx);
     if (mode == 0 && kh == 3 && kw == 3 && sh == 2 && sw == 2 && pt == 1 && pl == 1 && H == 2 * Ho && W == 2 * Wo &&
         Wo % 4 == 0 && aligned16(x) && aligned16(y)) {
@@ -979,7 +995,7 @@ int pl_upsample_nearest_f32(pl_ctx *ctx, const float *x, float *y, int NC, int H
     PL_REQUIRE(NC >= 0 && H > 0 && W > 0 && fh > 0 && fw > 0, PL_EINVAL, "pl_upsample_nearest_f32: bad shape");
     size_t total = (size_t)NC * H * fh * W * fw;
     if (!total) return PL_OK;
-    PL_REQUIRE(total < (1ull << 32), PL_EUNSUPPORTED, "upsample: tensor too large");
+    PL_REQUIRE(loop32_ok(ctx, total), PL_EUNSUPPORTED, "upsample: tensor too large");
     CtxGuard g(ctx);
     upsample_kernel<<<stream_grid(ctx, total), TPB, 0, ctx->stream>>>(x, y, (unsigned)total, H, W, H * fh, W * fw,
                                                                   FastDiv(W * fw), FastDiv(H * fh), FastDiv(fh), FastDiv(fw));
@@ -993,7 +1009,7 @@ int pl_copy2d_f32(pl_ctx *ctx, float *dst, size_t dst_pitch, const float *src, s
     PL_REQUIRE(dst_pitch >= width && src_pitch >= width, PL_EINVAL, "pl_copy2d_f32: pitch < width");
     size_t total = width * rows;
     if (!total) return PL_OK;
-    PL_REQUIRE(total < (1ull << 32), PL_EUNSUPPORTED, "copy2d: tensor too large");
+    PL_REQUIRE(loop32_ok(ctx, total), PL_EUNSUPPORTED, "copy2d: tensor too large");
     CtxGuard g(ctx);
     if (aligned16(dst) && aligned16(src) && width % 4 == 0 && dst_pitch % 4 == 0 && src_pitch % 4 == 0) {
         unsigned w4 = (unsigned)(width / 4), t4 = (unsigned)(total / 4);
@@ -1121,7 +1137,7 @@ int pl_splitk_reduce_f32(pl_ctx *ctx, const float *ws, int splits, float *y, int
     PL_REQUIRE(ctx && ws && y && splits >= 1, PL_EINVAL, "pl_splitk_reduce_f32: bad argument");
     size_t total = (size_t)N * C * inner;
     if (!total) return PL_OK;
-    PL_REQUIRE(total < (1ull << 32), PL_EUNSUPPORTED, "splitk reduce: tensor too large");
+    PL_REQUIRE(loop32_ok(ctx, total), PL_EUNSUPPORTED, "splitk reduce: tensor too large");
     CtxGuard g(ctx);
     Epilogue ep = make_epilogue(bias, scale, shift, res, act, alpha);
     splitk_reduce_kernel<<<stream_grid(ctx, total), TPB, 0, ctx->stream>>>(ws, splits, total, y, (unsigned)total, C,

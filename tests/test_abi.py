@@ -127,3 +127,65 @@ def test_stem_pool_shape_predicates_need_no_device():
     from planer_amd import _lib
     _lib.call("pl_conv2d_stem_nchw_filter_elems", 64, __import__("ctypes").byref(n))
     assert n.value == 48 * 64 * 4                                                                    # [48 k-quads][Cout][4]
+
+
+# ---- 32-bit grid-stride loops near 2^32 work items (pl_stream_loop32_ok) -----------------------------------------------
+def _loop32_ok(total, cus):
+    import ctypes
+    ok = ctypes.c_int(-1)
+    _lib.call("pl_stream_loop32_ok", int(total), int(cus), ctypes.byref(ok))
+    assert ok.value in (0, 1)
+    return bool(ok.value)
+
+
+def _stream_stride(total, cus):
+    """Threads of the streaming launch (csrc/pointwise.hip pl_stream_grid): blocks of 256, at most 8 per CU (256 CUs when unknown)."""
+    return max(1, min((total + 255) // 256, (cus if cus > 0 else 256) * 8)) * 256
+
+
+def _loop32_visits(total, stride, first, limit):
+    """`for (unsigned i = first; i < total; i += stride)` with i wrapping at 2^32 as the hardware does: the indices one thread
+    visits, cut off after `limit` of them (a loop that has not ended by then has wrapped)."""
+    seen, i = [], first
+    while i < total and len(seen) < limit:
+        seen.append(i)
+        i = (i + stride) & 0xFFFFFFFF
+    return seen
+
+
+@pytest.mark.skipif(not _built(), reason="libplaner_hip.so not built")
+@pytest.mark.parametrize("cus", [0, 256, 304])
+def test_loop32_guard_is_total_plus_stride_within_2_32(cus):
+    """Entry points whose kernels count work items in 32 bits accept `total` only if no thread's counter can wrap:
+    total + stride <= 2^32 (the old guard, total < 2^32, let the last `stride` totals through)."""
+    stride = _stream_stride(1 << 32, cus)
+    assert stride == (cus or 256) * 8 * 256
+    assert _loop32_ok((1 << 32) - stride, cus)
+    assert not _loop32_ok((1 << 32) - stride + 1, cus)
+    assert not _loop32_ok((1 << 32) - 1, cus)
+    assert not _loop32_ok(1 << 32, cus) and not _loop32_ok((1 << 32) + 5, cus) and not _loop32_ok(1 << 40, cus)
+    for total in (0, 1, 255, 256, 257, 1 << 20, (1 << 29) + 3, (1 << 31) - 1, 1 << 31, (1 << 31) + 1, 3 << 30):
+        assert _loop32_ok(total, cus), total
+        assert total + _stream_stride(total, cus) <= 1 << 32
+
+
+@pytest.mark.skipif(not _built(), reason="libplaner_hip.so not built")
+def test_loop32_guard_agrees_with_an_emulated_loop():
+    """A pure-Python run of the 32-bit loop for the thread that owns the last index, total - 1: under the guard it visits its
+    own indices once and stops; above it the counter wraps to an index below `total` and the thread goes round again -- for
+    ever on 256 CUs, where 2^32 is a multiple of the stride and the wrapped counter is the thread's first index."""
+    for cus in (256, 304):
+        stride = _stream_stride(1 << 32, cus)
+        for total in ((1 << 32) - stride, (1 << 32) - stride + 1, (1 << 32) - 1, (1 << 32) - 2 * stride + 7,
+                      (1 << 32) - stride // 2, (1 << 31) + 12345, 3 * stride + 1):
+            first = (total - 1) % stride
+            own = list(range(first, total, stride))
+            seen = _loop32_visits(total, stride, first, len(own) + 2)
+            assert seen[:len(own)] == own
+            ended = len(seen) == len(own)
+            assert ended is _loop32_ok(total, cus), (cus, total)
+            assert ended is (total + stride <= 1 << 32)
+            if not ended:
+                assert seen[len(own)] < stride                         # wrapped: back among the first indices of the tensor
+                if cus == 256:
+                    assert seen[len(own)] == first                     # ... at its own first index: the same cycle again
