@@ -69,6 +69,16 @@ int pl_free(pl_ctx *ctx, void *ptr);
 int pl_pool_stats(pl_ctx *ctx, size_t *bytes_reserved, size_t *bytes_in_use);
 int pl_pool_block(pl_ctx *ctx, const void *ptr, void **base, size_t *bytes); /* the pool block that holds ptr */
 int pl_pool_trim(pl_ctx *ctx);                       /* hipFree cached blocks */
+/* Hygiene mode of the pool, for tests (off by default).  While guard_bytes != 0 every pl_alloc outside capture, the library's
+ * own workspaces included, gets a hipMalloc of its own laid out [front guard][payload of exactly the requested bytes][back
+ * guard]; the guards hold a canary byte, the payload poison_byte (-1: not filled, else 0..255).  Such a block is never
+ * recycled: pl_free keeps it until the next check.  pl_pool_debug_check waits for the stream, compares the guards of every
+ * live hygiene block and of every one freed since the last check, releases the freed ones, and sets *violations to the
+ * number of dirty blocks; `report` (may be NULL) names the first few: serial, requested bytes, live or freed, side, offsets
+ * of the first and last dirty byte from the payload edge, dirty byte count.  guard_bytes 0 switches the mode off; blocks
+ * made under it stay valid. */
+int pl_pool_debug(pl_ctx *ctx, size_t guard_bytes, int poison_byte);
+int pl_pool_debug_check(pl_ctx *ctx, int *violations, char *report, size_t report_len);
 /* np.asarray / .get() of net.py:96-100 */
 int pl_h2d(pl_ctx *ctx, void *dst, const void *src_host, size_t bytes);
 int pl_d2h(pl_ctx *ctx, void *dst_host, const void *src, size_t bytes); /* syncs */

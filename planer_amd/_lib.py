@@ -37,6 +37,8 @@ SIGNATURES = {
     "pl_pool_stats": [_P, POINTER(c_size_t), POINTER(c_size_t)],
     "pl_pool_block": [_P, _P, POINTER(_P), POINTER(c_size_t)],
     "pl_pool_trim": [_P],
+    "pl_pool_debug": [_P, _Z, _I],
+    "pl_pool_debug_check": [_P, POINTER(c_int), c_char_p, _Z],
     "pl_h2d": [_P, _P, _P, _Z],
     "pl_d2h": [_P, _P, _P, _Z],
     "pl_d2d": [_P, _P, _P, _Z],

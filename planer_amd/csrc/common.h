@@ -63,6 +63,22 @@ struct pl_ctx {
     std::unordered_set<void *> live;         // blocks currently handed out
     size_t reserved = 0, in_use = 0;
 
+    // hygiene mode (pl_pool_debug): while dbg_guard != 0 every pl_alloc outside capture gets a hipMalloc of its
+    // own, [front guard][payload][back guard], that no free list ever sees.  `hyg` is keyed by the payload pointer, which is
+    // also the block's key in block_size / live; freed blocks wait in hyg_freed for pl_pool_debug_check.
+    struct HygBlock {
+        void *base = nullptr;
+        size_t front = 0, bytes = 0, back = 0;
+        unsigned long long serial = 0;
+        unsigned char canary = 0;
+        bool freed = false;
+    };
+    size_t dbg_guard = 0;
+    int dbg_poison = -1;
+    unsigned long long dbg_serial = 0;
+    std::unordered_map<void *, HygBlock> hyg;
+    std::vector<void *> hyg_freed;
+
     // capture state: blocks handed out while capturing belong to the graph
     bool capturing = false;
     std::unordered_set<void *> cap_blocks;

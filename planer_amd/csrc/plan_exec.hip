@@ -212,7 +212,9 @@ int pl_plan_build(pl_ctx *ctx, const void *program, size_t program_bytes, pl_pla
         rc = pl_h2d(ctx, pl->consts, cb, const_bytes);
         if (rc != PL_OK) return fail(rc);
     }
-    rc = pl_memset(ctx, pl->arena, 0, arena_bytes ? arena_bytes : 1);
+    // a zeroed arena; under the pool's hygiene mode the poison byte instead, so that a step which reads an arena byte that
+    // no step wrote shows in the outputs
+    rc = pl_memset(ctx, pl->arena, ctx->dbg_guard && ctx->dbg_poison >= 0 ? ctx->dbg_poison : 0, arena_bytes ? arena_bytes : 1);
     if (rc != PL_OK) return fail(rc);
     // one eager pass: launch plans are taken from the tuning database or found now; the pool learns the temporaries' sizes
     rc = run_calls(pl);

@@ -6,6 +6,7 @@
 #include <dlfcn.h>
 #include <rccl/rccl.h>
 
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 
@@ -79,7 +80,9 @@ int pl_ctx_destroy(pl_ctx *ctx) {
     (void)hipStreamSynchronize(ctx->stream);
     pl_stager_destroy(ctx);
     pl_comm_destroy(ctx);
-    for (auto &kv : ctx->block_size) (void)hipFree(kv.first);
+    for (auto &kv : ctx->block_size)
+        if (!ctx->hyg.count(kv.first)) (void)hipFree(kv.first);
+    for (auto &kv : ctx->hyg) (void)hipFree(kv.second.base);
     if (ctx->sync_event) (void)hipEventDestroy((hipEvent_t)ctx->sync_event);
     (void)hipStreamDestroy(ctx->stream);
     delete ctx;
@@ -132,10 +135,134 @@ static void *take_fit(std::multimap<size_t, void *> &fl, size_t sz) {
     return p;
 }
 
+// ---- hygiene mode -----------------------------------------
+// The pool above hides two kinds of mistake: a store past a tensor's end lands in rounding slack, and a recycled block still
+// holds a plausible answer.  In this mode a block is [front guard][payload of exactly the requested bytes][back guard] in a
+// hipMalloc of its own: guards hold a canary byte, the payload a poison byte, and pl_pool_debug_check compares the guards.
+static int hyg_alloc(pl_ctx *ctx, size_t bytes, void **out) {
+    const size_t front = (ctx->dbg_guard + 255) / 256 * 256;      // the payload keeps hipMalloc's 256-byte alignment
+    const size_t back = ctx->dbg_guard;
+    const unsigned char canary = ctx->dbg_poison == 0xA5 ? 0x5A : 0xA5;
+    void *base = nullptr;
+    hipError_t e = hipMalloc(&base, front + bytes + back);
+    if (e != hipSuccess) {
+        pl_set_error("hipMalloc(%zu): %s", front + bytes + back, hipGetErrorString(e));
+        return e == hipErrorOutOfMemory ? PL_ENOMEM : PL_EHIP;
+    }
+    char *p = (char *)base + front;
+    e = hipMemsetAsync(base, canary, front, ctx->stream);
+    if (e == hipSuccess && bytes && ctx->dbg_poison >= 0) e = hipMemsetAsync(p, ctx->dbg_poison, bytes, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(p + bytes, canary, back, ctx->stream);
+    // the fills are done before the pointer is out: a copy stream or a side context may write the block next, and neither
+    // is ordered behind this stream
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) {
+        (void)hipFree(base);
+        pl_set_error("pl_alloc (hygiene fill): %s", hipGetErrorString(e));
+        return PL_EHIP;
+    }
+    pl_ctx::HygBlock b;
+    b.base = base, b.front = front, b.bytes = bytes, b.back = back, b.canary = canary, b.serial = ++ctx->dbg_serial;
+    ctx->hyg[p] = b;
+    ctx->block_size[p] = bytes;
+    ctx->reserved += front + bytes + back;
+    ctx->in_use += bytes;
+    ctx->live.insert(p);
+    *out = p;
+    return PL_OK;
+}
+
+static void hyg_release(pl_ctx *ctx, void *p) {
+    auto it = ctx->hyg.find(p);
+    ctx->reserved -= it->second.front + it->second.bytes + it->second.back;
+    (void)hipFree(it->second.base);
+    ctx->block_size.erase(p);
+    ctx->hyg.erase(it);
+}
+
+int pl_pool_debug(pl_ctx *ctx, size_t guard_bytes, int poison_byte) {
+    PL_REQUIRE(ctx, PL_EINVAL, "null ctx");
+    PL_REQUIRE(poison_byte >= -1 && poison_byte <= 255, PL_EINVAL, "pl_pool_debug: poison byte %d (-1: none, else 0..255)", poison_byte);
+    PL_REQUIRE(guard_bytes <= ((size_t)1 << 30), PL_EINVAL, "pl_pool_debug: guard of %zu bytes", guard_bytes);
+    PL_REQUIRE(!ctx->capturing, PL_EINVAL, "pl_pool_debug during capture");
+    if (guard_bytes) {
+        int rc = pl_pool_trim(ctx);     // no block from before the switch is handed out under the mode
+        if (rc != PL_OK) return rc;
+    }
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    ctx->dbg_guard = guard_bytes;
+    ctx->dbg_poison = guard_bytes ? poison_byte : -1;
+    return PL_OK;
+}
+
+// First and last byte of g[0..n) that is not `canary`, and how many are not; false if all are.
+static bool hyg_scan(const unsigned char *g, size_t n, unsigned char canary, size_t *first, size_t *last, size_t *count) {
+    size_t c = 0;
+    for (size_t i = 0; i < n; ++i)
+        if (g[i] != canary) {
+            if (!c) *first = i;
+            *last = i;
+            ++c;
+        }
+    *count = c;
+    return c != 0;
+}
+
+int pl_pool_debug_check(pl_ctx *ctx, int *violations, char *report, size_t report_len) {
+    PL_REQUIRE(ctx && violations, PL_EINVAL, "pl_pool_debug_check: null argument");
+    CtxGuard g(ctx);
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    PL_REQUIRE(!ctx->capturing, PL_EINVAL, "pl_pool_debug_check during capture");
+    PL_HIP(hipStreamSynchronize(ctx->stream));
+    std::vector<void *> order;
+    for (auto &kv : ctx->hyg) order.push_back(kv.first);
+    std::sort(order.begin(), order.end(), [&](void *a, void *b) { return ctx->hyg[a].serial < ctx->hyg[b].serial; });
+    std::string rep;
+    std::vector<unsigned char> host;
+    int dirty = 0;
+    for (void *p : order) {
+        const pl_ctx::HygBlock &b = ctx->hyg[p];
+        bool block_dirty = false;
+        for (int side = 0; side < 2; ++side) {
+            const size_t n = side ? b.back : b.front;
+            char *dev = side ? (char *)p + b.bytes : (char *)b.base;
+            if (!n) continue;
+            host.resize(n);
+            PL_HIP(hipMemcpy(host.data(), dev, n, hipMemcpyDeviceToHost));
+            size_t first = 0, last = 0, count = 0;
+            if (!hyg_scan(host.data(), n, b.canary, &first, &last, &count)) continue;
+            block_dirty = true;
+            if (dirty < 8) {
+                // offsets count from the payload edge: +k is k bytes past the payload's last byte + 1, -k is k bytes before its first
+                char line[256];
+                if (side)
+                    snprintf(line, sizeof line, "block #%llu (%zu bytes, %s): back guard dirty, %zu bytes, first at end+%zu, last at end+%zu\n",
+                             b.serial, b.bytes, b.freed ? "freed" : "live", count, first, last);
+                else
+                    snprintf(line, sizeof line, "block #%llu (%zu bytes, %s): front guard dirty, %zu bytes, first at start-%zu, last at start-%zu\n",
+                             b.serial, b.bytes, b.freed ? "freed" : "live", count, n - first, n - last);
+                rep += line;
+            }
+            if (!b.freed) PL_HIP(hipMemset(dev, b.canary, n));   // a live block is reported once
+        }
+        dirty += block_dirty;
+    }
+    if (dirty > 8) rep += "... and " + std::to_string(dirty - 8) + " more dirty blocks\n";
+    for (void *p : ctx->hyg_freed) hyg_release(ctx, p);
+    ctx->hyg_freed.clear();
+    *violations = dirty;
+    if (report && report_len) {
+        strncpy(report, rep.c_str(), report_len - 1);
+        report[report_len - 1] = 0;
+    }
+    return PL_OK;
+}
+
 int pl_alloc(pl_ctx *ctx, size_t bytes, void **out) {
     PL_REQUIRE(ctx && out, PL_EINVAL, "pl_alloc: null argument");
     CtxGuard g(ctx);
     std::lock_guard<std::mutex> lk(ctx->mu);
+    if (ctx->dbg_guard && !ctx->capturing) return hyg_alloc(ctx, bytes, out);
     const size_t sz = round_block(bytes);
     void *p = nullptr;
     // (experiment cap_noreuse=1: a block freed during this capture is not handed out again inside it, so no kernel of
@@ -166,6 +293,14 @@ int pl_free(pl_ctx *ctx, void *ptr) {
     PL_REQUIRE(it != ctx->block_size.end(), PL_EINVAL, "pl_free: unknown pointer %p", ptr);
     if (!ctx->live.erase(ptr)) return PL_OK;        // already released
     ctx->in_use -= it->second;
+    if (!ctx->hyg.empty()) {
+        auto h = ctx->hyg.find(ptr);
+        if (h != ctx->hyg.end()) {                  // its guards are evidence until the next pl_pool_debug_check: no reuse, no sync
+            h->second.freed = true;
+            ctx->hyg_freed.push_back(ptr);
+            return PL_OK;
+        }
+    }
     if (ctx->graph_owned.count(ptr)) return PL_OK;  // memory stays with its graph
     if (ctx->capturing && ctx->cap_blocks.count(ptr))
         ctx->cap_free.emplace(it->second, ptr);

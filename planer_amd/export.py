@@ -21,7 +21,7 @@ from .hip import DeviceArray
 _ALIGN = 256
 _DTYPES = {"float32": 0, "int32": 1, "int64": 2, "uint8": 3, "bool": 3}
 _QUERIES = ("_elems", "_supported")
-_IGNORED = {"pl_conv2d_last_plan", "pl_conv2d_last_extents", "pl_tune_stats", "pl_pool_stats", "pl_pool_block", "pl_event_create",
+_IGNORED = {"pl_conv2d_last_plan", "pl_conv2d_last_extents", "pl_tune_stats", "pl_pool_stats", "pl_pool_block", "pl_pool_debug", "pl_pool_debug_check", "pl_event_create",
             "pl_event_record", "pl_event_elapsed_ms", "pl_event_sync"}
 
 

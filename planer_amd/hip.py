@@ -16,6 +16,8 @@ from ._lib import byref, c_int, c_size_t, c_void_p
 
 float32 = numpy.float32
 
+POOL_GUARD_BYTES = 64 << 10      # default guard of Context.pool_debug: one 64 x 256 float output tile
+
 _default_ctx = None
 _free_hook = None         # planer_amd.export: told about every block a DeviceArray gives back while a plan is being recorded
 
@@ -83,6 +85,20 @@ class Context:
 
     def trim(self):
         _lib.call("pl_pool_trim", self.handle)
+
+    def pool_debug(self, guard_bytes=POOL_GUARD_BYTES, poison=0xFF):
+        """Hygiene mode of the pool: every block allocated from now on is a hipMalloc of its own with
+        `guard_bytes` of canary on either side and a payload filled with the byte `poison` (None: not filled), and is never
+        recycled.  guard_bytes=0 turns the mode off."""
+        _lib.call("pl_pool_debug", self.handle, int(guard_bytes), -1 if poison is None else int(poison))
+
+    def pool_debug_check(self):
+        """(number of hygiene blocks, live or freed since the last check, whose guards were written; a report of the first few).
+        Waits for the stream and releases the freed blocks."""
+        n = c_int()
+        buf = ctypes.create_string_buffer(4096)
+        _lib.call("pl_pool_debug_check", self.handle, byref(n), buf, 4096)
+        return n.value, buf.value.decode()
 
     def set_conv_config(self, cfg=-1, split_k=0):
         _lib.call("pl_conv2d_set_config", self.handle, int(cfg), int(split_k))

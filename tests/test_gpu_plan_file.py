@@ -34,6 +34,8 @@ def _bind():
     lib.pl_sync.argtypes = [P]
     lib.pl_alloc.argtypes = [P, Z, ctypes.POINTER(P)]
     lib.pl_free.argtypes = [P, P]
+    lib.pl_pool_debug.argtypes = [P, Z, I]
+    lib.pl_pool_debug_check.argtypes = [P, ctypes.POINTER(I), ctypes.c_char_p, Z]
     return lib
 
 
@@ -41,10 +43,13 @@ def _ok(lib, rc):
     assert rc == 0, lib.pl_last_error().decode()
 
 
-def _run_plan(lib, blob, inputs, through_pointers=False):
-    """ctypes only: -> list of output arrays"""
+def _run_plan(lib, blob, inputs, through_pointers=False, hygiene=None):
+    """ctypes only: -> list of output arrays.  hygiene = (guard bytes, poison byte): the context's pool in hygiene mode from the
+    start (pl_plan_build then poisons the arena instead of clearing it), and every guard clean at the end."""
     ctx = ctypes.c_void_p()
     _ok(lib, lib.pl_ctx_create(0, ctypes.byref(ctx)))
+    if hygiene is not None:
+        _ok(lib, lib.pl_pool_debug(ctx, hygiene[0], hygiene[1]))
     plan = ctypes.c_void_p()
     buf = ctypes.create_string_buffer(blob, len(blob))
     _ok(lib, lib.pl_plan_build(ctx, buf, len(blob), ctypes.byref(plan)))
@@ -89,6 +94,10 @@ def _run_plan(lib, blob, inputs, through_pointers=False):
         for a, c in zip(outs[0], other):
             np.testing.assert_array_equal(a, c)
     _ok(lib, lib.pl_plan_destroy(plan))
+    if hygiene is not None:
+        dirty, report = ctypes.c_int(), ctypes.create_string_buffer(4096)
+        _ok(lib, lib.pl_pool_debug_check(ctx, ctypes.byref(dirty), report, 4096))
+        assert dirty.value == 0, report.value.decode()
     _ok(lib, lib.pl_ctx_destroy(ctx))
     return outs[0]
 
