@@ -12,7 +12,12 @@ every fresh block filled with 0xFF (every float a NaN, every integer -1) and onc
   (c) no guard byte changed (`hygiene` asserts it, with the library's report of block, side, offsets and byte count).
 The last test of the module asserts what the sweep reached: the w_layouts, a split-K plan, both dense paths, the chain and
 conv1x1 + Winograd-in kernels -- coverage is a condition.  Run with -s for seconds per group, mode off and on, and the peak
-pool size."""
+pool size.
+
+Group "index ops" (test_index_ops_at_their_boundaries): a kept subset of tests/test_gpu_index_ops.py, one case per family across
+its boundary -- TopK at n = 8193 and n = 16385, NonZero at 2C + 5 with density 0.5, the 70 000-update ScatterND, Gather past the
+grid, Where at 1 048 579 and Cast at 1 200 003 elements, one comparison and Erf: 0.3 s mode off, 0.8 s for the two poisoned
+runs."""
 import contextlib
 import ctypes
 import gc
@@ -372,6 +377,34 @@ def test_tile_blend_transpose_and_copies(pa, golden_layers):
             L.test_copy_and_compare_ops_are_bit_exact(pa, name, golden_layers)
 
     sweep("special", body, "tile / transpose / copies")
+
+
+# ---- index and selection operators: outputs and scratch whose size depends on the data ------------------------------------
+def test_index_ops_at_their_boundaries(pa):
+    """A kept subset of tests/test_gpu_index_ops.py, one case per family, each across its boundary: TopK at n = 8193
+    (128 KiB of LDS; every data class, ties among them) and at n = 16385 (selection rounds, k = 1, 7, 300), NonZero at 2C + 5 with
+    density 0.5 (the scan's carry; scratch of 2050 counts, an output sized by the count), the 70 000-update ScatterND, Gather past
+    the grid, Where at 1 048 579 and Cast at 1 200 003 elements, one comparison and Erf."""
+    from tests import ref_index as R
+    from tests import test_gpu_index_ops as I
+    size = 2 * R.NZ_CHUNK + 5
+    nz = R.nonzero_input(R.nonzero_mask("half", size), np.float32)
+
+    def body():
+        I.test_topk_every_data_class(pa, 8193)
+        I.test_topk_every_data_class(pa, 16385)
+        I._nonzero_check(pa, nz, "half float32 %d" % size)
+        I.test_scatternd_rows_last_write_wins(pa, 5, 70000)
+        I.test_gather_past_the_grid(pa)
+        I.test_where_passes_every_bit_pattern(pa, "random")
+        I.test_cast_every_pair(pa, "float32", "int64")
+        I.test_cast_every_pair(pa, "int64", "float32")
+        I.test_compare_sizes_and_single_value_operands(pa, "greater", np.greater)
+        I.test_erf_table_boundaries_and_clobbered_input(pa)
+
+    sweep("index ops", body)
+    assert {"pl_topk_f32", "pl_nonzero_count", "pl_nonzero_write", "pl_scatter_rows_f32", "pl_gather_f32", "pl_where_f32", "pl_cast",
+            "pl_compare_f32", "pl_erf_lut_f32"} <= REACHED["entries"], sorted(REACHED["entries"])
 
 
 # ---- whole programs, eagerly: the float64 step audit of tests/test_gpu_plan_audit.py with guards and poison ----------------
