@@ -413,6 +413,17 @@ int pl_concat2_q4_f32(pl_ctx *ctx, const float *aq, const float *bq, float *yq, 
 int pl_gap_q4_f32(pl_ctx *ctx, const float *xq, float *y, int N, int C, int HW);
 int pl_scale_shift_q4_f32(pl_ctx *ctx, const float *xq, float *yq, const float *scale,
                           const float *shift, int N, int C, int HW);
+/* layer.InstanceNormalization (layer.py:217-226) on a Q4 tensor IN PLACE with its tail fused into the write pass:
+ * x = IN(x) [+ resq] [relu] (act 0 / 1), statistics per (image, channel), variance in the reference's centred form.
+ * Planes of up to PL_INSTNORM_Q4_ONE_WG_PIXELS pixels are held by one workgroup per (image, quad): one read, one write.
+ * Larger planes: chunks of PL_INSTNORM_Q4_CHUNK_PIXELS pixels give (mean, M2) partials in a pool block, merged in chunk order
+ * (Chan's update) by the kernel that applies the tail.  The form depends on HW alone and there are no atomics: an image's bits
+ * do not depend on the batch, nor on the run.  Padding lanes of a partial last quad are written as +0.0.  HW == 0 or
+ * N == 0: nothing to do.  More than 2^29 quads: PL_EUNSUPPORTED. */
+#define PL_INSTNORM_Q4_ONE_WG_PIXELS 4096
+#define PL_INSTNORM_Q4_CHUNK_PIXELS 2048
+int pl_instancenorm_q4_f32(pl_ctx *ctx, float *xq, const float *scale, const float *bias, const float *resq,
+                           int N, int C, int HW, double eps, int act);
 
 /* First call for a new conv shape times every applicable tile configuration
  * and remembers the fastest (on by default; PLANER_HIP_AUTOTUNE=0 or 0 here

@@ -14,6 +14,8 @@ LIB_PATH = os.path.join(HERE, "libplaner_hip.so")
 
 PL_OK, PL_EINVAL, PL_EUNSUPPORTED, PL_ENOMEM, PL_EHIP, PL_ERCCL = range(6)
 NONZERO_BLOCK = 2048          # include/planer_hip.h PL_NONZERO_BLOCK
+INSTNORM_Q4_ONE_WG_PIXELS = 4096    # include/planer_hip.h PL_INSTNORM_Q4_ONE_WG_PIXELS
+INSTNORM_Q4_CHUNK_PIXELS = 2048     # include/planer_hip.h PL_INSTNORM_Q4_CHUNK_PIXELS
 ACT_NONE, ACT_RELU, ACT_LEAKY = 0, 1, 2
 ACT_RES_AFTER = 16
 UNIQUE_ID_BYTES = 128
@@ -167,6 +169,7 @@ SIGNATURES = {
     "pl_gather_f32": [_P, _P, _P, _P, _I, _I, _I, _I],
     "pl_erf_lut_f32": [_P, _P, _P, _P, _Z],
     "pl_instancenorm_f32": [_P, _P, _P, _P, _I, _I, _I, c_double],
+    "pl_instancenorm_q4_f32": [_P, _P, _P, _P, _P, _I, _I, _I, c_double, _I],
     "pl_scatter_rows_f32": [_P, _P, _P, _P, _P, _I, _I],
     "pl_nonzero_count": [_P, _P, _Z, _I, _P, _P],
     "pl_nonzero_write": [_P, _P, _Z, _I, _P, _P, _I, _P, c_longlong],

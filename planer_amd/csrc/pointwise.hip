@@ -5,6 +5,7 @@
 // grid-stride loop, wave64 shuffles for the one reduction.
 #include "common.h"
 #include "device_utils.h"
+#include "instnorm_q4_kernel.h"
 
 namespace {
 
@@ -1128,6 +1129,64 @@ int pl_scale_shift_q4_f32(pl_ctx *ctx, const float *xq, float *yq, const float *
     affine_q4_kernel<<<stream_grid(ctx, total), TPB, 0, ctx->stream>>>((const float4 *)xq, (float4 *)yq, scale, shift,
                                                                    (unsigned)total, C, Cq, FastDiv(HW), FastDiv(Cq));
     PL_LAUNCH_CHECK();
+    return PL_OK;
+}
+
+// layer.InstanceNormalization on a Q4 tensor, in place, y = IN(x) [+ res] [relu] (instnorm_q4_kernel.h).  The form
+// depends on HW alone: one workgroup per (image, quad) up to PL_INSTNORM_Q4_ONE_WG_PIXELS pixels, chunk statistics into a pool
+// block + merge-and-apply above.
+int pl_instancenorm_q4_f32(pl_ctx *ctx, float *xq, const float *scale, const float *bias, const float *resq, int N, int C, int HW,
+                           double eps, int act) {
+    namespace iq = instnorm_q4;
+    PL_REQUIRE(ctx && xq && scale && bias, PL_EINVAL, "pl_instancenorm_q4_f32: null argument");
+    PL_REQUIRE(N >= 0 && C > 0 && HW >= 0, PL_EINVAL, "pl_instancenorm_q4_f32: bad shape");
+    PL_REQUIRE(act == PL_ACT_NONE || act == PL_ACT_RELU, PL_EINVAL, "pl_instancenorm_q4_f32: act must be 0 (none) or 1 (relu)");
+    PL_REQUIRE(aligned16(xq) && aligned16(resq), PL_EINVAL, "pl_instancenorm_q4_f32: Q4 tensors must be 16-byte aligned");
+    const int Cq = (C + 3) / 4;
+    const size_t rows = (size_t)N * Cq, total = rows * (size_t)HW;
+    if (!total) return PL_OK;
+    PL_REQUIRE(total <= (1ull << 29), PL_EUNSUPPORTED, "instancenorm: tensor too large");
+    CtxGuard g(ctx);
+    float4 *x = (float4 *)xq;
+    const float4 *res = (const float4 *)resq;
+    const float e = (float)eps;
+    const int tail_id = (resq ? 2 : 0) | (act == PL_ACT_RELU ? 1 : 0);
+    if (HW <= PL_INSTNORM_Q4_ONE_WG_PIXELS) {
+        const dim3 grid((unsigned)rows), block(iq::TPB);
+        switch (tail_id) {
+        case 0: iq::instnorm_q4_one_wg_kernel<false, false><<<grid, block, 0, ctx->stream>>>(x, scale, bias, res, Cq, C, HW, e); break;
+        case 1: iq::instnorm_q4_one_wg_kernel<false, true><<<grid, block, 0, ctx->stream>>>(x, scale, bias, res, Cq, C, HW, e); break;
+        case 2: iq::instnorm_q4_one_wg_kernel<true, false><<<grid, block, 0, ctx->stream>>>(x, scale, bias, res, Cq, C, HW, e); break;
+        default: iq::instnorm_q4_one_wg_kernel<true, true><<<grid, block, 0, ctx->stream>>>(x, scale, bias, res, Cq, C, HW, e); break;
+        }
+        PL_LAUNCH_CHECK();
+        ctx->last_plan = "instnorm-q4 one-wg";
+        return PL_OK;
+    }
+    // rows * S <= total / CHUNK + rows < 2^19: one-dimensional grids
+    const int S = (HW + PL_INSTNORM_Q4_CHUNK_PIXELS - 1) / PL_INSTNORM_Q4_CHUNK_PIXELS;
+    const int A = S < iq::APPLY_MAX_WG_PER_ROW ? S : iq::APPLY_MAX_WG_PER_ROW;
+    float4 *part = nullptr;
+    int rc = pl_alloc(ctx, rows * S * 2 * sizeof(float4), (void **)&part);
+    if (rc != PL_OK) return rc;
+    iq::instnorm_q4_stats_kernel<<<dim3((unsigned)(rows * S)), dim3(iq::TPB), 0, ctx->stream>>>(x, part, S, HW);
+    hipError_t le = hipGetLastError();
+    if (le == hipSuccess) {
+        const dim3 grid((unsigned)(rows * A)), block(iq::TPB);
+        switch (tail_id) {
+        case 0: iq::instnorm_q4_apply_kernel<false, false><<<grid, block, 0, ctx->stream>>>(x, part, scale, bias, res, Cq, C, HW, S, A, e); break;
+        case 1: iq::instnorm_q4_apply_kernel<false, true><<<grid, block, 0, ctx->stream>>>(x, part, scale, bias, res, Cq, C, HW, S, A, e); break;
+        case 2: iq::instnorm_q4_apply_kernel<true, false><<<grid, block, 0, ctx->stream>>>(x, part, scale, bias, res, Cq, C, HW, S, A, e); break;
+        default: iq::instnorm_q4_apply_kernel<true, true><<<grid, block, 0, ctx->stream>>>(x, part, scale, bias, res, Cq, C, HW, S, A, e); break;
+        }
+        le = hipGetLastError();
+    }
+    pl_free(ctx, part);  // stream-ordered: safe to recycle after the enqueue
+    if (le != hipSuccess) {
+        pl_set_error("pl_instancenorm_q4_f32: kernel launch -> %s", hipGetErrorString(le));
+        return PL_EHIP;
+    }
+    ctx->last_plan = "instnorm-q4 chunks=" + std::to_string(S);
     return PL_OK;
 }
 

@@ -30,7 +30,7 @@ from . import q4 as _q4
 from .conv_layouts import (CONV_KINDS, CONVT_KINDS, DIRECT_Q4, IGEMM_NCHW, LAYOUTS, ROWPACK_Q4, STEM_POOL, STEM_POOL_NCHW, WINO4_Q4,
                            WINO43_Q4, choose, suffix)
 from .layer import layer_map, wrap
-from .plan import assign_layouts, chain_winograd, fuse_conv1x1_wino_in, fuse_flow, pair_sibling_convs
+from .plan import assign_layouts, chain_winograd, fuse_conv1x1_wino_in, fuse_flow, fuse_instnorm_q4, pair_sibling_convs
 
 _q4.register(layer_map)
 
@@ -337,6 +337,7 @@ class Net:
         self.wino_chains = 0         # F(4x4,3x3) output / input transform pairs the last plan runs as one kernel
         self.conv_pairs = 0          # sibling conv pairs the last plan runs as one launch
         self.conv_wino_fused = 0     # 1x1 convs the last plan runs inside the next conv's Winograd input transform
+        self.instnorm_fused = 0      # add / relu steps the last plan runs inside a channel-quad instance norm
         # force_algo: w_layout (int) every eligible 3x3/s1/p1 conv must use, or None = pick by timing
         fa = os.environ.get("PLANER_HIP_CONV_ALGO")
         self.force_algo = int(fa) if fa else None
@@ -452,6 +453,11 @@ class Net:
                     record.append({"layer": lname, "kind": obj.name, "w_layout": lay,
                                    "algo": W_LAYOUT_NAMES.get(lay, str(lay)), "plan": ctx_.last_conv_plan(),
                                    "extents": list(ctx_.last_conv_extents()), "x": list(xshape)})
+                if record is not None and obj.name == "instancenormalization_q4":
+                    # the form taken ("instnorm-q4 one-wg" / "instnorm-q4 chunks=S"), as the entry point left it
+                    record.append({"layer": name, "kind": obj.name, "w_layout": None, "algo": "instnorm-q4",
+                                   "plan": args[0].ctx.last_conv_plan() if args[0].size else "", "extents": [],
+                                   "x": list(_q4.logical_shape(args[0]))})
                 del args
                 if isinstance(dst, str):
                     env[dst] = val
@@ -499,7 +505,11 @@ class Net:
         else:
             body, flow, nfused = [list(b) for b in self.layer], [list(f) for f in self.flow], 0
         if self.use_q4:
-            body, flow, _ = assign_layouts(body, flow, self.inits, shapes, force=self.use_q4 == "force")
+            wmap = dict(zip(self.inits, self.weights))
+            body, flow, _ = assign_layouts(body, flow, self.inits, shapes, force=self.use_q4 == "force",
+                                           values=lambda key: wmap[key].host if key in wmap else None)
+            # instancenormalization_q4 -> [add_q4] -> [relu_q4] as one step: the tail goes into the norm's write pass
+            body, flow, self.instnorm_fused = fuse_instnorm_q4(body, flow, shapes)
         if os.environ.get("PLANER_HIP_TAPMAJOR", "1") != "0":
             body, flow = self._prepare_filters(body, flow, shapes)
         return _Program(body, flow), nfused

@@ -130,8 +130,19 @@ def fuse_flow(layers, flow, init_names, shapes):
 # downstream of a conv -- and everything else reads NCHW, with a conversion step inserted where a
 # value is needed in the layout it was not produced in (converted copies are cached per value).
 Q4_POINTWISE = ("maxpool", "averagepool", "gap", "upsample", "batchnorm", "relu", "leakyrelu", "sigmoid",
-                "add", "concat", "clip")
+                "add", "concat", "clip", "instancenormalization", "pad")
+# the kinds of instance-normalised generators (fast-neural-style, CycleGAN ...): PLANER_HIP_INSTNORM_Q4=0 takes them out again,
+# which gives the program of a compiler without them
+INSTNORM_Q4_KINDS = ("instancenormalization", "pad")
+PAD_MODES = ("constant", "wrap", "edge", "reflect", "symmetric")
 TO_Q4, FROM_Q4 = "@to_q4", "@from_q4"
+
+
+def q4_pointwise_kinds():
+    """Q4_POINTWISE as the environment leaves it."""
+    if os.environ.get("PLANER_HIP_INSTNORM_Q4", "1") == "0":
+        return tuple(k for k in Q4_POINTWISE if k not in INSTNORM_Q4_KINDS)
+    return Q4_POINTWISE
 
 
 def _is4d(shapes, key):
@@ -154,11 +165,31 @@ def q4_conv_ok(srcs, para, inits, shapes):
     return dw_q4_eligible(shapes[srcs[1]], group) or q4_conv_eligible(shapes[srcs[1]], group)
 
 
-def _q4_pointwise_ok(kind, srcs, para, inits, shapes):
+def pad_q4_ok(c, pads, constant_value=0, mode="constant", **_):
+    """PadQ4 pads pixels only -- (N, C, H, W) pads as ONNX orders them, all begins then all ends, N and C entries zero -- and in
+    constant mode keeps the zero padding lanes of a partial last quad only when the value is 0 (the rule of clip_q4_ok)."""
+    pads = [int(v) for v in pads]
+    if len(pads) != 8 or any(p < 0 for p in pads) or any(pads[i] for i in (0, 1, 4, 5)) or mode not in PAD_MODES:
+        return False
+    return mode != "constant" or c % 4 == 0 or float(constant_value) == 0.0
+
+
+def _q4_pointwise_ok(kind, srcs, para, inits, shapes, values=None):
     acts = [k for k in srcs if k != "None" and k not in inits]
     if not acts or not all(_is4d(shapes, k) for k in acts):
         return False
     c = shapes[acts[0]][1]
+    if kind == "instancenormalization":     # constant scale and bias
+        return len(srcs) == 3 and len(acts) == 1 and acts[0] == srcs[0] and srcs[1] in inits and srcs[2] in inits
+    if kind == "pad":                       # constant pads (and value): their numbers decide, so the caller must supply them
+        if values is None or len(srcs) not in (2, 3) or acts != [srcs[0]] or srcs[1] not in inits:
+            return False
+        pv = values(srcs[1])
+        cv = para.get("constant_value", 0)
+        if len(srcs) == 3 and srcs[2] != "None":
+            cv = values(srcs[2])
+            cv = None if cv is None or len(cv.reshape(-1)) != 1 else float(cv.reshape(-1)[0])
+        return pv is not None and cv is not None and pad_q4_ok(c, list(pv.reshape(-1)), cv, para.get("mode", "constant"))
     if kind == "add":
         return len(srcs) == 2 and len(acts) == 2 and tuple(shapes[srcs[0]]) == tuple(shapes[srcs[1]])
     if kind == "concat":
@@ -187,8 +218,9 @@ def _nbytes(shape):
     return n
 
 
-def assign_layouts(body, flow, init_names, shapes, force=False):
-    """-> (body', flow', number of Q4 steps).  Rewrites conv / conv_fused steps to `conv_q4`, the transposed convs
+def assign_layouts(body, flow, init_names, shapes, force=False, values=None):
+    """-> (body', flow', number of Q4 steps).  `values(key)` gives the host array of a constant (or None): `pad` goes Q4 only
+    where its pads are known numbers.  Rewrites conv / conv_fused steps to `conv_q4`, the transposed convs
     the phase-decomposed kernel takes (convtranspose / convt_fused) to `convt_q4`, and the
     HBM-bound layers that follow them to their `*_q4` kinds, inserting `to_q4` / `from_q4` steps at
     the edges.  The program's observable values (its last step's outputs) stay NCHW.
@@ -232,6 +264,7 @@ def assign_layouts(body, flow, init_names, shapes, force=False):
             copies.pop((key, lay), None)
 
     last = len(steps) - 1
+    pointwise = q4_pointwise_kinds()
     for i, (srcs, name, dst) in enumerate(steps):
         kind, para = kinds[name]
         single = isinstance(dst, str)
@@ -267,7 +300,7 @@ def assign_layouts(body, flow, init_names, shapes, force=False):
             for k in (srcs[0], dst):
                 if shapes.get(k) is not None:
                     est["gain"] += _nbytes(shapes[k]) * _CONVERT_S_PER_BYTE
-        elif kind in Q4_POINTWISE and single and _q4_pointwise_ok(kind, srcs, para, inits, shapes) \
+        elif kind in pointwise and single and _q4_pointwise_ok(kind, srcs, para, inits, shapes, values) \
                 and any(k in q4 for k in srcs):
             as_q4 = True
             args = [need(k, True) for k in srcs]
@@ -275,8 +308,8 @@ def assign_layouts(body, flow, init_names, shapes, force=False):
         if not as_q4:
             args = [need(k, False) for k in srcs]
             new_kind = kind
-        if kind in ("relu", "clip"):             # in place (layer.py:46, 250-251): cached copies of the input go stale
-            drop_copies(srcs[0])
+        if kind in ("relu", "clip", "instancenormalization"):   # in place (layer.py:46, 217-226, 250-251): cached copies of
+            drop_copies(srcs[0])                                # the input go stale
         out_key = dst
         produces_q4 = as_q4 and kind != "gap"
         if produces_q4 and i == last:
@@ -286,6 +319,12 @@ def assign_layouts(body, flow, init_names, shapes, force=False):
         if kind == "clip" and not as_q4 and srcs[0] in q4 and i != last:
             # clipped in place on its NCHW copy (a partial quad that clip would dirty): later readers of the input must
             # see the clipped values, so the Q4 primary is made again from that copy
+            add_layer([TO_Q4, TO_Q4[1:], {}])
+            out_flow.append([[args[0]], [TO_Q4], srcs[0]])
+        if (kind == "instancenormalization" and not as_q4 and srcs[0] in q4
+                and any(srcs[0] in s_ for s_, _, _ in steps[i + 1:])):
+            # likewise for an instance norm that stays NCHW (a scale computed by the graph, or the switch off) where the tensor it
+            # rewrote has later readers
             add_layer([TO_Q4, TO_Q4[1:], {}])
             out_flow.append([[args[0]], [TO_Q4], srcs[0]])
         for k in _as_list(dst):
@@ -306,6 +345,77 @@ def assign_layouts(body, flow, init_names, shapes, force=False):
     return out_body, out_flow, nq4
 
 
+# ---- instance norm tails ------------------------------------------------------------------------------
+def fuse_instnorm_q4(body, flow, shapes):
+    """-> (body', flow', number of absorbed steps).  Runs on assign_layouts' program (one layer per step).  Folds
+    instancenormalization_q4 -> [add_q4 with an operand of the same shape] -> [relu_q4]  into ONE instancenormalization_q4 step
+    with `res` and `act` set (q4.InstanceNormQ4: the tail goes into the kernel's write pass).  The order is fixed -- residual,
+    then activation -- so a relu that comes first ends the chain and the add behind it stays a step of its own.  As in
+    fuse_flow a link is absorbed only when the tensor between has one reader and one writer, and the fused step sits where the
+    last link was.  The norm works in place, so it is only moved when nothing else ever reads the tensor it rewrites."""
+    kinds = {b[0]: b for b in body}
+    steps = [[list(src) if isinstance(src, (list, tuple)) else [src], names[0] if isinstance(names, (list, tuple)) else names, dst]
+             for src, names, dst in flow]
+    readers, writers = {}, {}
+    for i, (srcs, name, dst) in enumerate(steps):
+        for k in set(srcs):
+            readers.setdefault(k, []).append(i)
+        for k in _as_list(dst):
+            writers[k] = writers.get(k, 0) + 1
+
+    def shape(key):
+        s = shapes.get(key.split("@")[0])
+        return None if s is None else tuple(s)
+
+    consumed, fused_at, nfused = set(), {}, 0
+    for i, (srcs, name, dst) in enumerate(steps):
+        _, kind, para = kinds[name]
+        if kind != "instancenormalization_q4" or i in consumed or not isinstance(dst, str) or len(srcs) != 3:
+            continue
+        if readers.get(srcs[0]) != [i] or writers.get(srcs[0], 0) > 1:
+            continue
+        chain, cur, res, act = [i], dst, "None", ACT_NONE
+        while act == ACT_NONE:
+            r = readers.get(cur, [])
+            if len(r) != 1 or writers.get(cur, 0) != 1:
+                break
+            j = r[0]
+            jsrcs, jname, jdst = steps[j]
+            jkind = kinds[jname][1]
+            if j in consumed or j <= chain[-1] or not isinstance(jdst, str):
+                break
+            if (jkind == "add_q4" and res == "None" and len(jsrcs) == 2 and jsrcs.count(cur) == 1
+                    and shape(jsrcs[0]) is not None and shape(jsrcs[0]) == shape(jsrcs[1])):
+                res = jsrcs[1 - jsrcs.index(cur)]
+            elif jkind == "relu_q4" and jsrcs == [cur]:
+                # the residual is now read at j: nothing may rewrite it between the add and here
+                if res != "None" and any((res in steps[t][0] and kinds[steps[t][1]][1] in _IN_PLACE) or res in _as_list(steps[t][2])
+                                         for t in range(chain[-1] + 1, j)):
+                    break
+                act = ACT_RELU
+            else:
+                break
+            chain.append(j)
+            cur = jdst
+        if len(chain) > 1:
+            consumed.update(chain)
+            fused_at[chain[-1]] = (srcs, name, para, res, act, cur)
+            nfused += len(chain) - 1
+    out = []
+    for i, (srcs, name, dst) in enumerate(steps):
+        if i in fused_at:
+            isrcs, iname, para, res, act, cur = fused_at[i]
+            out.append((isrcs + [res], iname + "+", "instancenormalization_q4", dict(para, act=act), cur))
+        elif i not in consumed:
+            out.append((srcs, name, kinds[name][1], kinds[name][2], dst))
+    out_body, seen = [], set()
+    for srcs, name, kind, para, dst in out:
+        if name not in seen:
+            seen.add(name)
+            out_body.append([name, kind, para])
+    return out_body, [[srcs, [name], dst] for srcs, name, kind, para, dst in out], nfused
+
+
 # ---- Winograd chaining ------------------------------------------------------------------------------
 # A conv_q4 step that runs F(4x4,3x3) (w_layout 7) is three kernels: input transform (x -> V), the 36
 # grouped GEMMs (V, U -> M) and output transform + fused tail (M -> y).  When the y of one such conv
@@ -316,7 +426,7 @@ def assign_layouts(body, flow, init_names, shapes, force=False):
 _PURE_READERS = ("conv_q4", "convt_q4", "wino4_in", "wino4_gemm", "wino4_out", "wino4_chain", "wino43_in", "wino43_gemm", "wino43_out",
                  "wino43_chain", "conv1x1_wino_in", "conv_q4_pair", "add_q4", "maxpool_q4",
                  "averagepool_q4", "gap_q4", "upsample_q4", "concat_q4", "upconcat_q4", "batchnorm_q4",
-                 "leakyrelu_q4", "sigmoid_q4", "from_q4")
+                 "leakyrelu_q4", "sigmoid_q4", "from_q4", "pad_q4")
 
 
 def chain_winograd(body, flow, supported=lambda key: True, chain=True):
@@ -428,7 +538,7 @@ def fuse_conv1x1_wino_in(body, flow, kshape=lambda key: None, small=lambda key: 
 # the stride-2 3x3 conv and the 1x1 stride-2 projection -- both run in ONE launch (q4.ConvQ4Pair,
 # csrc/conv_q4_kernel.h conv_q4_pair_kernel).  The second conv moves up to the first one's place; it only needs the
 # shared input and constants, so that is legal unless something rewrites the input in place in between.
-_IN_PLACE = ("relu", "relu_q4", "clip", "clip_q4", "erf", "instancenormalization")
+_IN_PLACE = ("relu", "relu_q4", "clip", "clip_q4", "erf", "instancenormalization", "instancenormalization_q4")
 
 
 def pair_sibling_convs(body, flow, kshape=lambda key: None):

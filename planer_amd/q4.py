@@ -24,7 +24,8 @@ from .conv_layouts import (dw_q4_eligible, prepare_dw_q4_weights, prepare_q4_wei
                            stem_pool_eligible, stem_pool_nchw_eligible, w1d_q4_eligible, winograd43_eligible, winograd_q4_eligible)
 from .conv_layouts import convt_phase_eligible as convt_q4_eligible, prepare_convt_weights as prepare_convt_q4_weights
 from .hip import DeviceArray, _f32, empty
-from .layer import ACT_NONE, _full, _host_values, _ptr, conv_out_hw, convt_out_hw, convt_q4_call
+from .layer import ACT_NONE, _PAD_MODES, _contig_strides, _full, _host_values, _ptr, _strided_map, conv_out_hw, convt_out_hw, convt_q4_call
+from .plan import ACT_RELU, pad_q4_ok
 
 
 def is_q4(a):
@@ -473,6 +474,49 @@ def ClipQ4(xq, min=0, max=1):
     return xq
 
 
+def InstanceNormQ4(xq, s, bias, resq=None, epsilon=1e-5, act=ACT_NONE):
+    """layer.InstanceNormalization (layer.py:217-226) on a Q4 tensor, IN PLACE like the reference, with the tail the plan
+    compiler folds in (plan.fuse_instnorm_q4): xq = IN(xq) [+ resq] [relu].  One workgroup per (image, quad) for planes of up to
+    _lib.INSTNORM_Q4_ONE_WG_PIXELS pixels, chunk statistics + merge-and-apply above (pl_instancenorm_q4_f32)."""
+    _f32(xq, s, bias, resq)
+    if not is_q4(xq) or (resq is not None and not is_q4(resq)):
+        raise TypeError("InstanceNormQ4 needs Q4 activations (planer_amd.q4.to_q4)")
+    n, c, h, w = logical_shape(xq)
+    if s.size != c or bias.size != c:
+        raise ValueError("instancenormalization: one scale / bias value per channel")
+    if resq is not None and (resq.shape != xq.shape or resq.chan != c):
+        raise ValueError("fused residual shape %s != instancenormalization input %s" % (resq.shape, xq.shape))
+    if int(act) not in (ACT_NONE, ACT_RELU):
+        raise ValueError("InstanceNormQ4: act is 0 (none) or 1 (relu)")
+    if h * w == 0 or xq.size == 0:                      # numpy leaves an empty x as it is
+        return xq
+    _lib.call("pl_instancenorm_q4_f32", xq.ctx.handle, xq.ptr, s.ptr, bias.ptr, _ptr(resq), n, c, h * w, float(epsilon), int(act))
+    return xq
+
+
+def PadQ4(xq, pads, constant_value=0, mode="constant"):
+    """layer.Pad (layer.py:241-245) of the pixel axes of a Q4 tensor: the strided-map kernel on the 5-D view (N, quads, H, W, 4),
+    whose last axis -- the four lanes of a pixel -- is copied as it is.  Only scheduled where plan.pad_q4_ok holds: no padding of
+    N or C, and in constant mode a value that keeps the padding lanes zero."""
+    _f32(xq)
+    if not is_q4(xq):
+        raise TypeError("PadQ4 needs a Q4 activation (planer_amd.q4.to_q4)")
+    if isinstance(constant_value, DeviceArray):
+        constant_value = _host_values(constant_value).reshape(-1)[0]
+    pv = [int(v) for v in _host_values(pads).reshape(-1)]
+    if not pad_q4_ok(xq.chan, pv, constant_value, mode):
+        raise ValueError("PadQ4: pixel pads only (N, C pads 0), modes %s, and a constant of 0 unless C %% 4 == 0" % (sorted(_PAD_MODES),))
+    n, cq, h, w, _ = xq.shape
+    (pt, pl), (pb, pr) = pv[2:4], pv[6:8]
+    if mode != "constant" and ((h == 0 and pt + pb) or (w == 0 and pl + pr)):
+        raise ValueError("can't extend empty axis using modes other than 'constant' or 'empty'")      # np.pad's refusal
+    m = _PAD_MODES[mode]
+    y = _strided_map(xq, [n, cq, h + pt + pb, w + pl + pr, 4], _contig_strides(xq.shape), [0, 0, -pt, -pl, 0], [1] * 5,
+                     extent=list(xq.shape), wrap=[0, 0, m, m, 0], fill=float(constant_value))
+    y.chan = xq.chan
+    return y
+
+
 def LeakyReLUQ4(xq, alpha=0.2):
     y = _like(xq)
     _lib.call("pl_leakyrelu_f32", xq.ctx.handle, xq.ptr, y.ptr, xq.size, float(alpha))
@@ -540,7 +584,8 @@ def UpConcatQ4(aq, k, bq, mode="nearest", axis=1):
 # kind -> Q4 implementation, for plan.assign_layouts (conv kinds are handled by the plan compiler)
 Q4_LAYERS = {"maxpool": MaxpoolQ4, "averagepool": AveragePoolQ4, "gap": GlobalAveragePoolQ4,
              "upsample": UpSampleQ4, "batchnorm": BatchNormQ4, "relu": ReLUQ4, "leakyrelu": LeakyReLUQ4,
-             "sigmoid": SigmoidQ4, "add": AddQ4, "concat": ConcatenateQ4, "clip": ClipQ4}
+             "sigmoid": SigmoidQ4, "add": AddQ4, "concat": ConcatenateQ4, "clip": ClipQ4,
+             "instancenormalization": InstanceNormQ4, "pad": PadQ4}
 
 
 def register(layer_map):
