@@ -19,6 +19,14 @@
 //     patch transform of a step is three TWO-ROW wave-items (wf4_transform_2rows: lane = row of a pair x tile x channel pair) on
 //     waves 1-3.  Layer2 conv of ResNet-18 at batch 32: 43.7 against 62.1 us alone (224 instead of 112 workgroups), bench.py
 //     58.1-58.4 k against 55.9-56.2 k img/s (profiles/r06_ab_wf4_half_blocks.txt).
+//   * The 16-tile block's K step is WOVEN (template parameter WEAVE; PLANER_HIP_EXPERIMENT=wf4_weave=0 brings the phased step
+//     back): no transform phase in front of the MFMAs -- every wave carries a two-row item of chunk c + 1 in pieces behind single
+//     MFMAs of chunk c (mma_weave: reads, first stage column by column, second stage, V writes; scheduling barriers pin the
+//     pieces).  One branch-free instruction stream for all four waves: an item's kind is per-wave DATA (row bases,
+//     coefficients; the three-row kind reads its fourth row out of 1 KB of -0.0 behind the patch buffer), wave 0 repeats wave 1's
+//     item.  Bit-identical to the phased step (tests/test_gpu_wf4_weave.py); 256 registers, no scratch in the K loop, 36.9 KB of
+//     LDS.  Per conv alone / per 32 images at batch 256: layer1 37.0 / 30.3 against 38.7 / 31.9 us, layer2 41.1 / 26.7 against
+//     44.0 / 27.6 us (profiles/wf4_weave.md).
 //   * The filter never touches LDS (round 6, WF4_GLOBAL_A): it is laid out [cout block][chunk][16-channel block][group of 4
 //     frequencies][lane][4], so the fragment a wave needs for one group of four MFMAs is ONE 16-byte load per lane over a
 //     contiguous 1 KB, requested five groups ahead into a ring of six register slots (profiles/r06_wf4_stalls.md: 39.2 / 60.2
@@ -63,7 +71,8 @@ struct Wf4Args {
 };
 
 // probe builds only (tools/wf4_knock.sh): bit 0 no filter LDS-DMA, 1 no patch LDS-DMA, 2 no patch transform, 3 no MFMAs,
-// 4 no fragment reads, 5 no output rows -- results are garbage, the time tells what a K step's parts cost
+// 4 no fragment reads, 5 no output rows -- results are garbage, the time tells what a K step's parts cost.  Bits 2-4 act on
+// every form of the K step (filter in LDS, filter in registers, woven); bit 0 only where the filter is staged in LDS.
 #ifndef WF4_KNOCK
 #define WF4_KNOCK 0
 #endif
@@ -370,9 +379,10 @@ __device__ __forceinline__ void wf4_output_row_coalesced(const Wf4Args &p, const
 // HALF (round 6, needs WF4_GLOBAL_A): a workgroup of FOUR waves carries 16 tiles x 64 output channels -- half the registers and
 // a quarter of the LDS of a CU, so two workgroups share it with barriers of their own: one's prologue, tail and barrier waits
 // run under the other's K loop.  Three two-row transform items (waves 1-3) per K step.
-template <bool DMA_A, bool PLANAR, bool STAGGER, int LBC, bool PACK = false, bool HALF = false>
+template <bool DMA_A, bool PLANAR, bool STAGGER, int LBC, bool PACK = false, bool HALF = false, bool WEAVE = false>
 __device__ __forceinline__ void conv_wf4_body(const Wf4Args &p) {
     constexpr int NT = HALF ? 256 : 512, LT = HALF ? 4 : 5;          // threads, log2(tiles) of a block
+    static_assert(!WEAVE || (HALF && STAGGER), "woven K step: 16-tile blocks only");
     static_assert(!HALF || (WF4_GLOBAL_A && DMA_A && !PLANAR), "half blocks: filter in registers, 16-byte-cell patch");
     // the LDS-DMA requests of a step go out one per MFMA group (measured: 40.9 -> 39.8 us per layer1 conv against all seven
     // in a row at the head of the step)
@@ -388,7 +398,9 @@ __device__ __forceinline__ void conv_wf4_body(const Wf4Args &p) {
 #endif
     // (HALF: one tile half of V, 512 patch cells -- 34.8 KB a workgroup, so that what else runs on the CU keeps its LDS)
     __shared__ __attribute__((aligned(16))) float Vs0[WF4_V_FLOATS / (HALF && WF4_HALF_TRIM ? 2 : 1)], Vs1[WF4_V_FLOATS / (HALF && WF4_HALF_TRIM ? 2 : 1)];      // [2 wn][4 k][16 i][36 f]
-    __shared__ __attribute__((aligned(16))) float Ps0[WF4_P_FLOATS / (HALF && WF4_HALF_TRIM ? 2 : 1)], Ps1[WF4_P_FLOATS / (HALF && WF4_HALF_TRIM ? 2 : 1)];      // [cells][4]  or  [4 ch][cells]
+    // (WEAVE: 1 KB of -0.0 behind each patch buffer -- the "fourth patch row" of the waves whose item reads three, see wv_p3)
+    constexpr int P_TAIL = WEAVE ? 256 : 0, P_BODY = WF4_P_FLOATS / (HALF && WF4_HALF_TRIM ? 2 : 1);
+    __shared__ __attribute__((aligned(16))) float Ps0[P_BODY + P_TAIL], Ps1[P_BODY + P_TAIL];      // [cells][4]  or  [4 ch][cells]
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -554,6 +566,27 @@ __device__ __forceinline__ void conv_wf4_body(const Wf4Args &p) {
         pb2 = 2 * cp + (((t_nb * p.R + 4 * t_r) * 4) * S + t_c) * 4;
         vb2 = ((((tj >> 4) * 4 + 2 * cp) * 16) + (tj & 15)) * 36;
     }
+    // WEAVE: the wave's item as DATA, so that one instruction stream serves every wave.  Each column's first stage is
+    //     m = c1 d0 + (c2 d1 + (c3 d2 + d3))        (fused multiply-adds, innermost first)
+    // over four patch rows.  Waves 2 / 3 (wf4_transform_2rows' KIND 1 / 2): patch rows 1-4, coefficients of rows 1 / 2
+    // (-4, -4, 1) / (4, -4, -1) and rows 3 / 4 (-2, -1, 2) / (2, -1, -2).  Waves 0 / 1 (KIND 0, rows 0 / 5 = 4 d0 - 5 d2 + d4 of patch
+    // rows r, r + 2, r + 4): coefficients (4, -5, 1), and their d3 is read out of the -0.0 tail of the patch buffer --
+    // fma(1, x, -0.0) is x for every x, signed zeros and infinities included, so the value that enters the c2 stage is the one
+    // KIND 0 feeds it: bit-identical.  (d3 selected in registers instead, two v_cndmask per column: 1-2 % slower per conv.)
+    // Bases (float index in the patch buffer): rows 1 and 3 of kinds 1 / 2 share wv_p13 with row 1 of kind 0.
+    const bool wv_k0 = wave < 2;
+    const int wv_p13 = wv_k0 ? pb2 + hr * rs : pb2;
+    const int wv_p0 = wv_k0 ? pb2 + hr * rs : pb2 + rs;
+    const int wv_p2 = wv_k0 ? pb2 + (hr + 4) * rs : pb2 + 3 * rs;
+    const int wv_p3 = wv_k0 ? P_BODY : pb2 + 4 * rs;
+    static_assert(!WEAVE || 3 * psz + 6 <= P_TAIL, "the -0.0 tail must cover every column offset");
+    if constexpr (WEAVE) {
+        if (tid < P_TAIL) Ps0[P_BODY + tid] = Ps1[P_BODY + tid] = -0.f;          // (published by the prologue's first barrier)
+    }
+    const int wv_vb = vb2 + (wv_k0 ? hr * 30 : wave == 2 ? 6 + hr * 6 : 18 + hr * 6);
+    const float wv_c1 = wv_k0 ? 4.f : wave == 2 ? (hr ? 4.f : -4.f) : (hr ? 2.f : -2.f);
+    const float wv_c2 = wv_k0 ? -5.f : wave == 2 ? -4.f : -1.f;
+    const float wv_c3 = wv_k0 ? 1.f : wave == 2 ? (hr ? -1.f : 1.f) : (hr ? -2.f : 2.f);
     auto transform_first = [&](int pbuf, int vbuf) {           // waves 4-7: a whole row (both halves)
         if constexpr (WF4_KNOCK & 4) return;
         const float *Pb = pbuf ? Ps1 : Ps0;
@@ -617,13 +650,18 @@ __device__ __forceinline__ void conv_wf4_body(const Wf4Args &p) {
     };
     auto mma_ga = [&](auto parity, int c, bool more2) {
         constexpr int par = decltype(parity)::value;
+        constexpr bool NOFRAG = (WF4_KNOCK & 16) != 0, NOMMA = (WF4_KNOCK & 8) != 0;
         const float4 *Vp = reinterpret_cast<const float4 *>((par ? Vs1 : Vs0) + b_off);
         float4 fb[3];
-        fb[0] = Vp[0];
-        fb[1] = Vp[1];
+        if constexpr (NOFRAG) {
+            fb[0] = fb[1] = fb[2] = make_float4(1.f, 2.f, 3.f, (float)lane);
+        } else {
+            fb[0] = Vp[0];
+            fb[1] = Vp[1];
+        }
 #pragma unroll
         for (int g = 0; g < 9; ++g) {
-            if (g + 2 < 9) fb[(g + 2) % 3] = Vp[g + 2];
+            if (!NOFRAG && g + 2 < 9) fb[(g + 2) % 3] = Vp[g + 2];
             {
                 const int gn = g + GA_D;                    // the group AHEAD: same chunk or the next one
                 auto issue = [&](auto sl) { ga_load(sl, gn < 9 ? c : c + 1, gn < 9 ? gn : gn - 9); };
@@ -640,10 +678,118 @@ __device__ __forceinline__ void conv_wf4_body(const Wf4Args &p) {
                 }
             }
             const float4 a = ga[(9 * par + g) % GA_SLOTS], b = fb[g % 3];
+            if constexpr (NOMMA) {
+                acc[4 * g + 0].x += a.x * b.x; acc[4 * g + 1].x += a.y * b.y; acc[4 * g + 2].x += a.z * b.z; acc[4 * g + 3].x += a.w * b.w;
+            } else {
             acc[4 * g + 0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, acc[4 * g + 0], 0, 0, 0);
             acc[4 * g + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b.y, acc[4 * g + 1], 0, 0, 0);
             acc[4 * g + 2] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b.z, acc[4 * g + 2], 0, 0, 0);
             acc[4 * g + 3] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b.w, acc[4 * g + 3], 0, 0, 0);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            if (g < WF4_P_PASSES) {
+                if (more2) load_p_piece(c + 2, par, g);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+    };
+    // WEAVE: the same K step with the wave's two-row transform item of chunk c + 1 cut into pieces that ride BEHIND single MFMAs of
+    // chunk c: slot s = 4 g + h follows MFMA h of group g.  A vector instruction issued by the wave that owns the matrix pipe costs
+    // 3-4 cycles of matrix time, the same instruction from the sibling wave ~20 (profiles/r04_mfma_valu.txt).
+    //   slots 0, 2 .. 10    patch column b = s / 2: its four 8-byte reads (P[nxt] landed a step ago)
+    //   slots 5, 7 .. 15    first stage of column b = (s - 5) / 2 -- at most three columns (24 registers) are in flight
+    //   slots 17 .. 22      second stage (wf4_bt2's operations in wf4_bt2's order), the V[nxt] writes behind their values
+    // (measured: the item 4 or 8 slots later, or 3 / 7 slots between a column's reads and its first stage, all within +-1 %)
+    // ONE branch-free instruction stream for all four waves and all steps; the item kinds differ in DATA (wv_* above).  Two other
+    // forms were compiled and dropped: a stream per item kind (the register allocator copies the 144 accumulators at the joins:
+    // 850 spilled registers) and scalar branches around the pieces (each piece becomes a basic block of its own and the
+    // compiler sinks the patch reads into the block that uses them: read, wait, multiply -- the latency the weave is there to
+    // hide).  So wave 0 repeats wave 1's item (same values to the same cells) and the last step transforms a patch nobody
+    // multiplies (V[nxt] is free until the epilogue's barrier).  Every slot ends in a scheduling barrier, so the pieces stay where
+    // they are put; the step's closing barrier publishes V[nxt] as before.
+    auto mma_weave = [&](auto parity, int c, bool more2) {
+        constexpr int par = decltype(parity)::value;
+        constexpr bool NOFRAG = (WF4_KNOCK & 16) != 0, NOMMA = (WF4_KNOCK & 8) != 0, ITEM = (WF4_KNOCK & 4) == 0;
+        const float4 *Vp = reinterpret_cast<const float4 *>((par ? Vs1 : Vs0) + b_off);
+        const float *Pn = par ? Ps0 : Ps1;
+        float *v0 = (par ? Vs0 : Vs1) + wv_vb, *v1 = v0 + 16 * 36;
+        wf4_v2 d[6][4], m[6], o[6], s2, t2;
+        auto item_slot = [&](int s) {
+            constexpr int R0 = 0, S1 = R0 + 5, S2 = S1 + 12;
+            if (!ITEM || s < R0 || s > S2 + 5) return;
+            if (s < R0 + 12 && ((s - R0) & 1) == 0) {
+                const int b = (s - R0) >> 1, co = (b & 3) * psz + (b >> 2) * 4;
+                d[b][0] = *reinterpret_cast<const wf4_v2 *>(Pn + wv_p0 + co);
+                d[b][1] = *reinterpret_cast<const wf4_v2 *>(Pn + wv_p13 + co + 2 * rs);
+                d[b][2] = *reinterpret_cast<const wf4_v2 *>(Pn + wv_p2 + co);
+                d[b][3] = *reinterpret_cast<const wf4_v2 *>(Pn + wv_p3 + co);
+            }
+            if (s >= S1 && s < S1 + 12 && ((s - S1) & 1) == 0) {
+                const int b = (s - S1) >> 1;
+                m[b] = wf4_fma2(wv_c1, d[b][0], wf4_fma2(wv_c2, d[b][1], wf4_fma2(wv_c3, d[b][2], d[b][3])));
+            }
+            if (s == S2) {
+                s2 = m[4] - m[2];
+                t2 = m[3] - m[1];
+                o[0] = wf4_fma2(4.f, m[0], wf4_fma2(-5.f, m[2], m[4]));
+            }
+            if (s == S2 + 1) o[1] = wf4_fma2(-4.f, m[1] + m[2], m[3] + m[4]);
+            if (s == S2 + 2) o[2] = wf4_fma2(4.f, m[1] - m[2], m[4] - m[3]);
+            if (s == S2 + 3) {
+                o[3] = wf4_fma2(2.f, t2, s2);
+                o[4] = wf4_fma2(-2.f, t2, s2);
+            }
+            if (s == S2 + 4) o[5] = wf4_fma2(4.f, m[1], wf4_fma2(-5.f, m[3], m[5]));
+            if (s == S2 + 2 || s == S2 + 4 || s == S2 + 5) {
+                const int j = s == S2 + 2 ? 0 : s == S2 + 4 ? 2 : 4;
+                v0[j] = o[j].x;
+                v0[j + 1] = o[j + 1].x;
+                v1[j] = o[j].y;
+                v1[j + 1] = o[j + 1].y;
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        };
+        float4 fb[3];
+        if constexpr (NOFRAG) {
+            fb[0] = fb[1] = fb[2] = make_float4(1.f, 2.f, 3.f, (float)lane);
+        } else {
+            fb[0] = Vp[0];
+            fb[1] = Vp[1];
+        }
+#pragma unroll
+        for (int g = 0; g < 9; ++g) {
+            if (!NOFRAG && g + 2 < 9) fb[(g + 2) % 3] = Vp[g + 2];
+            {
+                const int gn = g + GA_D;
+                auto issue = [&](auto sl) { ga_load(sl, gn < 9 ? c : c + 1, gn < 9 ? gn : gn - 9); };
+                switch ((9 * par + g + GA_D) % GA_SLOTS) {
+                case 0: issue(std::integral_constant<int, 0>{}); break;
+                case 1: issue(std::integral_constant<int, 1>{}); break;
+                case 2: issue(std::integral_constant<int, 2>{}); break;
+                case 3: issue(std::integral_constant<int, 3>{}); break;
+                case 4: issue(std::integral_constant<int, 4>{}); break;
+                case 5: issue(std::integral_constant<int, 5 % GA_SLOTS>{}); break;
+                case 6: issue(std::integral_constant<int, 6 % GA_SLOTS>{}); break;
+                case 7: issue(std::integral_constant<int, 7 % GA_SLOTS>{}); break;
+                default: issue(std::integral_constant<int, 8 % GA_SLOTS>{}); break;
+                }
+            }
+            const float4 a = ga[(9 * par + g) % GA_SLOTS], b = fb[g % 3];
+            if constexpr (NOMMA) {
+                acc[4 * g + 0].x += a.x * b.x; acc[4 * g + 1].x += a.y * b.y; acc[4 * g + 2].x += a.z * b.z; acc[4 * g + 3].x += a.w * b.w;
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int h = 0; h < 4; ++h) item_slot(4 * g + h);
+            } else {
+                acc[4 * g + 0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, acc[4 * g + 0], 0, 0, 0);
+                item_slot(4 * g + 0);
+                acc[4 * g + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b.y, acc[4 * g + 1], 0, 0, 0);
+                item_slot(4 * g + 1);
+                acc[4 * g + 2] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b.z, acc[4 * g + 2], 0, 0, 0);
+                item_slot(4 * g + 2);
+                acc[4 * g + 3] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b.w, acc[4 * g + 3], 0, 0, 0);
+                item_slot(4 * g + 3);
+            }
             __builtin_amdgcn_sched_barrier(0);
             if (g < WF4_P_PASSES) {
                 if (more2) load_p_piece(c + 2, par, g);
@@ -733,10 +879,14 @@ __device__ __forceinline__ void conv_wf4_body(const Wf4Args &p) {
             // ago; an LDS-DMA instruction holds a wave's issue slot ~100 cycles, seven of them would delay the transform
             // their MFMAs wait for): 38.2 -> 37.6 us
             WF4_STEP_MARK(c, 0);
-            if (more) transform_first(nxt, nxt);
+            if (!WEAVE && more) transform_first(nxt, nxt);
             WF4_STEP_MARK(c, 1);
 #if WF4_GLOBAL_A
-            mma_ga(parity, c, more2);
+            if constexpr (WEAVE) {
+                mma_weave(parity, c, more2);           // every wave carries its item of chunk c + 1 inside its own MFMA stream
+            } else {
+                mma_ga(parity, c, more2);
+            }
 #else
             if constexpr (SPREAD) {
                 mma(cur, c, more, more2, std::true_type{});
@@ -838,9 +988,9 @@ __device__ __forceinline__ void conv_wf4_body(const Wf4Args &p) {
 #endif
 }
 
-template <bool DMA_A, bool PLANAR, bool STAGGER, int LBC, bool PACK = false, bool HALF = false>
+template <bool DMA_A, bool PLANAR, bool STAGGER, int LBC, bool PACK = false, bool HALF = false, bool WEAVE = false>
 __global__ void __launch_bounds__(HALF ? 256 : 512) __attribute__((amdgpu_waves_per_eu(2, 2))) conv_wf4_kernel(const Wf4Args p) {
-    conv_wf4_body<DMA_A, PLANAR, STAGGER, LBC, PACK, HALF>(p);
+    conv_wf4_body<DMA_A, PLANAR, STAGGER, LBC, PACK, HALF, WEAVE>(p);
 }
 
 // filter: OIHW 3x3 -> u[cout block][chunk][cb][kk][i][f] = (G g G^T)[f] of channel (64 blk + 16 cb + i, 4 chunk + kk); zero beyond Cout

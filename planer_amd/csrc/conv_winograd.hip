@@ -989,6 +989,9 @@ int w1d_launch(pl_ctx *ctx, const float *xq, int N, int Cin, int H, int W, const
 #ifndef WF4_HALF_DEFAULT
 #define WF4_HALF_DEFAULT 1
 #endif
+#ifndef WF4_WEAVE_DEFAULT
+#define WF4_WEAVE_DEFAULT 1
+#endif
 #ifndef WF4_STAGGER
 #define WF4_STAGGER true      // (probe builds: false = every wave multiplies first, the patch transform follows)
 #endif
@@ -1004,6 +1007,9 @@ int wf4_launch(pl_ctx *ctx, const float *xq, int N, int Cin, int H, int W, const
     // blocks of 32 tiles on eight waves, or (PLANER_HIP_EXPERIMENT=wf4_half=1; needs the filter-in-registers build) of 16 tiles on
     // four waves -- two workgroups per CU with barriers of their own
     const bool half = WF4_GLOBAL_A && pl_experiment("wf4_half", WF4_HALF_DEFAULT) != 0;
+    // the 16-tile block's K step with each wave's transform item woven into its own MFMA stream (conv_wf4_kernel.h, WEAVE), or
+    // (PLANER_HIP_EXPERIMENT=wf4_weave=0) as a phase of its own in front of the MFMAs
+    const bool weave = half && WF4_STAGGER && pl_experiment("wf4_weave", WF4_WEAVE_DEFAULT) != 0;
     const int TB = half ? 16 : 32;
     int BC = 1, BR = 1, lBC = 0, lBR = 0;
     while (BC < a.tw && BC < 16) BC *= 2, ++lBC;
@@ -1056,7 +1062,17 @@ int wf4_launch(pl_ctx *ctx, const float *xq, int N, int Cin, int H, int W, const
     // per block width, so that every patch read is base + immediate
     void (*kern)(const Wf4Args) = nullptr;
 #if WF4_GLOBAL_A
-    if (half) {
+    if (half && weave) {
+        switch (a.pack_g ? 10 + lBC : lBC) {
+        case 14: kern = conv_wf4_kernel<true, false, true, 4, true, true, true>; break;
+        case 13: kern = conv_wf4_kernel<true, false, true, 3, true, true, true>; break;
+        case 4: kern = conv_wf4_kernel<true, false, true, 4, false, true, true>; break;
+        case 3: kern = conv_wf4_kernel<true, false, true, 3, false, true, true>; break;
+        case 2: kern = conv_wf4_kernel<true, false, true, 2, false, true, true>; break;
+        case 1: kern = conv_wf4_kernel<true, false, true, 1, false, true, true>; break;
+        default: kern = conv_wf4_kernel<true, false, true, 0, false, true, true>; break;
+        }
+    } else if (half) {
         switch (a.pack_g ? 10 + lBC : lBC) {
         case 14: kern = conv_wf4_kernel<true, false, WF4_STAGGER, 4, true, true>; break;
         case 13: kern = conv_wf4_kernel<true, false, WF4_STAGGER, 3, true, true>; break;
@@ -1080,7 +1096,7 @@ int wf4_launch(pl_ctx *ctx, const float *xq, int N, int Cin, int H, int W, const
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(half ? 256 : 512), 0, ctx->stream, a);      // LDS: static
     PL_LAUNCH_CHECK();
     char buf[96];
-    snprintf(buf, sizeof buf, "wf4 64co x %dtiles (%dx%dx%d%s) blocks=%lld", TB, NB, BR, BC, a.pack_g ? " packed" : "", blocks);
+    snprintf(buf, sizeof buf, "wf4 64co x %dtiles%s (%dx%dx%d%s) blocks=%lld", TB, weave ? " woven" : "", NB, BR, BC, a.pack_g ? " packed" : "", blocks);
     ctx->last_plan = buf;
     ctx->last_gemm[0] = 36; ctx->last_gemm[1] = (long long)a.cout_blocks * 64;
     ctx->last_gemm[2] = groups * a.rblocks * a.cblocks * TB; ctx->last_gemm[3] = Cin;
