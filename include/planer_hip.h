@@ -424,6 +424,16 @@ int pl_scale_shift_q4_f32(pl_ctx *ctx, const float *xq, float *yq, const float *
 #define PL_INSTNORM_Q4_CHUNK_PIXELS 2048
 int pl_instancenorm_q4_f32(pl_ctx *ctx, float *xq, const float *scale, const float *bias, const float *resq,
                            int N, int C, int HW, double eps, int act);
+/* Pixel-phase re-layout of a Q4 tensor.  The (N, C, H, W) activation "folded by (dh, dw)" is the Q4
+ * tensor of logical shape (N*dh*dw, C, ceil(H/dh), ceil(W/dw)): image (n*dh + i)*dw + j holds at pixel (r, c) the quads of
+ * x[n, :, r*dh + i, c*dw + j], and zero in all four lanes where that coordinate lies outside H x W.  A 3x3 / stride 1 conv with
+ * dilation (dh, dw) and pads (dh, dw, dh, dw) on x is the 3x3 / pad 1 / dilation 1 conv on the folded tensor.  This entry takes
+ * a tensor folded by (dh_in, dw_in) to the same activation folded by (dh_out, dw_out); (1, 1) is the unfolded tensor, so it
+ * folds, unfolds and goes from fold to fold.  N, C, H, W are the UNFOLDED shape.  Every output quad is written, the zero-fill
+ * cells included; the input's zero-fill cells are never read (a conv leaves junk there).  Bits are moved, not computed on.
+ * 2^29 quads or more on either side: PL_EUNSUPPORTED. */
+int pl_refold_q4_f32(pl_ctx *ctx, const float *xq, float *yq, int N, int C, int H, int W, int dh_in, int dw_in, int dh_out,
+                     int dw_out);
 
 /* First call for a new conv shape times every applicable tile configuration
  * and remembers the fastest (on by default; PLANER_HIP_AUTOTUNE=0 or 0 here

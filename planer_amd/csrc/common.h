@@ -84,6 +84,9 @@ struct pl_ctx {
     std::unordered_set<void *> cap_blocks;
     std::multimap<size_t, void *> cap_free;
     std::unordered_set<void *> graph_owned;  // pl_free on these is a no-op
+    // graphs whose owner dropped them while this stream was capturing: destroying one synchronises the stream, which would
+    // invalidate the capture, so they wait here until pl_capture_end
+    std::vector<pl_graph *> cap_doomed;
 
     // conv tuning overrides
     int conv_cfg = -1;

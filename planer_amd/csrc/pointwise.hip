@@ -357,6 +357,37 @@ __global__ void __launch_bounds__(TPB) upsample_q4_kernel(const float4 *x, float
     }
 }
 
+// Pixel-phase re-layout of a channel-quad tensor.  A tensor "folded by (dh, dw)" holds the (N, C, H, W) activation
+// as N*dh*dw images of ceil(H/dh) x ceil(W/dw) pixels: image (n*dh + i)*dw + j, pixel (r, c) = x[n, :, r*dh + i, c*dw + j], zero
+// where that coordinate lies outside H x W.  One output quad per lane, consecutive lanes store consecutive quads; the gather is
+// on the read side (a 16-byte store at a 64-byte stride runs at a third of a contiguous one's rate, profiles/r04_pointwise_gbs.md).
+// Every output quad is written, the zero-fill cells included; a coordinate inside H x W never maps to a zero-fill cell of the
+// input, so those -- junk behind a conv -- are never read.
+__global__ void __launch_bounds__(TPB) refold_q4_kernel(const float4 *x, float4 *y, unsigned total, int Cq, int H, int W, int Hi,
+                                                        int Wi, int dih, int diw, int doh, int dow, FastDiv divWo, FastDiv divHo,
+                                                        FastDiv divCq, FastDiv divDow, FastDiv divDoh, FastDiv divDih,
+                                                        FastDiv divDiw) {
+    const unsigned stride = gridDim.x * TPB;
+    for (unsigned i = blockIdx.x * TPB + threadIdx.x; i < total; i += stride) {      // i = ((m*Cq + q)*Ho + r)*Wo + c
+        unsigned row, c, mq, r, m, q, t, jo, n, io;
+        divWo.divmod(i, row, c);
+        divHo.divmod(row, mq, r);
+        divCq.divmod(mq, m, q);
+        divDow.divmod(m, t, jo);
+        divDoh.divmod(t, n, io);
+        const unsigned py = r * (unsigned)doh + io, px = c * (unsigned)dow + jo;      // the unfolded pixel
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (py < (unsigned)H && px < (unsigned)W) {
+            unsigned ri, ii, ci, ji;
+            divDih.divmod(py, ri, ii);
+            divDiw.divmod(px, ci, ji);
+            const size_t mi = ((size_t)n * dih + ii) * diw + ji;
+            v = x[((mi * Cq + q) * Hi + ri) * Wi + ci];
+        }
+        y[i] = v;
+    }
+}
+
 // layer.Concatenate (layer.py:90-91) of TWO channel-quad tensors along channels in one launch, the first one optionally
 // nearest-upsampled by (fh, fw) on the way (layer.UpSample, layer.py:80-82 -> util.upsample_nearest): the route layers of
 // a detection net -- upsample -> concat -- are one pass over the output instead of three kernels.
@@ -1080,6 +1111,41 @@ int pl_upsample_nearest_q4_f32(pl_ctx *ctx, const float *xq, float *yq, int N, i
     upsample_q4_kernel<<<stream_grid(ctx, total), TPB, 0, ctx->stream>>>(
         (const float4 *)xq, (float4 *)yq, (unsigned)total, H, W, H * fh, W * fw, FastDiv(W * fw), FastDiv(H * fh),
         FastDiv(fh), FastDiv(fw));
+    PL_LAUNCH_CHECK();
+    return PL_OK;
+}
+
+// Q4 tensor folded by (dh_in, dw_in) -> the same activation folded by (dh_out, dw_out); (1, 1) is the unfolded tensor, so this
+// folds, unfolds and goes from one fold to another.  N, C, H, W: the UNFOLDED logical shape.
+int pl_refold_q4_f32(pl_ctx *ctx, const float *xq, float *yq, int N, int C, int H, int W, int dh_in, int dw_in, int dh_out,
+                     int dw_out) {
+    PL_REQUIRE(ctx && xq && yq, PL_EINVAL, "pl_refold_q4_f32: null argument");
+    PL_REQUIRE(N >= 0 && C > 0 && H > 0 && W > 0, PL_EINVAL, "pl_refold_q4_f32: bad shape");
+    PL_REQUIRE(dh_in > 0 && dw_in > 0 && dh_out > 0 && dw_out > 0, PL_EINVAL, "pl_refold_q4_f32: a fold is at least 1");
+    PL_REQUIRE(aligned16(xq) && aligned16(yq), PL_EINVAL, "pl_refold_q4_f32: Q4 tensors must be 16-byte aligned");
+    PL_REQUIRE(xq != yq, PL_EINVAL, "pl_refold_q4_f32: not an in-place operation");
+    const int Cq = (C + 3) / 4;
+    // quads of the tensor folded by (dh, dw), saturating at 2^29: every factor is checked before the next multiplication
+    auto quads = [&](int dh, int dw, int &Hf, int &Wf) {
+        const size_t lim = 1ull << 29;
+        Hf = (H + dh - 1) / dh;
+        Wf = (W + dw - 1) / dw;
+        size_t t = (size_t)N;
+        for (size_t f : {(size_t)dh, (size_t)dw, (size_t)Cq, (size_t)Hf, (size_t)Wf}) {
+            if (t >= lim) return lim;
+            t *= f;                                             // t < 2^29, f < 2^31
+        }
+        return t < lim ? t : lim;
+    };
+    int Hi, Wi, Ho, Wo;
+    const size_t in_total = quads(dh_in, dw_in, Hi, Wi), total = quads(dh_out, dw_out, Ho, Wo);
+    PL_REQUIRE(in_total < (1ull << 29) && total < (1ull << 29) && loop32_ok(ctx, total), PL_EUNSUPPORTED,
+               "pl_refold_q4_f32: Q4 tensor of 2^29 pixel quads (8 GiB) or more");
+    if (!total) return PL_OK;
+    CtxGuard g(ctx);
+    refold_q4_kernel<<<stream_grid(ctx, total), TPB, 0, ctx->stream>>>(
+        (const float4 *)xq, (float4 *)yq, (unsigned)total, Cq, H, W, Hi, Wi, dh_in, dw_in, dh_out, dw_out, FastDiv(Wo), FastDiv(Ho),
+        FastDiv(Cq), FastDiv(dw_out), FastDiv(dh_out), FastDiv(dh_in), FastDiv(dw_in));
     PL_LAUNCH_CHECK();
     return PL_OK;
 }

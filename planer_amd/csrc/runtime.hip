@@ -473,10 +473,23 @@ int pl_capture_begin(pl_ctx *ctx) {
     return PL_OK;
 }
 
+static int capture_end_locked(pl_ctx *ctx, pl_graph **out);
+
 int pl_capture_end(pl_ctx *ctx, pl_graph **out) {
     PL_REQUIRE(ctx && out, PL_EINVAL, "pl_capture_end: null argument");
     CtxGuard g(ctx);
-    std::lock_guard<std::mutex> lk(ctx->mu);
+    std::vector<pl_graph *> doomed;
+    int rc;
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        rc = capture_end_locked(ctx, out);
+        doomed.swap(ctx->cap_doomed);
+    }
+    for (pl_graph *d : doomed) pl_graph_destroy(d);     // dropped by their owners while the stream was capturing
+    return rc;
+}
+
+static int capture_end_locked(pl_ctx *ctx, pl_graph **out) {
     PL_REQUIRE(ctx->capturing, PL_EINVAL, "no capture in progress");
     ctx->capturing = false;
     hipGraph_t graph = nullptr;
@@ -518,6 +531,17 @@ int pl_graph_launch(pl_graph *g) {
 int pl_graph_destroy(pl_graph *g) {
     if (!g) return PL_OK;
     pl_ctx *ctx = g->ctx;
+    {
+        // The owner may drop a graph at any moment -- Python's cycle collector runs when it likes -- and that moment may be
+        // inside another plan's capture on this context's stream.  The synchronise below is illegal on a capturing stream and
+        // invalidates the capture (the next launch fails with "operation failed due to a previous error during capture"), so
+        // such a graph is destroyed when the capture ends.
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        if (ctx->capturing) {
+            ctx->cap_doomed.push_back(g);
+            return PL_OK;
+        }
+    }
     CtxGuard guard(ctx);
     (void)hipStreamSynchronize(ctx->stream);
     if (g->exec) (void)hipGraphExecDestroy(g->exec);

@@ -282,8 +282,9 @@ def _upsample_linear(x, fh, fw):
         if fh * fw > 64:
             raise NotImplementedError("linear upsample: fh * fw <= 64 on the HIP path, got %d x %d" % (fh, fw))
         tab = _linear_weights(fh, fw)
+        # (a ctypes array, like the host tables of transpose and the strided map: a plan file records its bytes)
         _lib.call("pl_upsample_linear_f32", x.ctx.handle, x.ptr, y.ptr, n * c, h, w, fh, fw,
-                  tab.ctypes.data_as(_lib.POINTER(_lib.c_float)))
+                  (_lib.c_float * tab.size)(*tab.reshape(-1).tolist()))
         return y
     oh, ow = int(round(fh * h)), int(round(fw * w))
     if h < 2 or w < 2:

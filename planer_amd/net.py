@@ -30,7 +30,8 @@ from . import q4 as _q4
 from .conv_layouts import (CONV_KINDS, CONVT_KINDS, DIRECT_Q4, IGEMM_NCHW, LAYOUTS, ROWPACK_Q4, STEM_POOL, STEM_POOL_NCHW, WINO4_Q4,
                            WINO43_Q4, choose, suffix)
 from .layer import layer_map, wrap
-from .plan import assign_layouts, chain_winograd, fuse_conv1x1_wino_in, fuse_flow, fuse_instnorm_q4, pair_sibling_convs
+from .plan import (assign_layouts, chain_winograd, fold_dilated, fuse_conv1x1_wino_in, fuse_flow, fuse_instnorm_q4,
+                   pair_sibling_convs)
 
 _q4.register(layer_map)
 
@@ -319,6 +320,12 @@ class Net:
         # compiled plans keep activations channel-quad (Q4) between layers that have Q4 kernels
         # "force": channel-quad layout wherever a Q4 kernel exists, whatever the conversion-cost estimate says (tests)
         self.use_q4 = {"0": False, "force": "force"}.get(os.environ.get("PLANER_HIP_Q4", "1"), True)
+        # dilated 3x3 convs folded by pixel phase onto the Winograd kernels (plan.fold_dilated): False (the default:
+        # the program of a compiler without the pass), True = where it measures faster (_fold_worth), "force" = every eligible conv
+        self.fold_dilated = {"1": True, "force": "force"}.get(os.environ.get("PLANER_HIP_DILATED_FOLD", "0"), False)
+        self.dilated_folds = 0       # dilated convs the last plan runs folded
+        self.refolds = 0             # refold_q4 steps of the last plan
+        self._fold_pick = {}         # (x shape, filter shape, dilation) -> fold or not, as measured (_fold_worth)
         # streams: how many sub-batch graphs a forward pass is fanned out to ("auto" measures 1/2/4)
         self.streams = os.environ.get("PLANER_HIP_STREAMS", "auto")
         self._side = []
@@ -453,6 +460,8 @@ class Net:
                     record.append({"layer": lname, "kind": obj.name, "w_layout": lay,
                                    "algo": W_LAYOUT_NAMES.get(lay, str(lay)), "plan": ctx_.last_conv_plan(),
                                    "extents": list(ctx_.last_conv_extents()), "x": list(xshape)})
+                    if getattr(args[0], "fold", None) is not None:       # a conv on a folded tensor: `x` is the folded shape
+                        record[-1]["fold"] = list(args[0].fold)
                 if record is not None and obj.name == "instancenormalization_q4":
                     # the form taken ("instnorm-q4 one-wg" / "instnorm-q4 chunks=S"), as the entry point left it
                     record.append({"layer": name, "kind": obj.name, "w_layout": None, "algo": "instnorm-q4",
@@ -510,6 +519,12 @@ class Net:
                                            values=lambda key: wmap[key].host if key in wmap else None)
             # instancenormalization_q4 -> [add_q4] -> [relu_q4] as one step: the tail goes into the norm's write pass
             body, flow, self.instnorm_fused = fuse_instnorm_q4(body, flow, shapes)
+            if self.fold_dilated:
+                worth = (lambda xs, ks, para: True) if self.fold_dilated == "force" else self._fold_worth
+                body, flow, regions = fold_dilated(body, flow, shapes, worth)
+                self.dilated_folds = sum(len(r["heads"]) for r in regions)
+                refold_layers = {b[0] for b in body if b[1] == "refold_q4"}
+                self.refolds = sum(1 for f in flow if f[1][0] in refold_layers)
         if os.environ.get("PLANER_HIP_TAPMAJOR", "1") != "0":
             body, flow = self._prepare_filters(body, flow, shapes)
         return _Program(body, flow), nfused
@@ -707,6 +722,54 @@ class Net:
         self._algo_dirty = True
         return best
 
+    def _fold_worth(self, xs, ks, para):
+        """plan.fold_dilated's `worth` under PLANER_HIP_DILATED_FOLD=1: is the dilated conv of input `xs` and filter `ks` faster
+        folded?  Times (a) the conv as it stands -- the direct kernel at its own shape -- against (b) refold in, the picked
+        candidate at the folded shape, refold out, by the burst protocol of _pick_conv_algo.  Both refolds are charged to the
+        one conv although a run of folded convs shares them: deliberately conservative.  The verdict is cached per (input,
+        filter, dilation) beside the algorithm picks (table "dilated_fold" of the algo cache file)."""
+        from .conv_layouts import candidates
+        fold = tuple(int(v) for v in para["dilations"])
+        sig = ("fold", tuple(xs), tuple(ks), fold)
+        self._load_algo_cache()
+        if sig in self._fold_pick:
+            return self._fold_pick[sig]
+        self.algo_misses += 1
+        ctx = self.ctx
+        rng = numpy.random.default_rng(1234)
+        x = _q4.to_q4(hip.asarray(rng.standard_normal(xs).astype(numpy.float32), ctx=ctx))
+        K = hip.asarray((rng.standard_normal(ks) * 0.05).astype(numpy.float32), ctx=ctx)
+        geo = {k: v for k, v in para.items() if k in ("group", "strides", "dilations", "pads")}
+        one = dict(geo, dilations=[1, 1], pads=[1, 1, 1, 1])
+        fxs = _q4.folded_shape(xs, *fold)
+        cands = candidates(True, tuple(ks), one, fxs)
+        lay = cands[0] if len(cands) == 1 else self._pick_conv_algo(cands, K, ["~fold_probe", "~k"], one, {"~fold_probe": fxs}, q4=True)
+        Kd, Kf = LAYOUTS[DIRECT_Q4].prepare(K, **geo), LAYOUTS[lay].prepare(K, **one)
+
+        def folded():
+            y = _q4.ConvQ4(_q4.refold_q4(x, *fold), Kf, w_layout=lay, **one)
+            return _q4.refold_q4(y, 1, 1)
+        ms = []
+        for run in (lambda: _q4.ConvQ4(x, Kd, w_layout=DIRECT_Q4, **geo), folded):
+            for _ in range(3):
+                run()
+            best = None
+            for _ in range(3):                     # best of three bursts of 8
+                e0 = hip.Event(ctx).record()
+                for _ in range(8):
+                    run()
+                e1 = hip.Event(ctx).record()
+                t = e0.elapsed_ms(e1) / 8
+                best = t if best is None else min(best, t)
+            ms.append(best)
+        if os.environ.get("PLANER_CONV_TUNE_LOG"):
+            import sys
+            print("[planer_amd] dilated conv %s k%s d%s: direct %.1f us, folded on w_layout %d (with both refolds) %.1f us"
+                  % (tuple(xs), tuple(ks), fold, ms[0] * 1e3, lay, ms[1] * 1e3), file=sys.stderr)
+        self._fold_pick[sig] = ms[1] < ms[0]
+        self._algo_dirty = True
+        return self._fold_pick[sig]
+
     @staticmethod
     def _sig_key(sig):
         return repr(sig)
@@ -744,6 +807,11 @@ class Net:
                     except (ValueError, SyntaxError):
                         pass
             self._streams_pick.update({str(k): str(v) for k, v in stored.get("streams", {}).items()})
+            for k, v in stored.get("dilated_fold", {}).items():
+                try:
+                    self._fold_pick[ast.literal_eval(k)] = bool(v)
+                except (ValueError, SyntaxError):
+                    pass
 
     def save_algo_cache(self, path=None):
         """Persist the per-shape conv algorithm choices and the stream-plan choices (next to PLANER_HIP_TUNE_CACHE
@@ -756,6 +824,8 @@ class Net:
                 "algo": {self._sig_key(k): v for k, v in sorted(self._algo.items(), key=repr)},
                 "algo_throughput": {self._sig_key(k): v for k, v in sorted(self._algo_tp.items(), key=repr)},
                 "streams": dict(sorted(self._streams_pick.items()))}
+        if self._fold_pick:
+            data["dilated_fold"] = {self._sig_key(k): bool(v) for k, v in sorted(self._fold_pick.items(), key=repr)}
         tmp = "%s.%d.tmp" % (path, os.getpid())
         with open(tmp, "w") as f:
             json.dump(data, f, indent=1)

@@ -426,7 +426,7 @@ def fuse_instnorm_q4(body, flow, shapes):
 _PURE_READERS = ("conv_q4", "convt_q4", "wino4_in", "wino4_gemm", "wino4_out", "wino4_chain", "wino43_in", "wino43_gemm", "wino43_out",
                  "wino43_chain", "conv1x1_wino_in", "conv_q4_pair", "add_q4", "maxpool_q4",
                  "averagepool_q4", "gap_q4", "upsample_q4", "concat_q4", "upconcat_q4", "batchnorm_q4",
-                 "leakyrelu_q4", "sigmoid_q4", "from_q4", "pad_q4")
+                 "leakyrelu_q4", "sigmoid_q4", "from_q4", "pad_q4", "refold_q4")
 
 
 def chain_winograd(body, flow, supported=lambda key: True, chain=True):
@@ -595,3 +595,175 @@ def pair_sibling_convs(body, flow, kshape=lambda key: None):
             seen.add(name)
             out_body.append([name, kind, para])
     return out_body, [[srcs, [name], dst] for srcs, name, kind, para, dst in out], npairs
+
+
+# ---- dilated 3x3 convs on the Winograd kernels: pixel-phase folding ------------------------------------------------------------
+# A 3x3 / stride 1 conv with dilation (dh, dw) and pads (dh, dw, dh, dw) is dh * dw independent 3x3 / pad 1 convs, one per pixel
+# phase x[:, :, i::dh, j::dw].  With the phases moved into the batch axis (q4.refold_q4: the tensor "folded by (dh, dw)") it is
+# an ordinary conv on (N dh dw, C, ceil(H/dh), ceil(W/dw)) that every Winograd layout takes.  Where dh | H and dw | W the folded
+# tensor has no zero-fill cells and position-independent steps run on it as they are, so a run of dilated convs is folded once
+# on the way in and unfolded once on the way out.  On other maps the conv leaves junk in the zero-fill cells -- the next
+# folded conv would read it as padding -- so it folds alone: in, conv, out.
+FOLD_SEP = "~"
+REFOLD = "@refold_q4"
+_FOLD_POINTWISE = ("relu_q4", "leakyrelu_q4", "clip_q4", "sigmoid_q4", "batchnorm_q4", "add_q4", "concat_q4")
+_FOLD_IN_PLACE = ("relu_q4", "clip_q4", "instancenormalization_q4")
+
+
+def folded_key(key, fold, junk=False):
+    """The key of tensor `key` folded by `fold`: the part before the first "@" -- what every pass looks shapes up by -- gets the
+    fold, so the folded tensor has a shape entry of its own.  `junk`: the output of a conv that folds alone, whose zero-fill
+    cells hold junk -- a key of its own, so that a clean folded copy of the same tensor can exist beside it."""
+    if tuple(fold) == (1, 1):
+        return key
+    base = key.split("@")[0]
+    return "%s%s%dx%d%s%s" % (base, FOLD_SEP, fold[0], fold[1], "j" if junk else "", key[len(base):])
+
+
+def _folded_shape(shape, fold):
+    n, c, h, w = shape
+    return (n * fold[0] * fold[1], c, -(-h // fold[0]), -(-w // fold[1]))
+
+
+def _act_positions(kind, srcs):
+    """Positions of the activation operands of a step that can run on folded tensors (the others are constants)."""
+    if kind == "conv_q4":
+        return [0] + ([5] if len(srcs) > 5 and srcs[5] != "None" else [])
+    if kind == "batchnorm_q4":
+        return [0]
+    return [i for i, k in enumerate(srcs) if k != "None"]
+
+
+def fold_dilated(body, flow, shapes, worth=lambda x_shape, k_shape, para: True):
+    """-> (body', flow', regions).  Runs on assign_layouts' program (one layer per step).  A `conv_q4` step is a HEAD when it
+    has a constant 4-D 3x3 filter, strides [1, 1], dilations [dh, dw] with dh * dw > 1, pads [dh, dw, dh, dw], is neither
+    depthwise nor row-packed, would be w1d_q4_eligible at dilation 1 / pad 1, and `worth(x_shape, k_shape, para)` agrees.  It is
+    rewritten to dilation 1 / pad 1 on its input folded by (dh, dw) -- same filter key, so prepared filters are shared with
+    undilated users.  Where dh | H and dw | W, steps of position-independent kinds that read a tensor folded by (dh, dw) JOIN:
+    other heads of that dilation, 1x1 / stride 1 / pad 0 convs, relu / leakyrelu / clip / sigmoid / batchnorm / add and concat
+    along channels; all their activation operands are brought to the fold.  Everything else reads unfolded tensors, and the
+    program's result is unfolded.  One fold state per key as in assign_layouts' `need`: `refold_q4` steps are inserted where a
+    value is needed in a fold it does not have (fold to fold directly), converted copies are cached per (key, fold) and dropped
+    when a step rewrites their tensor in place.  Folded tensors get keys of their own (`folded_key`) and `shapes` gains their
+    shapes.  `regions`: one {"fold", "dividing", "heads", "steps"} per run of steps that share folded tensors."""
+    from .conv_layouts import w1d_q4_eligible
+    kinds = {b[0]: b for b in body}
+    steps = [[list(src) if isinstance(src, (list, tuple)) else [src], names[0] if isinstance(names, (list, tuple)) else names, dst]
+             for src, names, dst in flow]
+    forms = {}            # key -> the folds it exists in, the one it was produced in first; absent: unfolded only
+    region_of = {}        # key -> index of the region that produced it folded
+    copy_region = {}      # (key, fold) -> index of the region a folded copy of an operand was first made for
+    out, regions = [], []
+
+    def shape(key):
+        s = shapes.get(key.split("@")[0])
+        return tuple(s) if s is not None and len(s) == 4 else None
+
+    def need(key, fold):
+        if key == "None":
+            return key
+        have = forms.setdefault(key, [(1, 1)])
+        if fold not in have:
+            src = have[0]
+            out.append(([folded_key(key, src)], REFOLD, "refold_q4", {"to": list(fold), "from": list(src)}, folded_key(key, fold)))
+            have.append(fold)
+            if fold != (1, 1) and shape(key) is not None:
+                shapes[folded_key(key, fold).split("@")[0]] = _folded_shape(shape(key), fold)
+        return folded_key(key, fold)
+
+    def head_fold(kind, para, srcs):
+        if kind != "conv_q4" or para.get("rowpack") or len(srcs) < 2:
+            return None
+        k, x = shapes.get(srcs[1]), shape(srcs[0])
+        d = [int(v) for v in para.get("dilations", (1, 1))]
+        if k is None or x is None or len(k) != 4 or len(d) != 2 or d[0] * d[1] <= 1 or min(d) < 1:
+            return None
+        group = int(para.get("group", 1))
+        if ([int(v) for v in para.get("pads", (0, 0, 0, 0))] != [d[0], d[1], d[0], d[1]] or dw_q4_eligible(tuple(k), group)
+                or not w1d_q4_eligible(tuple(k), group, para.get("strides", (1, 1)), (1, 1), (1, 1, 1, 1))):
+            return None
+        return (d[0], d[1]) if worth(x, tuple(k), dict(para)) else None
+
+    def joins(kind, para, srcs, fold):
+        """A position-independent step with an operand whose tensor is folded by `fold` (and, for a conv, the right geometry)."""
+        if not any(forms.get(srcs[p], [(1, 1)])[0] == fold for p in _act_positions(kind, srcs)):
+            return False
+        if kind == "conv_q4":
+            k = shapes.get(srcs[1])
+            return (not para.get("rowpack") and k is not None and len(k) == 4 and tuple(k[2:]) == (1, 1)
+                    and [int(v) for v in para.get("strides", (1, 1))] == [1, 1] and not any(int(v) for v in para.get("pads", (0, 0, 0, 0))))
+        if kind == "concat_q4":
+            return int(para.get("axis", 0)) in (1, -3)
+        return kind in _FOLD_POINTWISE
+
+    last = len(steps) - 1
+    for i, (srcs, name, dst) in enumerate(steps):
+        _, kind, para = kinds[name]
+        fold, head = None, False
+        if isinstance(dst, str):
+            fold = head_fold(kind, para, srcs)
+            head = fold is not None
+            if not head:
+                # the folds its operands are in, in operand order: the step joins the first it can run in
+                for p in (_act_positions(kind, srcs) if kind == "conv_q4" or kind in _FOLD_POINTWISE else []):
+                    f = forms.get(srcs[p], [(1, 1)])[0]
+                    if f != (1, 1) and joins(kind, para, srcs, f):
+                        fold = f
+                        break
+        if fold is None:
+            args = [need(k, (1, 1)) if k in forms else k for k in srcs]
+            out.append((args, name, kind, para, dst))
+            if kind in _IN_PLACE and srcs:
+                forms[srcs[0]] = [(1, 1)]
+            for k in _as_list(dst):
+                forms[k] = [(1, 1)]
+                region_of.pop(k, None)
+            continue
+        x = shape(srcs[0])
+        dividing = x is not None and x[2] % fold[0] == 0 and x[3] % fold[1] == 0
+        acts = _act_positions(kind, srcs)
+        # the region: that of an operand already folded this way, else a new one
+        reg = next((region_of[srcs[p]] for p in acts if srcs[p] in region_of and forms.get(srcs[p], [None])[0] == fold), None)
+        if reg is None:                                 # ... or that of the step a cached folded copy of an operand was made for
+            reg = next((copy_region[(srcs[p], fold)] for p in acts
+                        if (srcs[p], fold) in copy_region and fold in forms.get(srcs[p], [])), None)
+        if reg is None or not dividing:
+            regions.append({"fold": list(fold), "dividing": bool(dividing), "heads": [], "steps": []})
+            reg = len(regions) - 1
+        args = list(srcs)
+        for p in acts:
+            args[p] = need(srcs[p], fold)
+            if dividing:
+                copy_region.setdefault((srcs[p], fold), reg)
+        if head:
+            para = dict(para, dilations=[1, 1], pads=[1, 1, 1, 1])
+            regions[reg]["heads"].append(name)
+        regions[reg]["steps"].append(name)
+        fdst = folded_key(dst, fold, junk=not dividing)
+        out.append((args, name, kind, para, fdst))
+        if kind in _FOLD_IN_PLACE:
+            forms[srcs[0]] = [fold]                     # rewritten in this fold: the other copies are stale
+        ys = shape(dst)
+        if ys is not None:
+            shapes[fdst.split("@")[0]] = _folded_shape(ys, fold)
+        forms[dst] = [fold]
+        region_of[dst] = reg
+        if not dividing or i == last:
+            # zero-fill cells hold junk behind the conv: nothing may read this tensor folded.  (And a program ends unfolded.)
+            out.append(([fdst], REFOLD, "refold_q4", {"to": [1, 1], "from": list(fold)}, dst))
+            forms[dst] = [(1, 1)]
+            region_of.pop(dst, None)
+    out_body, seen = [], set()
+    named = []
+    nre = 0
+    for srcs, name, kind, para, dst in out:
+        if kind == "refold_q4":                          # one layer per (from, to) pair: a layer's parameters are its own
+            name = "%s:%dx%d>%dx%d" % (REFOLD, para["from"][0], para["from"][1], para["to"][0], para["to"][1])
+            nre += 1
+        if name not in seen:
+            seen.add(name)
+            out_body.append([name, kind, para])
+        named.append([srcs, [name], dst])
+    if not regions:
+        return [list(b) for b in body], [[list(s) if isinstance(s, (list, tuple)) else s, n, d] for s, n, d in flow], []
+    return out_body, named, regions

@@ -66,6 +66,47 @@ def from_q4(xq):
     return y
 
 
+def _carry_fold(dst, src):
+    """A position-independent step keeps its input's pixel-phase fold (refold_q4): same map, same image order."""
+    if dst is not None and src is not None and src.fold is not None:
+        dst.fold = src.fold
+    return dst
+
+
+def folded_shape(shape, dh, dw):
+    """Logical shape of the (N, C, H, W) activation folded by (dh, dw): the pixel phases x[:, :, i::dh, j::dw] as images."""
+    n, c, h, w = shape
+    return (n * dh * dw, c, -(-h // dh), -(-w // dw))
+
+
+def refold_q4(xq, dh=1, dw=1, to=None, **check):
+    """The Q4 tensor `xq` folded by (dh, dw) (pl_refold_q4_f32): image (n*dh + i)*dw + j of the result holds the pixels
+    x[n, :, i::dh, j::dw] of the activation `xq` stands for, zero-filled to ceil(H/dh) x ceil(W/dw).  `xq` may itself be folded
+    (`xq.fold`): (1, 1) unfolds, anything else goes from fold to fold in one pass.  A 3x3 / stride 1 conv with dilation (dh, dw)
+    and pads (dh, dw, dh, dw) is ConvQ4(dilations=(1, 1), pads=(1, 1, 1, 1)) on the folded tensor, residual folded the same way.
+    As a plan step (kind `refold_q4`) the target comes as `to=[dh, dw]`; `from=[dh, dw]`, where the plan gives it, must be the
+    fold the input really carries."""
+    _f32(xq)
+    if not is_q4(xq):
+        raise TypeError("refold_q4 needs a Q4 activation (planer_amd.q4.to_q4)")
+    if to is not None:
+        dh, dw = to
+    dh, dw = int(dh), int(dw)
+    if dh < 1 or dw < 1:
+        raise ValueError("refold_q4: a fold is at least 1, got (%d, %d)" % (dh, dw))
+    nf, c, hf, wf = logical_shape(xq)
+    sdh, sdw, h, w = xq.fold if xq.fold is not None else (1, 1, hf, wf)
+    if check.get("from") is not None and tuple(int(v) for v in check["from"]) != (sdh, sdw):
+        raise ValueError("refold_q4: the plan expects an input folded by %s, this one is folded by %s" % (tuple(check["from"]), (sdh, sdw)))
+    n = nf // (sdh * sdw)
+    y = _new_q4(*folded_shape((n, c, h, w), dh, dw), xq.ctx)
+    if dh * dw > 1:
+        y.fold = (dh, dw, h, w)
+    if y.size:
+        _lib.call("pl_refold_q4_f32", xq.ctx.handle, xq.ptr, y.ptr, n, c, h, w, sdh, sdw, dh, dw)
+    return y
+
+
 def ConvTransposeQ4(xq, Kq, B=None, scale=None, shift=None, resq=None, strides=(2, 2), dilations=(1, 1), pads=(0, 0, 0, 0),
                     output_padding=(0, 0), group=1, act=ACT_NONE, alpha=0.0, w_layout=0, **_):
     """layer.ConvTranspose2d with the fused tail of ConvQ4 on Q4 tensors, by output phase (pl_conv2d_convt_q4_f32).
@@ -147,6 +188,8 @@ def ConvQ4(xq, Kq, B=None, scale=None, shift=None, resq=None, group=1, strides=(
     y = _new_q4(n, cout, ho, wo, xq.ctx)
     if resq is not None and resq.shape != y.shape:
         raise ValueError("fused residual shape %s != conv output %s" % (resq.shape, y.shape))
+    if (ho, wo) == (h, w):
+        _carry_fold(y, xq)                             # a folded conv (refold_q4): the output is folded like the input
     lay = LAYOUTS.get(w_layout)
     if lay is not None and lay.kernel:
         # the Winograd families and the fused 1-D F(4,3) share one signature
@@ -278,7 +321,7 @@ def Wino4In(xq):
     if not is_q4(xq):
         raise TypeError("Wino4In needs a Q4 activation")
     n, c, h, w = logical_shape(xq)
-    v = _wino_tensor(n, c, h, w, xq.ctx)
+    v = _carry_fold(_wino_tensor(n, c, h, w, xq.ctx), xq)
     _lib.call("pl_wino4_input_q4_f32", xq.ctx.handle, xq.ptr, n, c, h, w, v.ptr)
     return v
 
@@ -289,7 +332,7 @@ def Wino4Gemm(v, Kq, **_):
     cout, cin_k, kh, kw = Kq.shape
     if cin_k != cin or (kh, kw) != (3, 3):
         raise ValueError("conv: weight %s does not match input %s" % (Kq.shape, (n, cin, h, w)))
-    m = _wino_tensor(n, cout, h, w, v.ctx)
+    m = _carry_fold(_wino_tensor(n, cout, h, w, v.ctx), v)
     _lib.call("pl_wino4_gemm_q4_f32", v.ctx.handle, v.ptr, n, cin, h, w, Kq.ptr, cout, m.ptr)
     return m
 
@@ -305,7 +348,7 @@ def Wino4Out(m, B=None, scale=None, shift=None, resq=None, act=ACT_NONE, alpha=0
     """A^T m A + the conv's fused tail -> y (Q4)."""
     _f32(B, scale, shift, resq)
     n, c, h, w = _wino_tail_check(m, resq)
-    y = _new_q4(n, c, h, w, m.ctx)
+    y = _carry_fold(_new_q4(n, c, h, w, m.ctx), m)
     _lib.call("pl_wino4_output_q4_f32", m.ctx.handle, m.ptr, n, c, h, w, _ptr(B), _ptr(scale), _ptr(shift), _ptr(resq),
               int(act), float(alpha), y.ptr)
     return y
@@ -316,8 +359,8 @@ def Wino4Chain(m, B=None, scale=None, shift=None, resq=None, act=ACT_NONE, alpha
     (nothing else reads y), V alone -- y then never exists in memory."""
     _f32(B, scale, shift, resq)
     n, c, h, w = _wino_tail_check(m, resq)
-    y = _new_q4(n, c, h, w, m.ctx) if keep_y else None
-    v = _wino_tensor(n, c, h, w, m.ctx)
+    y = _carry_fold(_new_q4(n, c, h, w, m.ctx), m) if keep_y else None
+    v = _carry_fold(_wino_tensor(n, c, h, w, m.ctx), m)
     _lib.call("pl_wino4_chain_q4_f32", m.ctx.handle, m.ptr, n, c, h, w, _ptr(B), _ptr(scale), _ptr(shift), _ptr(resq),
               int(act), float(alpha), _ptr(y), v.ptr)
     return (y, v) if keep_y else v
@@ -337,7 +380,7 @@ def Wino43In(xq):
     if not is_q4(xq):
         raise TypeError("Wino43In needs a Q4 activation")
     n, c, h, w = logical_shape(xq)
-    v = _wino43_tensor(n, c, h, w, xq.ctx)
+    v = _carry_fold(_wino43_tensor(n, c, h, w, xq.ctx), xq)
     _lib.call("pl_wino43_input_q4_f32", xq.ctx.handle, xq.ptr, n, c, h, w, v.ptr)
     return v
 
@@ -347,7 +390,7 @@ def Wino43Gemm(v, Kq, **_):
     cout, cin_k, kh, kw = Kq.shape
     if cin_k != cin or (kh, kw) != (3, 3):
         raise ValueError("conv: weight %s does not match input %s" % (Kq.shape, (n, cin, h, w)))
-    m = _wino43_tensor(n, cout, h, w, v.ctx)
+    m = _carry_fold(_wino43_tensor(n, cout, h, w, v.ctx), v)
     _lib.call("pl_wino43_gemm_q4_f32", v.ctx.handle, v.ptr, n, cin, h, w, Kq.ptr, cout, m.ptr)
     return m
 
@@ -355,7 +398,7 @@ def Wino43Gemm(v, Kq, **_):
 def Wino43Out(m, B=None, scale=None, shift=None, resq=None, act=ACT_NONE, alpha=0.0, **_):
     _f32(B, scale, shift, resq)
     n, c, h, w = _wino_tail_check(m, resq)
-    y = _new_q4(n, c, h, w, m.ctx)
+    y = _carry_fold(_new_q4(n, c, h, w, m.ctx), m)
     _lib.call("pl_wino43_output_q4_f32", m.ctx.handle, m.ptr, n, c, h, w, _ptr(B), _ptr(scale), _ptr(shift), _ptr(resq),
               int(act), float(alpha), y.ptr)
     return y
@@ -364,8 +407,8 @@ def Wino43Out(m, B=None, scale=None, shift=None, resq=None, act=ACT_NONE, alpha=
 def Wino43Chain(m, B=None, scale=None, shift=None, resq=None, act=ACT_NONE, alpha=0.0, keep_y=True, **_):
     _f32(B, scale, shift, resq)
     n, c, h, w = _wino_tail_check(m, resq)
-    y = _new_q4(n, c, h, w, m.ctx) if keep_y else None
-    v = _wino43_tensor(n, c, h, w, m.ctx)
+    y = _carry_fold(_new_q4(n, c, h, w, m.ctx), m) if keep_y else None
+    v = _carry_fold(_wino43_tensor(n, c, h, w, m.ctx), m)
     _lib.call("pl_wino43_chain_q4_f32", m.ctx.handle, m.ptr, n, c, h, w, _ptr(B), _ptr(scale), _ptr(shift), _ptr(resq),
               int(act), float(alpha), _ptr(y), v.ptr)
     return (y, v) if keep_y else v
@@ -382,7 +425,7 @@ def Conv1x1WinoIn(xq, Kq, B=None, scale=None, shift=None, act=ACT_NONE, alpha=0.
     cout, cin_k, kh, kw = Kq.shape
     if (kh, kw) != (1, 1) or cin_k != cin or cout % 4 or int(wino) != 4:
         raise ValueError("Conv1x1WinoIn: 1x1 filter %s on input %s, Cout %% 4 == 0, F(4x4,3x3) tiles" % (Kq.shape, (n, cin, h, w)))
-    v = _wino_tensor(n, cout, h, w, xq.ctx)
+    v = _carry_fold(_wino_tensor(n, cout, h, w, xq.ctx), xq)
     _lib.call("pl_conv1x1_wino_in_q4_f32", xq.ctx.handle, xq.ptr, n, cin, h, w, Kq.ptr, cout, _ptr(B), _ptr(scale), _ptr(shift),
               int(act), float(alpha), int(wino), v.ptr)
     return v
@@ -392,7 +435,7 @@ def Conv1x1WinoIn(xq, Kq, B=None, scale=None, shift=None, act=ACT_NONE, alpha=0.
 def _like(x, shape=None):
     y = empty(shape or x.shape, ctx=x.ctx)
     y.chan = x.chan
-    return y
+    return _carry_fold(y, x) if shape is None else y
 
 
 def _pool_q4(xq, w, pads, strides, mode):
@@ -550,7 +593,7 @@ def ConcatenateQ4(*xs, axis=1):
     total = sum(a.chan for a in xs)
     if len(xs) == 2:
         return UpConcatQ4(xs[0], None, xs[1])
-    y = _new_q4(n, total, h, w, xs[0].ctx)
+    y = _carry_fold(_new_q4(n, total, h, w, xs[0].ctx), xs[0])
     off, pitch = 0, (total // 4) * h * w * 4
     for a in xs:
         width = a.shape[1] * h * w * 4
@@ -576,7 +619,7 @@ def UpConcatQ4(aq, k, bq, mode="nearest", axis=1):
     nb, cb, h, w = logical_shape(bq)
     if nb != n or (ha * fh, wa * fw) != (h, w):
         raise ValueError("concat: shapes differ off the axis: %s (x%d, x%d) vs %s" % ((n, ca, ha, wa), fh, fw, (nb, cb, h, w)))
-    y = _new_q4(n, ca + cb, h, w, aq.ctx)
+    y = _carry_fold(_new_q4(n, ca + cb, h, w, aq.ctx), bq)
     _lib.call("pl_concat2_q4_f32", aq.ctx.handle, aq.ptr, bq.ptr, y.ptr, n, ca, cb, h, w, fh, fw)
     return y
 
@@ -590,7 +633,7 @@ Q4_LAYERS = {"maxpool": MaxpoolQ4, "averagepool": AveragePoolQ4, "gap": GlobalAv
 
 def register(layer_map):
     """Plan-internal kinds (never present in a user's IR)."""
-    layer_map.update({"to_q4": to_q4, "from_q4": from_q4, "conv_q4": ConvQ4, "convt_q4": ConvTransposeQ4, "upconcat_q4": UpConcatQ4,
+    layer_map.update({"to_q4": to_q4, "from_q4": from_q4, "refold_q4": refold_q4, "conv_q4": ConvQ4, "convt_q4": ConvTransposeQ4, "upconcat_q4": UpConcatQ4,
                       "wino4_in": Wino4In, "wino4_gemm": Wino4Gemm, "wino4_out": Wino4Out, "wino4_chain": Wino4Chain,
                       "conv_q4_pair": ConvQ4Pair, "conv_pool_q4": ConvPoolQ4, "conv1x1_wino_in": Conv1x1WinoIn,
                       "wino43_in": Wino43In, "wino43_gemm": Wino43Gemm, "wino43_out": Wino43Out, "wino43_chain": Wino43Chain})
