@@ -406,6 +406,14 @@ int pl_pool2d_q4_f32(pl_ctx *ctx, const float *xq, float *yq, int N, int C, int 
                      int mode);
 int pl_upsample_nearest_q4_f32(pl_ctx *ctx, const float *xq, float *yq, int N, int C,
                                int H, int W, int fh, int fw);
+/* The channel-quad twins of pl_upsample_linear_f32 / pl_resize_linear_f32 (below): same host weight table and same device
+ * position tables, per component the same roundings, so from_q4(twin(to_q4(x))) equals the NCHW entry bit for bit.  `resq`: NULL
+ * or a Q4 tensor of the output's shape, added in the write pass as a rounding of its own (= the upsample followed by pl_add_f32).
+ * Every quad of yq is written; xq != yq; fewer than 2^30 output quads. */
+int pl_upsample_linear_q4_f32(pl_ctx *ctx, const float *xq, float *yq, const float *resq, int N, int C, int H, int W, int fh,
+                              int fw, const float *weights);
+int pl_resize_linear_q4_f32(pl_ctx *ctx, const float *xq, float *yq, const float *resq, int N, int C, int H, int W, int OH,
+                            int OW, const int *ra, const float *rs, const int *ca, const float *cs);
 /* layer.Concatenate (axis 1) of two Q4 tensors in one launch; the first is nearest-upsampled by (fh, fw) on the way
  * (layer.UpSample + layer.Concatenate, layer.py:80-82, 90-91): a is (N, Ca, H/fh, W/fw), b (N, Cb, H, W), y (N, Ca+Cb, H, W). */
 int pl_concat2_q4_f32(pl_ctx *ctx, const float *aq, const float *bq, float *yq, int N, int Ca, int Cb, int H, int W, int fh,

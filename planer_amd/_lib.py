@@ -129,6 +129,8 @@ SIGNATURES = {
     "pl_conv2d_w1d4_q4_f32": [_P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _I, c_double],
     "pl_pool2d_q4_f32": [_P, _P, _P] + [_I] * 13,
     "pl_upsample_nearest_q4_f32": [_P, _P, _P, _I, _I, _I, _I, _I, _I],
+    "pl_upsample_linear_q4_f32": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, POINTER(ctypes.c_float)],
+    "pl_resize_linear_q4_f32": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P],
     "pl_gap_q4_f32": [_P, _P, _P, _I, _I, _I],
     "pl_concat2_q4_f32": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I],
     "pl_scale_shift_q4_f32": [_P, _P, _P, _P, _P, _I, _I, _I],

@@ -531,6 +531,53 @@ struct UpLinArgs {
     float w[4 * 64];
 };
 
+// Where output pixel (oy, ox) of the integer-factor map samples: clamped rows r0 / r1, columns c0 / c1 and the offset of its
+// weights in the (terms, fh, fw) table.  Shared by the NCHW kernel and its channel-quad twin.
+struct UpLinTap {
+    int r0, r1, c0, c1, wofs;
+};
+
+__device__ __forceinline__ UpLinTap uplin_tap(const UpLinArgs &p, int oy, int ox) {
+    UpLinTap t;
+    t.r0 = oy; t.r1 = oy; t.c0 = ox; t.c1 = ox;
+    int a = 0, b = 0;
+    if (p.fh > 1) {
+        const int Y = oy + p.fh / 2, q = Y / p.fh;
+        a = Y - q * p.fh;
+        t.r0 = max(q - 1, 0);
+        t.r1 = min(q, p.H - 1);
+    }
+    if (p.fw > 1) {
+        const int X = ox + p.fw / 2, q = X / p.fw;
+        b = X - q * p.fw;
+        t.c0 = max(q - 1, 0);
+        t.c1 = min(q, p.W - 1);
+    }
+    t.wofs = a * p.fw + b;
+    return t;
+}
+
+// One component of the integer-factor interpolation.  The chain starts from +0 like the oracle's matrix product: an all -0
+// neighbourhood gives +0, not -0.  Four terms: lt, rt, lb, rb; two terms: (a, b) are the two samples of the one axis.
+__device__ __forceinline__ float uplin4(float lt, float rt, float lb, float rb, const float *w, int kk) {
+    float v = __fmaf_rn(lt, w[0], 0.f);
+    v = __fmaf_rn(rt, w[kk], v);
+    v = __fmaf_rn(lb, w[2 * kk], v);
+    return __fmaf_rn(rb, w[3 * kk], v);
+}
+
+__device__ __forceinline__ float uplin2(float a, float b, const float *w, int kk) {
+    return __fmaf_rn(b, w[kk], __fmaf_rn(a, w[0], 0.f));
+}
+
+// One component of the fractional interpolation: columns first, a*(1-fc) + b*fc, then rows on those -- the reference's order of
+// roundings.
+__device__ __forceinline__ float resize_lerp(float lt, float rt, float lb, float rb, float fc, float gc, float fr, float gr) {
+    const float top = __fadd_rn(__fmul_rn(lt, gc), __fmul_rn(rt, fc));
+    const float bot = __fadd_rn(__fmul_rn(lb, gc), __fmul_rn(rb, fc));
+    return __fadd_rn(__fmul_rn(top, gr), __fmul_rn(bot, fr));
+}
+
 __global__ void __launch_bounds__(TPB) upsample_linear_kernel(const float *x, float *y, unsigned total, UpLinArgs p,
                                                               FastDiv divOW, FastDiv divOH) {
     const unsigned stride = gridDim.x * TPB;
@@ -540,34 +587,16 @@ __global__ void __launch_bounds__(TPB) upsample_linear_kernel(const float *x, fl
         divOW.divmod(i, row, ox);
         divOH.divmod(row, plane, oy);
         const float *xp = x + (size_t)plane * p.H * p.W;
-        int r0 = (int)oy, r1 = (int)oy, a = 0, c0 = (int)ox, c1 = (int)ox, b = 0;
-        if (p.fh > 1) {
-            const int Y = (int)oy + p.fh / 2, q = Y / p.fh;
-            a = Y - q * p.fh;
-            r0 = max(q - 1, 0);
-            r1 = min(q, p.H - 1);
-        }
-        if (p.fw > 1) {
-            const int X = (int)ox + p.fw / 2, q = X / p.fw;
-            b = X - q * p.fw;
-            c0 = max(q - 1, 0);
-            c1 = min(q, p.W - 1);
-        }
-        const float *w = p.w + a * p.fw + b;
-        // the chain starts from +0 like the oracle's matrix product: an all -0 neighbourhood gives +0, not -0
+        const UpLinTap t = uplin_tap(p, (int)oy, (int)ox);
+        const float *w = p.w + t.wofs;
         float v;
-        if (p.terms == 4) {
-            v = __fmaf_rn(xp[(size_t)r0 * p.W + c0], w[0], 0.f);
-            v = __fmaf_rn(xp[(size_t)r0 * p.W + c1], w[kk], v);
-            v = __fmaf_rn(xp[(size_t)r1 * p.W + c0], w[2 * kk], v);
-            v = __fmaf_rn(xp[(size_t)r1 * p.W + c1], w[3 * kk], v);
-        } else if (p.fw > 1) {
-            v = __fmaf_rn(xp[(size_t)r0 * p.W + c0], w[0], 0.f);
-            v = __fmaf_rn(xp[(size_t)r0 * p.W + c1], w[kk], v);
-        } else {
-            v = __fmaf_rn(xp[(size_t)r0 * p.W + c0], w[0], 0.f);
-            v = __fmaf_rn(xp[(size_t)r1 * p.W + c0], w[kk], v);
-        }
+        if (p.terms == 4)
+            v = uplin4(xp[(size_t)t.r0 * p.W + t.c0], xp[(size_t)t.r0 * p.W + t.c1], xp[(size_t)t.r1 * p.W + t.c0],
+                       xp[(size_t)t.r1 * p.W + t.c1], w, kk);
+        else if (p.fw > 1)
+            v = uplin2(xp[(size_t)t.r0 * p.W + t.c0], xp[(size_t)t.r0 * p.W + t.c1], w, kk);
+        else
+            v = uplin2(xp[(size_t)t.r0 * p.W + t.c0], xp[(size_t)t.r1 * p.W + t.c0], w, kk);
         y[i] = v;
     }
 }
@@ -587,9 +616,67 @@ __global__ void __launch_bounds__(TPB) resize_planes_kernel(const float *x, floa
         const float fr = rs[oy], fc = cs[ox];
         const float gc = __fsub_rn(1.f, fc), gr = __fsub_rn(1.f, fr);
         const float *p0 = x + ((size_t)plane * H + r0) * W + c0, *p1 = p0 + W;
-        const float top = __fadd_rn(__fmul_rn(p0[0], gc), __fmul_rn(p0[1], fc));
-        const float bot = __fadd_rn(__fmul_rn(p1[0], gc), __fmul_rn(p1[1], fc));
-        y[i] = __fadd_rn(__fmul_rn(top, gr), __fmul_rn(bot, fr));
+        y[i] = resize_lerp(p0[0], p0[1], p1[0], p1[1], fc, gc, fr, gr);
+    }
+}
+
+// The channel-quad twins: one output quad per lane, i = ((n*Cq + q)*OH + oy)*OW + ox, consecutive lanes store
+// consecutive quads; the gather is on the read side, where the fh*fw outputs of a neighbourhood hit the same four input quads in
+// cache.  Per component the arithmetic is the NCHW kernel's (the helpers above), so zero lanes stay +0.  `res`, where given, is
+// added in the write pass as a rounding of its own -- never contracted into the last fma -- so the step equals the upsample
+// followed by an add bit for bit.
+__device__ __forceinline__ float4 q4_add_res(float4 v, const float4 *res, unsigned i) {
+    if (res) {
+        const float4 r = res[i];
+        v.x = __fadd_rn(v.x, r.x); v.y = __fadd_rn(v.y, r.y); v.z = __fadd_rn(v.z, r.z); v.w = __fadd_rn(v.w, r.w);
+    }
+    return v;
+}
+
+__global__ void __launch_bounds__(TPB) upsample_linear_q4_kernel(const float4 *x, float4 *y, const float4 *res, unsigned total,
+                                                                 UpLinArgs p, FastDiv divOW, FastDiv divOH) {
+    const unsigned stride = gridDim.x * TPB;
+    const int kk = p.fh * p.fw;
+    for (unsigned i = blockIdx.x * TPB + threadIdx.x; i < total; i += stride) {
+        unsigned row, ox, plane, oy;
+        divOW.divmod(i, row, ox);
+        divOH.divmod(row, plane, oy);
+        const float4 *xp = x + (size_t)plane * p.H * p.W;
+        const UpLinTap t = uplin_tap(p, (int)oy, (int)ox);
+        const float *w = p.w + t.wofs;
+        float4 v;
+        if (p.terms == 4) {
+            const float4 lt = xp[(size_t)t.r0 * p.W + t.c0], rt = xp[(size_t)t.r0 * p.W + t.c1];
+            const float4 lb = xp[(size_t)t.r1 * p.W + t.c0], rb = xp[(size_t)t.r1 * p.W + t.c1];
+            v.x = uplin4(lt.x, rt.x, lb.x, rb.x, w, kk); v.y = uplin4(lt.y, rt.y, lb.y, rb.y, w, kk);
+            v.z = uplin4(lt.z, rt.z, lb.z, rb.z, w, kk); v.w = uplin4(lt.w, rt.w, lb.w, rb.w, w, kk);
+        } else {
+            const float4 a = xp[(size_t)t.r0 * p.W + t.c0];
+            const float4 b = p.fw > 1 ? xp[(size_t)t.r0 * p.W + t.c1] : xp[(size_t)t.r1 * p.W + t.c0];
+            v.x = uplin2(a.x, b.x, w, kk); v.y = uplin2(a.y, b.y, w, kk);
+            v.z = uplin2(a.z, b.z, w, kk); v.w = uplin2(a.w, b.w, w, kk);
+        }
+        y[i] = q4_add_res(v, res, i);
+    }
+}
+
+__global__ void __launch_bounds__(TPB) resize_linear_q4_kernel(const float4 *x, float4 *y, const float4 *res, unsigned total,
+                                                               int H, int W, const int *ra, const float *rs, const int *ca,
+                                                               const float *cs, FastDiv divOW, FastDiv divOH) {
+    const unsigned stride = gridDim.x * TPB;
+    for (unsigned i = blockIdx.x * TPB + threadIdx.x; i < total; i += stride) {
+        unsigned row, ox, plane, oy;
+        divOW.divmod(i, row, ox);
+        divOH.divmod(row, plane, oy);
+        const int r0 = ra[oy], c0 = ca[ox];
+        const float fr = rs[oy], fc = cs[ox];
+        const float gc = __fsub_rn(1.f, fc), gr = __fsub_rn(1.f, fr);
+        const float4 *p0 = x + ((size_t)plane * H + r0) * W + c0, *p1 = p0 + W;
+        const float4 lt = p0[0], rt = p0[1], lb = p1[0], rb = p1[1];
+        float4 v;
+        v.x = resize_lerp(lt.x, rt.x, lb.x, rb.x, fc, gc, fr, gr); v.y = resize_lerp(lt.y, rt.y, lb.y, rb.y, fc, gc, fr, gr);
+        v.z = resize_lerp(lt.z, rt.z, lb.z, rb.z, fc, gc, fr, gr); v.w = resize_lerp(lt.w, rt.w, lb.w, rb.w, fc, gc, fr, gr);
+        y[i] = q4_add_res(v, res, i);
     }
 }
 
@@ -1111,6 +1198,51 @@ int pl_upsample_nearest_q4_f32(pl_ctx *ctx, const float *xq, float *yq, int N, i
     upsample_q4_kernel<<<stream_grid(ctx, total), TPB, 0, ctx->stream>>>(
         (const float4 *)xq, (float4 *)yq, (unsigned)total, H, W, H * fh, W * fw, FastDiv(W * fw), FastDiv(H * fh),
         FastDiv(fh), FastDiv(fw));
+    PL_LAUNCH_CHECK();
+    return PL_OK;
+}
+
+// The channel-quad twin of pl_upsample_linear_f32: same host weight table, same two-term forms, same limits.  `resq`: NULL or a
+// Q4 tensor of the output's shape, added in the write pass (a rounding of its own).
+int pl_upsample_linear_q4_f32(pl_ctx *ctx, const float *xq, float *yq, const float *resq, int N, int C, int H, int W, int fh,
+                              int fw, const float *weights) {
+    PL_REQUIRE(ctx && xq && yq && weights, PL_EINVAL, "pl_upsample_linear_q4_f32: null argument");
+    PL_REQUIRE(N >= 0 && C > 0 && H > 0 && W > 0 && fh > 0 && fw > 0, PL_EINVAL, "pl_upsample_linear_q4_f32: bad shape");
+    PL_REQUIRE(fh * fw > 1, PL_EINVAL, "pl_upsample_linear_q4_f32: factors 1 x 1 are the identity");
+    PL_REQUIRE(fh <= 64 && fw <= 64 && fh * fw <= 64, PL_EUNSUPPORTED, "pl_upsample_linear_q4_f32: fh * fw <= 64 supported, got %d",
+               fh * fw);
+    PL_REQUIRE(aligned16(xq) && aligned16(yq) && aligned16(resq), PL_EINVAL,
+               "pl_upsample_linear_q4_f32: Q4 tensors must be 16-byte aligned");
+    PL_REQUIRE(xq != yq, PL_EINVAL, "pl_upsample_linear_q4_f32: cannot run in place");
+    const size_t total = (size_t)N * ((C + 3) / 4) * H * fh * W * fw;
+    if (!total) return PL_OK;
+    PL_REQUIRE(total < (1ull << 30), PL_EUNSUPPORTED, "upsample: tensor too large");
+    UpLinArgs p;
+    p.H = H; p.W = W; p.fh = fh; p.fw = fw;
+    p.terms = (fh > 1 && fw > 1) ? 4 : 2;
+    for (int i = 0; i < 4 * 64; ++i) p.w[i] = i < p.terms * fh * fw ? weights[i] : 0.f;
+    CtxGuard g(ctx);
+    upsample_linear_q4_kernel<<<stream_grid(ctx, total), TPB, 0, ctx->stream>>>(
+        (const float4 *)xq, (float4 *)yq, (const float4 *)resq, (unsigned)total, p, FastDiv(W * fw), FastDiv(H * fh));
+    PL_LAUNCH_CHECK();
+    return PL_OK;
+}
+
+// The channel-quad twin of pl_resize_linear_f32: same device position tables (ra, rs: OH entries; ca, cs: OW entries).
+int pl_resize_linear_q4_f32(pl_ctx *ctx, const float *xq, float *yq, const float *resq, int N, int C, int H, int W, int OH,
+                            int OW, const int *ra, const float *rs, const int *ca, const float *cs) {
+    PL_REQUIRE(ctx && xq && yq && ra && rs && ca && cs, PL_EINVAL, "pl_resize_linear_q4_f32: null argument");
+    PL_REQUIRE(N >= 0 && C > 0 && H > 1 && W > 1 && OH > 0 && OW > 0, PL_EINVAL,
+               "pl_resize_linear_q4_f32: bad shape (needs H, W >= 2)");
+    PL_REQUIRE(aligned16(xq) && aligned16(yq) && aligned16(resq), PL_EINVAL,
+               "pl_resize_linear_q4_f32: Q4 tensors must be 16-byte aligned");
+    PL_REQUIRE(xq != yq, PL_EINVAL, "pl_resize_linear_q4_f32: cannot run in place");
+    const size_t total = (size_t)N * ((C + 3) / 4) * OH * OW;
+    if (!total) return PL_OK;
+    PL_REQUIRE(total < (1ull << 30) && (size_t)N * ((C + 3) / 4) * H * W < (1ull << 30), PL_EUNSUPPORTED, "resize: tensor too large");
+    CtxGuard g(ctx);
+    resize_linear_q4_kernel<<<stream_grid(ctx, total), TPB, 0, ctx->stream>>>(
+        (const float4 *)xq, (float4 *)yq, (const float4 *)resq, (unsigned)total, H, W, ra, rs, ca, cs, FastDiv(OW), FastDiv(OH));
     PL_LAUNCH_CHECK();
     return PL_OK;
 }

@@ -30,7 +30,7 @@ from . import q4 as _q4
 from .conv_layouts import (CONV_KINDS, CONVT_KINDS, DIRECT_Q4, IGEMM_NCHW, LAYOUTS, ROWPACK_Q4, STEM_POOL, STEM_POOL_NCHW, WINO4_Q4,
                            WINO43_Q4, choose, suffix)
 from .layer import layer_map, wrap
-from .plan import (assign_layouts, chain_winograd, fold_dilated, fuse_conv1x1_wino_in, fuse_flow, fuse_instnorm_q4,
+from .plan import (assign_layouts, chain_winograd, fold_dilated, fuse_conv1x1_wino_in, fuse_flow, fuse_instnorm_q4, fuse_linear_add,
                    pair_sibling_convs)
 
 _q4.register(layer_map)
@@ -345,6 +345,7 @@ class Net:
         self.conv_pairs = 0          # sibling conv pairs the last plan runs as one launch
         self.conv_wino_fused = 0     # 1x1 convs the last plan runs inside the next conv's Winograd input transform
         self.instnorm_fused = 0      # add / relu steps the last plan runs inside a channel-quad instance norm
+        self.linear_adds_fused = 0   # add steps the last plan runs inside a channel-quad linear upsample / resize
         # force_algo: w_layout (int) every eligible 3x3/s1/p1 conv must use, or None = pick by timing
         fa = os.environ.get("PLANER_HIP_CONV_ALGO")
         self.force_algo = int(fa) if fa else None
@@ -519,6 +520,8 @@ class Net:
                                            values=lambda key: wmap[key].host if key in wmap else None)
             # instancenormalization_q4 -> [add_q4] -> [relu_q4] as one step: the tail goes into the norm's write pass
             body, flow, self.instnorm_fused = fuse_instnorm_q4(body, flow, shapes)
+            # linear upsample_q4 / resize_q4 -> add_q4 as one step: the add goes into the upsample's write pass
+            body, flow, self.linear_adds_fused = fuse_linear_add(body, flow, shapes)
             if self.fold_dilated:
                 worth = (lambda xs, ks, para: True) if self.fold_dilated == "force" else self._fold_worth
                 body, flow, regions = fold_dilated(body, flow, shapes, worth)

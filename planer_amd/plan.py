@@ -16,6 +16,7 @@ chain was, so a residual operand produced after the conv is still available.
 import os
 
 from .conv_layouts import DIRECT_Q4, STAGED_LAYOUTS, convt_phase_eligible, dw_q4_eligible, q4_conv_eligible
+from .layer import _nearest_shift
 
 ACT_NONE, ACT_RELU, ACT_LEAKY = 0, 1, 2
 ACT_RES_AFTER = 16      # OR-ed into `act`: the residual is added after the activation
@@ -130,7 +131,7 @@ def fuse_flow(layers, flow, init_names, shapes):
 # downstream of a conv -- and everything else reads NCHW, with a conversion step inserted where a
 # value is needed in the layout it was not produced in (converted copies are cached per value).
 Q4_POINTWISE = ("maxpool", "averagepool", "gap", "upsample", "batchnorm", "relu", "leakyrelu", "sigmoid",
-                "add", "concat", "clip", "instancenormalization", "pad")
+                "add", "concat", "clip", "instancenormalization", "pad", "resize")
 # the kinds of instance-normalised generators (fast-neural-style, CycleGAN ...): PLANER_HIP_INSTNORM_Q4=0 takes them out again,
 # which gives the program of a compiler without them
 INSTNORM_Q4_KINDS = ("instancenormalization", "pad")
@@ -138,11 +139,24 @@ PAD_MODES = ("constant", "wrap", "edge", "reflect", "symmetric")
 TO_Q4, FROM_Q4 = "@to_q4", "@from_q4"
 
 
+# bilinear interpolation between convs (FPN top-down paths, segmentation decoders): PLANER_HIP_LINEAR_Q4=0 takes linear
+# `upsample` and the WHOLE of `resize` out again -- nearest `resize` too, although the switch is named after the linear kernels:
+# no `resize` ran in Q4 before them, and the switch's contract is the program of a compiler without this change
+LINEAR_Q4_KINDS = ("resize",)
+
+
+def linear_q4_enabled():
+    return os.environ.get("PLANER_HIP_LINEAR_Q4", "1") != "0"
+
+
 def q4_pointwise_kinds():
     """Q4_POINTWISE as the environment leaves it."""
+    kinds = Q4_POINTWISE
     if os.environ.get("PLANER_HIP_INSTNORM_Q4", "1") == "0":
-        return tuple(k for k in Q4_POINTWISE if k not in INSTNORM_Q4_KINDS)
-    return Q4_POINTWISE
+        kinds = tuple(k for k in kinds if k not in INSTNORM_Q4_KINDS)
+    if not linear_q4_enabled():
+        kinds = tuple(k for k in kinds if k not in LINEAR_Q4_KINDS)
+    return kinds
 
 
 def _is4d(shapes, key):
@@ -174,6 +188,44 @@ def pad_q4_ok(c, pads, constant_value=0, mode="constant", **_):
     return mode != "constant" or c % 4 == 0 or float(constant_value) == 0.0
 
 
+def _linear_factors_ok(fh, fw, h, w):
+    """The geometries the linear channel-quad kernels take (q4._upsample_linear_q4): integer factors other than 1 x 1 with at
+    most 64 weights, or fractional ones on a map of at least 2 x 2 pixels."""
+    if fh == int(fh) and fw == int(fw):
+        return fh >= 1 and fw >= 1 and 1 < int(fh) * int(fw) <= 64
+    return h >= 2 and w >= 2 and int(round(fh * h)) >= 1 and int(round(fw * w)) >= 1
+
+
+def resize_factors(srcs, shape, values):
+    """(fh, fw) of a resize step as layer.Resize reads them -- scales, or sizes over the input's -- or None where they are not
+    constants whose numbers are known."""
+    if values is None or len(srcs) < 3:
+        return None
+    kv = values(srcs[2])
+    if kv is None:
+        return None
+    kv = kv.reshape(-1)
+    if kv.size == 0:
+        sz = values(srcs[3]) if len(srcs) > 3 else None
+        if sz is None or sz.reshape(-1).size < 2 or not shape[2] or not shape[3]:
+            return None
+        sz = sz.reshape(-1)
+        return float(sz[-2]) / shape[2], float(sz[-1]) / shape[3]
+    return (float(kv[-2]), float(kv[-1])) if kv.size >= 2 else None
+
+
+def resize_nearest_q4_ok(fh, fw, trans_mode="half_pixel", round_mode="round_prefer_floor"):
+    """A nearest `resize` by (fh, fw), truncated as layer.Resize truncates them, has a channel-quad form: up-scaling, and a
+    (transform, rounding) pair that does not shift the replicated map (layer._nearest_shift is 0 on both axes)."""
+    fh, fw = int(fh), int(fw)
+    return fh >= 1 and fw >= 1 and _nearest_shift(fh, trans_mode, round_mode) == 0 and _nearest_shift(fw, trans_mode, round_mode) == 0
+
+
+def is_linear(kind, para):
+    """A step that interpolates linearly: `upsample` / `resize` (or their channel-quad kinds) with mode "linear"."""
+    return kind.split("_")[0] in ("upsample", "resize") and para.get("mode", "nearest") == "linear"
+
+
 def _q4_pointwise_ok(kind, srcs, para, inits, shapes, values=None):
     acts = [k for k in srcs if k != "None" and k not in inits]
     if not acts or not all(_is4d(shapes, k) for k in acts):
@@ -201,7 +253,29 @@ def _q4_pointwise_ok(kind, srcs, para, inits, shapes, values=None):
     if kind == "batchnorm":
         return len(srcs) == 3 and srcs[1] in inits and srcs[2] in inits
     if kind == "upsample":
-        return len(srcs) == 2 and srcs[1] in inits and para.get("mode", "nearest") == "nearest"
+        if len(srcs) != 2 or srcs[1] not in inits:
+            return False
+        if para.get("mode", "nearest") == "nearest":
+            return True
+        if para.get("mode") != "linear" or not linear_q4_enabled() or values is None or values(srcs[1]) is None:
+            return False
+        kv = values(srcs[1]).reshape(-1)
+        if kv.size < 2:
+            return False
+        n, _, h, w = shapes[srcs[0]]
+        return _linear_factors_ok(int(kv[-2]), int(kv[-1]), h, w)          # truncated, layer.py:82
+    if kind == "resize":                  # constant scales / sizes: their numbers decide
+        if acts != [srcs[0]] or any(k != "None" and k not in inits for k in srcs[1:]):
+            return False
+        f = resize_factors(srcs, shapes[srcs[0]], values)
+        if f is None:
+            return False
+        n, _, h, w = shapes[srcs[0]]
+        if para.get("mode", "nearest") == "linear":
+            return _linear_factors_ok(f[0], f[1], h, w)
+        return (para.get("mode", "nearest") == "nearest" and int(f[0]) * int(f[1]) != 1
+                and resize_nearest_q4_ok(f[0], f[1], para.get("coordinate_transformation_mode", "half_pixel"),
+                                         para.get("nearest_mode", "round_prefer_floor")))
     return len(acts) == 1
 
 
@@ -265,6 +339,11 @@ def assign_layouts(body, flow, init_names, shapes, force=False, values=None):
 
     last = len(steps) - 1
     pointwise = q4_pointwise_kinds()
+
+    def ends_program(i, dst):
+        """Step i is the program's last, or what it writes is handed out by the closing `return`."""
+        return i == last or (kinds[steps[last][1]][0] == "return" and dst in steps[last][0]
+                             and not any(dst in s_ for s_, _, _ in steps[i + 1:last]))
     for i, (srcs, name, dst) in enumerate(steps):
         kind, para = kinds[name]
         single = isinstance(dst, str)
@@ -301,7 +380,9 @@ def assign_layouts(body, flow, init_names, shapes, force=False, values=None):
                 if shapes.get(k) is not None:
                     est["gain"] += _nbytes(shapes[k]) * _CONVERT_S_PER_BYTE
         elif kind in pointwise and single and _q4_pointwise_ok(kind, srcs, para, inits, shapes, values) \
-                and any(k in q4 for k in srcs):
+                and any(k in q4 for k in srcs) and not (is_linear(kind, para) and ends_program(i, dst)):
+            # (a linear upsample that ends the program stays NCHW behind a from_q4 of its small input: the result has to be NCHW
+            # anyway, and converting the large tensor costs more than converting the small one)
             as_q4 = True
             args = [need(k, True) for k in srcs]
             new_kind = kind + "_q4"
@@ -416,6 +497,70 @@ def fuse_instnorm_q4(body, flow, shapes):
     return out_body, [[srcs, [name], dst] for srcs, name, kind, para, dst in out], nfused
 
 
+# ---- linear upsample + add ---------------------------------------------------------------------------
+LINEAR_ADD_KINDS = {"upsample_q4": "upsample_add_q4", "resize_q4": "resize_add_q4"}
+
+
+def fuse_linear_add(body, flow, shapes):
+    """-> (body', flow', number of absorbed adds).  Runs on assign_layouts' program (one layer per step).  A linear `upsample_q4`
+    / `resize_q4` whose result has one reader and one writer, that reader an `add_q4` of two equal known shapes, becomes ONE
+    `upsample_add_q4` / `resize_add_q4` step (q4.UpSampleAddQ4 / ResizeAddQ4: the add's other operand, in either position, goes
+    into the kernel's write pass as a rounding of its own).  The fused step sits where the add was, so the upsample now reads its
+    source there: not fused where a step between the two rewrites that source in place (`_IN_PLACE`) or writes it, or writes the
+    other operand.  fuse_flow has already put an add behind a conv into that conv's epilogue; this takes what is left -- the
+    second and later terms of a sum of upsampled maps."""
+    kinds = {b[0]: b for b in body}
+    steps = [[list(src) if isinstance(src, (list, tuple)) else [src], names[0] if isinstance(names, (list, tuple)) else names, dst]
+             for src, names, dst in flow]
+    readers, writers = {}, {}
+    for i, (srcs, name, dst) in enumerate(steps):
+        for k in set(srcs):
+            readers.setdefault(k, []).append(i)
+        for k in _as_list(dst):
+            writers[k] = writers.get(k, 0) + 1
+
+    def shape(key):
+        s = shapes.get(key.split("@")[0])
+        return None if s is None else tuple(s)
+
+    consumed, fused_at = set(), {}
+    for i, (srcs, name, dst) in enumerate(steps):
+        _, kind, para = kinds[name]
+        if kind not in LINEAR_ADD_KINDS or not is_linear(kind, para) or not isinstance(dst, str):
+            continue
+        r = readers.get(dst, [])
+        if len(r) != 1 or writers.get(dst, 0) != 1 or r[0] <= i or r[0] in consumed:
+            continue
+        j = r[0]
+        jsrcs, jname, jdst = steps[j]
+        if (kinds[jname][1] != "add_q4" or not isinstance(jdst, str) or len(jsrcs) != 2 or jsrcs.count(dst) != 1
+                or shape(jsrcs[0]) is None or shape(jsrcs[0]) != shape(jsrcs[1])):
+            continue
+        res = jsrcs[1 - jsrcs.index(dst)]
+        between = range(i + 1, j)
+        if any((srcs[0] in steps[t][0] and kinds[steps[t][1]][1] in _IN_PLACE) or srcs[0] in _as_list(steps[t][2])
+               or res in _as_list(steps[t][2]) for t in between):
+            continue
+        if kind == "upsample_q4":
+            args = [srcs[0], srcs[1], res]
+        else:
+            args = (srcs + ["None"] * 4)[:4] + [res]
+        consumed.update((i, j))
+        fused_at[j] = (args, name + "+", LINEAR_ADD_KINDS[kind], para, jdst)
+    out = []
+    for i, (srcs, name, dst) in enumerate(steps):
+        if i in fused_at:
+            out.append(fused_at[i])
+        elif i not in consumed:
+            out.append((srcs, name, kinds[name][1], kinds[name][2], dst))
+    out_body, seen = [], set()
+    for srcs, name, kind, para, dst in out:
+        if name not in seen:
+            seen.add(name)
+            out_body.append([name, kind, para])
+    return out_body, [[srcs, [name], dst] for srcs, name, kind, para, dst in out], len(fused_at)
+
+
 # ---- Winograd chaining ------------------------------------------------------------------------------
 # A conv_q4 step that runs F(4x4,3x3) (w_layout 7) is three kernels: input transform (x -> V), the 36
 # grouped GEMMs (V, U -> M) and output transform + fused tail (M -> y).  When the y of one such conv
@@ -426,7 +571,7 @@ def fuse_instnorm_q4(body, flow, shapes):
 _PURE_READERS = ("conv_q4", "convt_q4", "wino4_in", "wino4_gemm", "wino4_out", "wino4_chain", "wino43_in", "wino43_gemm", "wino43_out",
                  "wino43_chain", "conv1x1_wino_in", "conv_q4_pair", "add_q4", "maxpool_q4",
                  "averagepool_q4", "gap_q4", "upsample_q4", "concat_q4", "upconcat_q4", "batchnorm_q4",
-                 "leakyrelu_q4", "sigmoid_q4", "from_q4", "pad_q4", "refold_q4")
+                 "leakyrelu_q4", "sigmoid_q4", "from_q4", "pad_q4", "refold_q4", "resize_q4", "upsample_add_q4", "resize_add_q4")
 
 
 def chain_winograd(body, flow, supported=lambda key: True, chain=True):

@@ -23,9 +23,10 @@ from .conv_layouts import (dw_q4_eligible, prepare_dw_q4_weights, prepare_q4_wei
                            prepare_winograd43_q4_weights, prepare_winograd_q4_weights, q4_conv_eligible, rowpack_eligible,
                            stem_pool_eligible, stem_pool_nchw_eligible, w1d_q4_eligible, winograd43_eligible, winograd_q4_eligible)
 from .conv_layouts import convt_phase_eligible as convt_q4_eligible, prepare_convt_weights as prepare_convt_q4_weights
-from .hip import DeviceArray, _f32, empty
-from .layer import ACT_NONE, _PAD_MODES, _contig_strides, _full, _host_values, _ptr, _strided_map, conv_out_hw, convt_out_hw, convt_q4_call
-from .plan import ACT_RELU, pad_q4_ok
+from .hip import DeviceArray, _f32, asarray, empty
+from .layer import (ACT_NONE, _PAD_MODES, _contig_strides, _full, _host_values, _linear_positions, _linear_weights,
+                    _ptr, _strided_map, conv_out_hw, convt_out_hw, convt_q4_call)
+from .plan import ACT_RELU, pad_q4_ok, resize_nearest_q4_ok
 
 
 def is_q4(a):
@@ -473,19 +474,113 @@ def GlobalAveragePoolQ4(xq):
     return y
 
 
-def UpSampleQ4(xq, k, mode="nearest"):
-    """layer.UpSample (layer.py:80-82) on a Q4 tensor."""
-    _f32(xq)
-    if mode != "nearest":
-        raise NotImplementedError("upsample mode %r is not on the HIP path" % mode)
-    kv = _host_values(k)
-    if kv.size == 0:
-        raise ValueError("upsample needs scales (the reference's size-only branch is broken, layer.py:81)")
-    fh, fw = [int(v) for v in kv[-2:].astype(int).tolist()]
+def _linear_tables(ctx, h, w, oh, ow):
+    """The device position tables of layer._linear_positions for one geometry, uploaded once and kept with the context: a
+    captured plan or a plan file then reads them as constants (an upload cannot be captured).  This differs from the NCHW
+    layer._upsample_linear on purpose: that one uploads on every call and so cannot run inside a captured plan at all.  Four
+    small arrays (OH + OW entries each) per geometry a context has seen, never evicted -- a net has a handful.  A table made
+    before Context.pool_debug was switched on is an ordinary block: a hygiene check that wants the table reads under guard
+    drops the cache first (`ctx.__dict__.pop("_linear_q4_tables", None)`, as tests/test_gpu_linear_q4.py does)."""
+    cache = ctx.__dict__.setdefault("_linear_q4_tables", {})
+    t = cache.get((h, w, oh, ow))
+    if t is None:
+        t = cache[(h, w, oh, ow)] = [asarray(a, ctx=ctx) for a in _linear_positions(h, oh) + _linear_positions(w, ow)]
+    return t
+
+
+def _check_res(resq, y):
+    if resq is not None and (not is_q4(resq) or resq.shape != y.shape or resq.chan != y.chan):
+        raise ValueError("fused residual %s != upsample output %s" % (getattr(resq, "shape", None), y.shape))
+
+
+def _upsample_linear_q4(xq, fh, fw, resq=None):
+    """layer._upsample_linear on a Q4 tensor: integer factors -> pl_upsample_linear_q4_f32, anything else ->
+    pl_resize_linear_q4_f32 at round(k * size); `resq` is added in the kernel's write pass."""
+    n, c, h, w = logical_shape(xq)
+    if fh == int(fh) and fw == int(fw):
+        fh, fw = int(fh), int(fw)
+        if fh == 1 and fw == 1:
+            return xq if resq is None else AddQ4(xq, resq)
+        y = _new_q4(n, c, h * fh, w * fw, xq.ctx)
+        _check_res(resq, y)
+        if fh * fw > 64:
+            raise NotImplementedError("linear upsample: fh * fw <= 64 on the HIP path, got %d x %d" % (fh, fw))
+        tab = _linear_weights(fh, fw)
+        _lib.call("pl_upsample_linear_q4_f32", xq.ctx.handle, xq.ptr, y.ptr, _ptr(resq), n, c, h, w, fh, fw,
+                  (_lib.c_float * tab.size)(*tab.reshape(-1).tolist()))
+        return y
+    oh, ow = int(round(fh * h)), int(round(fw * w))
+    if h < 2 or w < 2:
+        raise ValueError("linear resize needs at least 2 x 2 pixels (the reference indexes row / column + 1)")
+    y = _new_q4(n, c, oh, ow, xq.ctx)
+    _check_res(resq, y)
+    if y.size:
+        dev = _linear_tables(xq.ctx, h, w, oh, ow)
+        _lib.call("pl_resize_linear_q4_f32", xq.ctx.handle, xq.ptr, y.ptr, _ptr(resq), n, c, h, w, oh, ow, *[d.ptr for d in dev])
+    return y
+
+
+def _upsample_nearest_q4(xq, fh, fw):
     n, c, h, w = logical_shape(xq)
     y = _new_q4(n, c, h * fh, w * fw, xq.ctx)
     _lib.call("pl_upsample_nearest_q4_f32", xq.ctx.handle, xq.ptr, y.ptr, n, c, h, w, fh, fw)
     return y
+
+
+def UpSampleQ4(xq, k, mode="nearest", resq=None):
+    """layer.UpSample (layer.py:80-82) on a Q4 tensor.  `resq` (linear only): a Q4 tensor of the output's shape added on the
+    way out -- what plan.fuse_linear_add folds an add_q4 behind the upsample into."""
+    _f32(xq, resq)
+    if not is_q4(xq):
+        raise TypeError("UpSampleQ4 needs a Q4 activation (planer_amd.q4.to_q4)")
+    if mode not in ("nearest", "linear"):
+        raise NotImplementedError("upsample mode %r is not on the HIP path" % mode)
+    kv = _host_values(k)
+    if kv.size == 0:
+        raise ValueError("upsample needs scales (the reference's size-only branch is broken, layer.py:81)")
+    fh, fw = [int(v) for v in kv[-2:].astype(int).tolist()]       # truncated, layer.py:82
+    if mode == "linear":
+        return _upsample_linear_q4(xq, fh, fw, resq)
+    if resq is not None:
+        raise ValueError("UpSampleQ4: a fused residual goes with mode 'linear' only")
+    return _upsample_nearest_q4(xq, fh, fw)
+
+
+def ResizeQ4(xq, roi, k, size=None, mode="nearest", coordinate_transformation_mode="half_pixel",
+             nearest_mode="round_prefer_floor", resq=None):
+    """layer.Resize (layer.py:84-88) on a Q4 tensor: scales or sizes; linear as in UpSampleQ4 (the mode names are ignored, as
+    the reference ignores them), nearest for the pairs whose shift is zero.  The shifted nearest pairs have no Q4 form."""
+    _f32(xq, resq)
+    if not is_q4(xq):
+        raise TypeError("ResizeQ4 needs a Q4 activation (planer_amd.q4.to_q4)")
+    if mode not in ("nearest", "linear"):
+        raise NotImplementedError("resize mode %r is not on the HIP path" % mode)
+    kv = _host_values(k)
+    if kv.size == 0:
+        sz = _host_values(size)
+        kv = sz[-2:] / numpy.array(logical_shape(xq)[-2:])
+    fh, fw = [float(v) for v in kv[-2:].tolist()]
+    if mode == "linear":
+        return _upsample_linear_q4(xq, fh, fw, resq)
+    if resq is not None:
+        raise ValueError("ResizeQ4: a fused residual goes with mode 'linear' only")
+    fh, fw = int(fh), int(fw)                      # util.py:213
+    if fh < 1 or fw < 1:
+        raise NotImplementedError("resize: nearest down-scaling (the reference returns an empty map) is not on the HIP path")
+    if not resize_nearest_q4_ok(fh, fw, coordinate_transformation_mode, nearest_mode):
+        raise NotImplementedError("ResizeQ4: nearest up-scaling with (%s, %s) shifts the map; that has no channel-quad form"
+                                  % (coordinate_transformation_mode, nearest_mode))
+    return _upsample_nearest_q4(xq, fh, fw)
+
+
+def UpSampleAddQ4(xq, k, resq, **para):
+    """UpSampleQ4(mode="linear") + AddQ4 in one kernel: the plan step `upsample_add_q4` (plan.fuse_linear_add)."""
+    return UpSampleQ4(xq, k, resq=resq, **para)
+
+
+def ResizeAddQ4(xq, roi, k, size, resq, **para):
+    """ResizeQ4(mode="linear") + AddQ4 in one kernel: the plan step `resize_add_q4`; `size` may be None."""
+    return ResizeQ4(xq, roi, k, size, resq=resq, **para)
 
 
 def BatchNormQ4(xq, K, B):
@@ -628,7 +723,7 @@ def UpConcatQ4(aq, k, bq, mode="nearest", axis=1):
 Q4_LAYERS = {"maxpool": MaxpoolQ4, "averagepool": AveragePoolQ4, "gap": GlobalAveragePoolQ4,
              "upsample": UpSampleQ4, "batchnorm": BatchNormQ4, "relu": ReLUQ4, "leakyrelu": LeakyReLUQ4,
              "sigmoid": SigmoidQ4, "add": AddQ4, "concat": ConcatenateQ4, "clip": ClipQ4,
-             "instancenormalization": InstanceNormQ4, "pad": PadQ4}
+             "instancenormalization": InstanceNormQ4, "pad": PadQ4, "resize": ResizeQ4}
 
 
 def register(layer_map):
@@ -636,5 +731,6 @@ def register(layer_map):
     layer_map.update({"to_q4": to_q4, "from_q4": from_q4, "refold_q4": refold_q4, "conv_q4": ConvQ4, "convt_q4": ConvTransposeQ4, "upconcat_q4": UpConcatQ4,
                       "wino4_in": Wino4In, "wino4_gemm": Wino4Gemm, "wino4_out": Wino4Out, "wino4_chain": Wino4Chain,
                       "conv_q4_pair": ConvQ4Pair, "conv_pool_q4": ConvPoolQ4, "conv1x1_wino_in": Conv1x1WinoIn,
+                      "upsample_add_q4": UpSampleAddQ4, "resize_add_q4": ResizeAddQ4,
                       "wino43_in": Wino43In, "wino43_gemm": Wino43Gemm, "wino43_out": Wino43Out, "wino43_chain": Wino43Chain})
     layer_map.update({k + "_q4": f for k, f in Q4_LAYERS.items()})
