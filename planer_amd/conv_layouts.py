@@ -75,7 +75,7 @@ prepare_winograd4_q4_weights = _packer("winograd4_q4", _cout_cin, _wino_check)
 # OIHW 3x3 -> fused 1-D Winograd F(4,3) filters [6][row*Cin/4 + cin/4][Cout][4]
 prepare_w1d4_q4_weights = _packer("w1d4_q4", _cout_cin, _refuse(lambda co, ci, kh, kw: (kh, kw) == (3, 3) and ci % 4 == 0,
                                                                 "1-D winograd filters need 3x3 kernels and Cin % 4 == 0"))
-# OIHW 3x3 -> fully fused F(4x4,3x3) filters [Cout/64][Cin/4][36][4][4][16]
+# OIHW 3x3 -> fully fused F(4x4,3x3) filters [Cout/64][Cin/4][4 blocks of 16 channels][9 groups of 4 frequencies][4 k x 16 channels][4]
 prepare_wf4_q4_weights = _packer("wf4", _cout_cin, _wino_check)
 # OIHW 3x3 -> mixed-tile Winograd filters [121][k-quad][Cout][4]
 prepare_winograd43_q4_weights = _packer("winograd43_q4", _cout_cin, _wino_check)

@@ -5,55 +5,59 @@
 // 93-95, 44-51).  The staged pipeline (input transform -> 36 grouped GEMMs -> output transform) needs 4x fewer
 // multiplies than the direct conv but moves V and M -- 2.25x the activation each, written and read -- through
 // memory; the fused 1-D kernel (conv_w1d4_kernel) moves nothing extra but only halves the multiplies.  Here ONE
-// workgroup carries a block of 32 tiles x 64 output channels through all 36 frequencies:
-//   * 8 waves, two per SIMD, 256 registers each (amdgpu_waves_per_eu(2,2)).  Wave (wm, wn) owns output channels
-//     [16 wm, 16 wm + 16) x tiles [16 wn, 16 wn + 16) as 36 accumulator blocks of v_mfma_f32_16x16x4_f32 (144 registers):
-//     lane (i = lane % 16, rg = lane / 16) ends up holding, for ITS tile i and ITS channel quad 4 rg .. 4 rg + 3, all 36
-//     frequencies -- so the output transform A^T m A is lane-local; the fused tail and the stores go through a wave-private
-//     LDS exchange that turns (tile, quad) lanes into (tile, pixel) lanes: one store covers a contiguous 1 KB run.  M never
-//     exists.  (The first version had 4 waves x 288 accumulators: 67 us against 48 us -- the compiler shuffled through AGPRs.)
-//   * Round 6, what ships: BLOCKS OF 16 TILES ON FOUR WAVES (template parameter HALF; PLANER_HIP_EXPERIMENT=wf4_half=0 brings the
-//     32-tile / eight-wave block described below back).  A workgroup then holds half the registers of a CU and 34.8 KB of LDS,
-//     so two of them -- or one and another kernel's workgroups -- share a CU with barriers of their own: one's prologue, store
-//     tail and barrier waits run under the other's K loop.  Wave wm owns output channels [16 wm, 16 wm + 16) x the 16 tiles; the
-//     patch transform of a step is three TWO-ROW wave-items (wf4_transform_2rows: lane = row of a pair x tile x channel pair) on
-//     waves 1-3.  Layer2 conv of ResNet-18 at batch 32: 43.7 against 62.1 us alone (224 instead of 112 workgroups), bench.py
-//     58.1-58.4 k against 55.9-56.2 k img/s (profiles/r06_ab_wf4_half_blocks.txt).
-//   * The 16-tile block's K step is WOVEN (template parameter WEAVE; PLANER_HIP_EXPERIMENT=wf4_weave=0 brings the phased step
-//     back): no transform phase in front of the MFMAs -- every wave carries a two-row item of chunk c + 1 in pieces behind single
-//     MFMAs of chunk c (mma_weave: reads, first stage column by column, second stage, V writes; scheduling barriers pin the
-//     pieces).  One branch-free instruction stream for all four waves: an item's kind is per-wave DATA (row bases,
-//     coefficients; the three-row kind reads its fourth row out of 1 KB of -0.0 behind the patch buffer), wave 0 repeats wave 1's
-//     item.  Bit-identical to the phased step (tests/test_gpu_wf4_weave.py); 256 registers, no scratch in the K loop, 36.9 KB of
-//     LDS.  Per conv alone / per 32 images at batch 256: layer1 37.0 / 30.3 against 38.7 / 31.9 us, layer2 41.1 / 26.7 against
-//     44.0 / 27.6 us (profiles/wf4_weave.md).
-//   * The filter never touches LDS (round 6, WF4_GLOBAL_A): it is laid out [cout block][chunk][16-channel block][group of 4
-//     frequencies][lane][4], so the fragment a wave needs for one group of four MFMAs is ONE 16-byte load per lane over a
-//     contiguous 1 KB, requested five groups ahead into a ring of six register slots (profiles/r06_wf4_stalls.md: 39.2 / 60.2
-//     against 40.3 / 62.6 us per layer1 / layer2 conv, 110 KB less LDS traffic per K step, 69.6 instead of 143 KB of LDS).
-//     (WF4_GLOBAL_A = 0, the form of rounds 3-5: the filter slice A[4 cout blocks][4 k][16][36] of a chunk, 36.9 KB, staged in
-//     LDS by LDS-DMA and read back as fragments -- what the next item still describes.)
-//   * K runs over input channel quads (one quad = one chunk = one MFMA K step of 4).  Per chunk the workgroup
-//     holds in LDS: the filter slice A[4 cout blocks][4 k][16][36] (36.9 KB, by LDS-DMA straight from a filter laid out in
-//     exactly that order), the input patch P of the block's tiles -- (4 BR + 2) x (4 BC + 2) pixels per image,
-//     halo shared between neighbouring tiles, stored [row][x mod 4][x div 4] as 16-byte cells (by LDS-DMA, zero fill by the
-//     range check) -- and the transformed patch V[2 wn][4 k][16 tiles][36] (18.4 KB) that six wave-items compute from P
-//     (one row of B^T d B for all 32 tiles x a channel pair per lane, packed arithmetic): V never leaves the CU.
-//   * One barrier per chunk.  In iteration c the waves request chunk c+1's filter slice and chunk c+2's patch (LDS-DMA,
-//     one request per MFMA group), waves 4-7 transform P[(c+1)&1] into V[(c+1)&1] BEFORE their 36 MFMAs of chunk c and waves
-//     0-1 after theirs (rows 4-5), so that the two waves of a SIMD alternate on its matrix pipe; every buffer written in an
-//     interval was last read in the previous one.
-//   * Fragment reads are conflict free by layout: a lane's 36 frequencies of one (k, row) are 144 consecutive bytes.
-//   * What a K step costs (profiles/r04_wf4_knockout.md): 1.00 us of MFMAs + 0.36 fragment reads + 0.38 transform + 0.13 both
-//     LDS-DMA streams = 1.61 us; fp32 MFMAs do not overlap with the other vector instructions of their SIMD.
+// workgroup carries a block of tiles x 64 output channels through all 36 frequencies:
+//   * A wave owns 16 output channels x 16 tiles as 36 accumulator blocks of v_mfma_f32_16x16x4_f32 (144 of its 256
+//     registers, amdgpu_waves_per_eu(2,2)): lane (i = lane % 16, rg = lane / 16) ends up holding, for ITS tile i and ITS channel
+//     quad 4 rg .. 4 rg + 3, all 36 frequencies -- so the output transform A^T m A is lane-local; the fused tail and the stores
+//     go through a wave-private LDS exchange that turns (tile, quad) lanes into (tile, pixel) lanes: one store covers a
+//     contiguous 1 KB run.  M never exists.  (The first version had 4 waves x 288 accumulators: 67 us against 48 us -- the
+//     compiler shuffled through AGPRs.)
+//   * What ships: BLOCKS OF 16 TILES ON FOUR WAVES (template parameter HALF).  Wave wm owns output channels [16 wm, 16 wm + 16)
+//     x the 16 tiles.  A workgroup holds half the registers of a CU, so two of them -- or one and another kernel's workgroups
+//     -- share a CU with barriers of their own: one's prologue, store tail and barrier waits run under the other's K loop.
+//     Layer2 conv of ResNet-18 at batch 32: 43.7 against 62.1 us alone (224 instead of 112 workgroups), bench.py 58.1-58.4 k
+//     against 55.9-56.2 k img/s (profiles/r06_ab_wf4_half_blocks.txt).
+//   * The oracle: BLOCKS OF 32 TILES ON EIGHT WAVES, two per SIMD (PLANER_HIP_EXPERIMENT=wf4_half=0).  Wave (wm, wn) = (wave / 2,
+//     wave % 2) owns channels [16 wm, 16 wm + 16) x tiles [16 wn, 16 wn + 16).  One workgroup owns the CU.
+//   * K runs over input channel quads (one quad = one chunk = one MFMA K step of 4), one barrier per chunk.  Per chunk the
+//     workgroup holds in LDS, double buffered: the input patch P of the block's tiles -- (4 BR + 2) x (4 BC + 2) pixels per
+//     image, halo shared between neighbouring tiles, stored [row][x mod 4][x div 4] as 16-byte cells (by LDS-DMA straight from
+//     the activation, zero fill by the range check; 512 cells = 8 KB for 16 tiles, 1024 = 16 KB for 32) -- and the transformed
+//     patch V[wn][4 k][16 tiles][36] (9.2 KB per 16 tiles) that wave-items compute from P (B^T d B, a channel pair per lane,
+//     packed arithmetic): V never leaves the CU.  LDS per workgroup: 34.8 KB with 16 tiles (36.9 KB woven, see below), 69.6 KB
+//     with 32.  In iteration c the waves request chunk c + 2's patch (one request behind each of the first MFMA groups) and
+//     transform P[(c+1)&1] into V[(c+1)&1]; every buffer written in an interval was last read in the previous one.
+//   * The filter never touches LDS: it is laid out [cout block][chunk][16-channel block][group of 4 frequencies][lane][4]
+//     (wf4_filter_kernel), so the fragment a wave needs for one group of four MFMAs is ONE 16-byte load per lane over a
+//     contiguous 1 KB, global -> registers, requested WF4_GA_AHEAD = five groups ahead into a ring of WF4_GA_SLOTS = six register
+//     slots (profiles/r06_wf4_stalls.md: 39.2 / 60.2 against 40.3 / 62.6 us per layer1 / layer2 conv with the slice staged in LDS,
+//     110 KB less LDS traffic per K step, 69.6 instead of 143 KB of LDS for the 32-tile block).
+//   * The 16-tile block's K step is WOVEN (template parameter WEAVE): no transform phase in front of the MFMAs -- every wave
+//     carries a two-row item of chunk c + 1 in pieces behind single MFMAs of chunk c (mma_weave: reads, first stage column by
+//     column, second stage, V writes; scheduling barriers pin the pieces).  One branch-free instruction stream for all four
+//     waves: an item's kind is per-wave DATA (row bases, coefficients; the three-row kind reads its fourth row out of 1 KB of
+//     -0.0 behind the patch buffer), wave 0 repeats wave 1's item.  256 registers, no scratch in the K loop.  Per conv alone /
+//     per 32 images at batch 256: layer1 37.0 / 30.3 against 38.7 / 31.9 us, layer2 41.1 / 26.7 against 44.0 / 27.6 us
+//     (profiles/wf4_weave.md).
+//   * The PHASED K step (mma_ga; PLANER_HIP_EXPERIMENT=wf4_weave=0, and the 32-tile block always): the transform is a phase of
+//     its own.  16 tiles: three TWO-ROW wave-items (wf4_transform_2rows: lane = row of a pair x tile x channel pair) on waves 1-3
+//     in front of their MFMAs.  32 tiles: six one-row items (wf4_transform_row2: lane = tile x channel pair) -- waves 4-7 rows
+//     0-3 BEFORE their 36 MFMAs of chunk c, waves 0-1 rows 4-5 after theirs, so that the two waves of a SIMD alternate on its
+//     matrix pipe.  The woven step is bit-identical to the phased one (tests/test_gpu_wf4_weave.py).
+//   * Fragment reads of V are conflict free by layout: a lane's 36 frequencies of one (k, tile) are 144 consecutive bytes.
+//   * What a K step of the 32-tile block with the filter in LDS cost (profiles/r04_wf4_knockout.md): 1.00 us of MFMAs + 0.36
+//     fragment reads + 0.38 transform + 0.13 both LDS-DMA streams = 1.61 us; fp32 MFMAs do not overlap with the other vector
+//     instructions of their SIMD.  The 16-tile form's table: profiles/wf4_weave.md.
 // Executed MFMA work = 36/16 of a GEMM per output pixel = 4x fewer multiplies than the direct conv (tile and
 // channel padding aside); HBM traffic = x + y (+ residual) + the filter.
+// Forms measured and dropped (filter slice staged in LDS, patch stored channel plane by channel plane, register-staged operands, every wave multiplying
+// first): DESIGN.md, the fused F(4x4,3x3) items, and profiles/r06_wf4_stalls.md.
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 struct Wf4Args {
     const float *x;        // [N][Cq][H][W][4]
-    const float *u;        // [cout block of 64][chunk = cin/4][36][4 blocks of 16][4 k][16]   (pl_conv2d_prepare_wf4_f32)
+    const float *u;        // [cout block of 64][chunk = cin/4][wm = 16-channel block][g = 4 frequencies][lane = 16 k + i][4]   (pl_conv2d_prepare_wf4_f32)
     float *y;              // [N][Coq][H][W][4]
     int N, Cq, Coq, H, W, th, tw;
     int nchunks;           // Cin / 4
@@ -70,21 +74,14 @@ struct Wf4Args {
     Epilogue ep;
 };
 
-// probe builds only (tools/wf4_knock.sh): bit 0 no filter LDS-DMA, 1 no patch LDS-DMA, 2 no patch transform, 3 no MFMAs,
-// 4 no fragment reads, 5 no output rows -- results are garbage, the time tells what a K step's parts cost.  Bits 2-4 act on
-// every form of the K step (filter in LDS, filter in registers, woven); bit 0 only where the filter is staged in LDS.
+// probe builds only (tools/wf4_knock.sh): bit 0 unused (it dropped the filter's LDS-DMA while the filter slice was staged in
+// LDS; the numbering stays so that profiles/r04_wf4_knockout.md reads as written), 1 no patch LDS-DMA, 2 no patch transform,
+// 3 no MFMAs, 4 no fragment reads, 5 no output rows -- results are garbage, the time tells what a K step's parts cost.  Bits 2-4
+// act on both forms of the K step (phased, woven).
 #ifndef WF4_KNOCK
 #define WF4_KNOCK 0
 #endif
-// 1: the filter fragments go global -> REGISTERS (16-byte loads that a wave issues as one contiguous 1 KB run, a rolling
-// prefetch WF4_GA_AHEAD MFMA groups deep) and never touch LDS; 0: the filter slice of a K step is staged in LDS by LDS-DMA and
-// read back as fragments (two readers per value).  The filter layout differs (pl_conv2d_prepare_wf4_f32 follows the same macro).
-#ifndef WF4_GLOBAL_A
-#define WF4_GLOBAL_A 1
-#endif
-#ifndef WF4_HALF_TRIM
-#define WF4_HALF_TRIM 1      // (probe builds: 0 keeps the 32-tile block's LDS allocation for the 16-tile block)
-#endif
+// the filter fragments' rolling prefetch: WF4_GA_AHEAD MFMA groups deep into a ring of WF4_GA_SLOTS register slots
 #ifndef WF4_GA_AHEAD
 #define WF4_GA_AHEAD 5
 #endif
@@ -112,63 +109,14 @@ __device__ unsigned long long wf4_step_stamps[512 * 8 * 2 * 8];
 #define WF4_MARK(i)
 #define WF4_STEP_MARK(c, i)
 #endif
-constexpr int WF4_A_FLOATS = 36 * 256, WF4_V_FLOATS = 2 * 36 * 64, WF4_P_PASSES = 2;      // patch passes of 512 cells
-constexpr int WF4_P_CELLS = 1024, WF4_P_FLOATS = WF4_P_CELLS * 4;
-constexpr int WF4_LDS_BYTES = (2 * WF4_A_FLOATS + 2 * WF4_V_FLOATS + 2 * WF4_P_FLOATS) * 4;
+constexpr int WF4_A_FLOATS = 36 * 256;                  // one (cout block, chunk) of the prepared filter: 64 channels x 4 k x 36 frequencies
+constexpr int WF4_V_FLOATS = 2 * 36 * 64, WF4_P_PASSES = 2;      // V of 32 tiles; patch passes of one cell per thread
+constexpr int WF4_P_CELLS = 1024, WF4_P_FLOATS = WF4_P_CELLS * 4;      // patch of 32 tiles (16 tiles: half of each)
 
-__device__ __forceinline__ void wf4_bt(const float (&d)[6], float (&o)[6]) {      // o = B^T d, with fused multiply-adds
-    const float s = d[4] - d[2], t = d[3] - d[1];
-    o[0] = __builtin_fmaf(4.f, d[0], __builtin_fmaf(-5.f, d[2], d[4]));
-    o[1] = __builtin_fmaf(-4.f, d[1] + d[2], d[3] + d[4]);
-    o[2] = __builtin_fmaf(4.f, d[1] - d[2], d[4] - d[3]);
-    o[3] = __builtin_fmaf(2.f, t, s);
-    o[4] = __builtin_fmaf(-2.f, t, s);
-    o[5] = __builtin_fmaf(4.f, d[1], __builtin_fmaf(-5.f, d[3], d[5]));
-}
-template <int A>
-__device__ __forceinline__ float wf4_bt_row(const float (&d)[6]) {
-    if constexpr (A == 0) return __builtin_fmaf(4.f, d[0], __builtin_fmaf(-5.f, d[2], d[4]));
-    else if constexpr (A == 1) return __builtin_fmaf(-4.f, d[1] + d[2], d[3] + d[4]);
-    else if constexpr (A == 2) return __builtin_fmaf(4.f, d[1] - d[2], d[4] - d[3]);
-    else if constexpr (A == 3) return __builtin_fmaf(2.f, d[3] - d[1], d[4] - d[2]);
-    else if constexpr (A == 4) return __builtin_fmaf(-2.f, d[3] - d[1], d[4] - d[2]);
-    else return __builtin_fmaf(4.f, d[1], __builtin_fmaf(-5.f, d[3], d[5]));
-}
-
-// one transform wave-item: row A of B^T d B for (tile, channel), lanes = 16 tiles x 4 channels (tile fastest): 6 columns x
-// (the rows of d with a non-zero coefficient) out of the channel-planar patch, 6 consecutive values into
-// V[half][ch][i][6 A .. 6 A + 5].  pbase: float index of the tile's first patch cell in its channel plane; vbase: float index
-// of V[half][ch][i][0]; rs = cells per patch row (4 S), ps = cells per x phase (S).
-template <int A, int rs, int ps, int cst>
-__device__ __forceinline__ void wf4_transform_row(const float *P, float *V, int pbase, int vbase) {
-    // all the patch values this row needs are requested before the first is used (the rows of d with a zero coefficient in
-    // row A of B^T are never read: the compiler drops those loads)
-    float d[6][6];
-#pragma unroll
-    for (int b = 0; b < 6; ++b) {
-        const float *col = P + pbase + (b & 3) * ps + (b >> 2) * cst;
-#pragma unroll
-        for (int k = 0; k < 6; ++k) {
-            constexpr bool used[6][6] = {{1, 0, 1, 0, 1, 0}, {0, 1, 1, 1, 1, 0}, {0, 1, 1, 1, 1, 0},
-                                         {0, 1, 1, 1, 1, 0}, {0, 1, 1, 1, 1, 0}, {0, 1, 0, 1, 0, 1}};
-            d[b][k] = used[A][k] ? col[k * rs] : 0.f;
-        }
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    float m[6];
-#pragma unroll
-    for (int b = 0; b < 6; ++b) m[b] = wf4_bt_row<A>(d[b]);
-    float o[6];
-    wf4_bt(m, o);
-    float2 *dst = reinterpret_cast<float2 *>(V + vbase + A * 6);       // vbase is a multiple of 36, 6 A is even: 8-byte aligned
-    dst[0] = make_float2(o[0], o[1]);
-    dst[1] = make_float2(o[2], o[3]);
-    dst[2] = make_float2(o[4], o[5]);
-}
-
-// The same row for TWO channels per lane (16-byte-cell patch layout): every value is a channel pair out of one 8-byte LDS read
-// and every operation a packed one -- half the vector instructions of the one-channel form and no operand shuffling.  Lanes =
-// 32 tiles x 2 channel pairs (pair fastest: consecutive lanes read consecutive 8 bytes).  Same formulas, same roundings.
+// One transform wave-item of the 32-tile block: row A of B^T d B for TWO channels per lane -- every value is a channel pair out
+// of one 8-byte LDS read and every operation a packed one, no operand shuffling.  Lanes = 32 tiles x 2 channel pairs (pair
+// fastest: consecutive lanes read consecutive 8 bytes).  All the patch values the row needs are requested before the first is
+// used; the rows of d with a zero coefficient in row A of B^T are never read (the compiler drops those loads).
 typedef float wf4_v2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ wf4_v2 wf4_fma2(float a, wf4_v2 b, wf4_v2 c) { return __builtin_elementwise_fma((wf4_v2){a, a}, b, c); }
 __device__ __forceinline__ void wf4_bt2(const wf4_v2 (&d)[6], wf4_v2 (&o)[6]) {
@@ -372,35 +320,21 @@ __device__ __forceinline__ void wf4_output_row_coalesced(const Wf4Args &p, const
     wf4_row_finish<RES, PLAIN>(p, slo, shi, cqc, scale, shift, xb, wr_cell, rd_cell, yrsrc, rrsrc, off);
 }
 
-// Variants (compile-time; the launcher picks one): DMA_A -- the filter slice goes global -> LDS by LDS-DMA instead of through
-// registers; PLANAR -- the patch is stored channel-planar (transform lanes = 16 tiles x 4 channels, tile fastest: conflict-free
-// patch reads AND 2-way instead of 4-way conflicts on the V writes) instead of as 16-byte cells (lanes channel fastest);
-// STAGGER -- waves 4-7 transform before their MFMAs and waves 0-3 after, so the two waves of a SIMD alternate on its matrix pipe.
-// HALF (round 6, needs WF4_GLOBAL_A): a workgroup of FOUR waves carries 16 tiles x 64 output channels -- half the registers and
-// a quarter of the LDS of a CU, so two workgroups share it with barriers of their own: one's prologue, tail and barrier waits
-// run under the other's K loop.  Three two-row transform items (waves 1-3) per K step.
-template <bool DMA_A, bool PLANAR, bool STAGGER, int LBC, bool PACK = false, bool HALF = false, bool WEAVE = false>
+// Variants (compile-time; the launcher picks one per block width, so that every patch read is base + immediate): PACK -- spare
+// slot columns carry a donor image's tiles (Wf4Args); HALF -- 16 tiles on four waves instead of 32 on eight; WEAVE -- the woven
+// K step instead of the phased one.
+template <int LBC, bool PACK = false, bool HALF = false, bool WEAVE = false>
 __device__ __forceinline__ void conv_wf4_body(const Wf4Args &p) {
     constexpr int NT = HALF ? 256 : 512, LT = HALF ? 4 : 5;          // threads, log2(tiles) of a block
-    static_assert(!WEAVE || (HALF && STAGGER), "woven K step: 16-tile blocks only");
-    static_assert(!HALF || (WF4_GLOBAL_A && DMA_A && !PLANAR), "half blocks: filter in registers, 16-byte-cell patch");
-    // the LDS-DMA requests of a step go out one per MFMA group (measured: 40.9 -> 39.8 us per layer1 conv against all seven
-    // in a row at the head of the step)
-    constexpr bool SPREAD = DMA_A && !PLANAR && STAGGER;
+    static_assert(!WEAVE || HALF, "woven K step: 16-tile blocks only");
     constexpr int S = (1 << LBC) + 1 + (PACK ? 1 : 0);      // 16-byte cells per x phase: compile time, so every patch read is base + immediate
-    static_assert(!PACK || !PLANAR, "packed blocks: 16-byte-cell patch layout only");
-    // six separate LDS objects (not one dynamic array): the compiler orders LDS-DMA against later LDS accesses object by
-    // object, so a DMA into A1 / P0 does not hold up the reads of A0 / P1 / V0 and the writes of V1
-#if WF4_GLOBAL_A
-    float *const As0 = nullptr, *const As1 = nullptr;          // (no filter slice in LDS: 73.7 KB fewer)
-#else
-    __shared__ __attribute__((aligned(16))) float As0[WF4_A_FLOATS], As1[WF4_A_FLOATS];      // [4 cb][4 k][16 i][36 f]
-#endif
+    // four separate LDS objects (not one dynamic array): the compiler orders LDS-DMA against later LDS accesses object by
+    // object, so a DMA into P0 does not hold up the reads of P1 / V0 and the writes of V1
     // (HALF: one tile half of V, 512 patch cells -- 34.8 KB a workgroup, so that what else runs on the CU keeps its LDS)
-    __shared__ __attribute__((aligned(16))) float Vs0[WF4_V_FLOATS / (HALF && WF4_HALF_TRIM ? 2 : 1)], Vs1[WF4_V_FLOATS / (HALF && WF4_HALF_TRIM ? 2 : 1)];      // [2 wn][4 k][16 i][36 f]
+    __shared__ __attribute__((aligned(16))) float Vs0[WF4_V_FLOATS / (HALF ? 2 : 1)], Vs1[WF4_V_FLOATS / (HALF ? 2 : 1)];      // [wn][4 k][16 i][36 f]
     // (WEAVE: 1 KB of -0.0 behind each patch buffer -- the "fourth patch row" of the waves whose item reads three, see wv_p3)
-    constexpr int P_TAIL = WEAVE ? 256 : 0, P_BODY = WF4_P_FLOATS / (HALF && WF4_HALF_TRIM ? 2 : 1);
-    __shared__ __attribute__((aligned(16))) float Ps0[P_BODY + P_TAIL], Ps1[P_BODY + P_TAIL];      // [cells][4]  or  [4 ch][cells]
+    constexpr int P_TAIL = WEAVE ? 256 : 0, P_BODY = WF4_P_FLOATS / (HALF ? 2 : 1);
+    __shared__ __attribute__((aligned(16))) float Ps0[P_BODY + P_TAIL], Ps1[P_BODY + P_TAIL];      // [cells][4]
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -460,62 +394,18 @@ __device__ __forceinline__ void conv_wf4_body(const Wf4Args &p) {
                 pvoff[ps] = (int)(((unsigned)(n * p.Cq) * (unsigned)HW + (unsigned)(h * p.W + w)) << 4);
         }
     }
-    float4 preg[WF4_P_PASSES], areg[5];
-    constexpr bool DMA_P = DMA_A && !PLANAR;            // 16-byte cells land lane-linear: LDS-DMA can write them directly
+    // 16-byte cells land lane-linear: LDS-DMA writes them directly
     auto load_p = [&](int c, int buf) {
         const int soff = (c * HW) << 4;
         float *Pb = buf ? Ps1 : Ps0;
 #pragma unroll
         for (int ps = 0; ps < WF4_P_PASSES; ++ps)
-            if (ps * NT < p.cells) {
-                if constexpr (DMA_P) {
-                    if (ps * NT + tid < p.cells)
-                        __builtin_amdgcn_raw_ptr_buffer_load_lds(xrsrc, (lds_float *)(Pb + (ps * NT + tid - lane) * 4), 16, pvoff[ps], soff, 0, 0);
-                } else {
-                    preg[ps] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(xrsrc, pvoff[ps], soff, 0));
-                }
-            }
+            if (ps * NT < p.cells && ps * NT + tid < p.cells)
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(xrsrc, (lds_float *)(Pb + (ps * NT + tid - lane) * 4), 16, pvoff[ps], soff, 0, 0);
     };
-    auto store_p = [&](int buf) {
-        if constexpr (DMA_P) return;
-        float *Pb = buf ? Ps1 : Ps0;
-#pragma unroll
-        for (int ps = 0; ps < WF4_P_PASSES; ++ps)
-            if (ps * NT < p.cells && ps * NT + tid < p.cells) {
-                if constexpr (PLANAR) {
-                    float *d = Pb + ps * NT + tid;
-                    d[0] = preg[ps].x;
-                    d[p.cells] = preg[ps].y;
-                    d[2 * p.cells] = preg[ps].z;
-                    d[3 * p.cells] = preg[ps].w;
-                } else {
-                    *reinterpret_cast<float4 *>(Pb + (ps * NT + tid) * 4) = preg[ps];
-                }
-            }
-    };
-    // filter slice: 2304 x 16 bytes = four passes of 512 threads and one of 256 (waves 0-3)
-    auto load_a = [&](int c, int buf) {
-        const int soff = (int)(((unsigned)coutblk * (unsigned)p.nchunks + (unsigned)c) * (unsigned)(WF4_A_FLOATS * 4));
-        float *Ab = buf ? As1 : As0;
-#pragma unroll
-        for (int it = 0; it < 5; ++it)
-            if (it < 4 || wave < 4) {
-                if constexpr (DMA_A)
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(ursrc, (lds_float *)(Ab + (it * 512 + tid - lane) * 4), 16, (it * 512 + tid) << 4, soff, 0, 0);
-                else
-                    areg[it] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(ursrc, (it * 512 + tid) << 4, soff, 0));
-            }
-    };
-    // one piece (1 KB per wave) of the next filter slice / of the patch after next: the K step issues them BETWEEN its MFMA
-    // groups, so that the ~100 issue cycles an LDS-DMA instruction costs a wave are spent while its SIMD partner's MFMAs
-    // keep the matrix pipe busy (all seven in a row before the first MFMA left the pipe idle at the head of every step)
-    auto load_a_piece = [&](int c, int buf, int it) {
-        const int soff = (int)(((unsigned)coutblk * (unsigned)p.nchunks + (unsigned)c) * (unsigned)(WF4_A_FLOATS * 4));
-        float *Ab = buf ? As1 : As0;
-        if constexpr (WF4_KNOCK & 1) return;
-        if (it < 4 || wave < 4)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(ursrc, (lds_float *)(Ab + (it * 512 + tid - lane) * 4), 16, (it * 512 + tid) << 4, soff, 0, 0);
-    };
+    // one piece (1 KB per wave) of the patch after next: the K step issues them BETWEEN its MFMA groups, so that the ~100 issue
+    // cycles an LDS-DMA instruction costs a wave are spent while the matrix pipe is busy (all in a row before the first MFMA
+    // left the pipe idle at the head of every step: 40.9 -> 39.8 us per layer1 conv)
     auto load_p_piece = [&](int c, int buf, int ps) {
         const int soff = (c * HW) << 4;
         float *Pb = buf ? Ps1 : Ps0;
@@ -523,32 +413,25 @@ __device__ __forceinline__ void conv_wf4_body(const Wf4Args &p) {
         if (ps * NT < p.cells && ps * NT + tid < p.cells)
             __builtin_amdgcn_raw_ptr_buffer_load_lds(xrsrc, (lds_float *)(Pb + (ps * NT + tid - lane) * 4), 16, pvoff[ps], soff, 0, 0);
     };
-    auto store_a = [&](int buf) {
-        if constexpr (!DMA_A) {
-            float *Ab = buf ? As1 : As0;
-#pragma unroll
-            for (int it = 0; it < 5; ++it)
-                if (it < 4 || wave < 4) *reinterpret_cast<float4 *>(Ab + (it * 512 + tid) * 4) = areg[it];
-        }
-    };
 
-    // ---- transform: 12 wave-items = 6 rows of B^T d B x 2 halves of the block's tiles; a wave-item's 64 lanes are 16 tiles x
-    //      4 channels.  Waves 4-7 take rows 0-3 (both halves), waves 0-3 row 4 or 5 of one half ----
-    const int ti = PLANAR ? (lane & 15) : (lane >> 2), tch = PLANAR ? (lane >> 4) : (lane & 3);
-    constexpr int rs = PLANAR ? 4 * S : 16 * S, psz = PLANAR ? S : 4 * S, cst = PLANAR ? 1 : 4;
-    auto item_bases = [&](int half, int &pbase, int &vbase) {
-        const int tj = half * 16 + ti;
-        const int t_nb = tj >> lT, t_r = (tj >> LBC) & BRm;
-        int t_c = tj & BCm;
-        if (PACK && t_c >= p.tw) t_c += 1;                       // spare slots read the donor patch, one cell further right
-        pbase = (PLANAR ? tch * p.cells : tch) + (((t_nb * p.R + 4 * t_r) * 4) * S + t_c) * cst;
-        vbase = (((half * 4 + tch) * 16) + ti) * 36;
+    // ---- transform.  32 tiles: a lane takes a channel PAIR of one of the block's tiles (wf4_transform_row2), so a whole row of
+    //      B^T d B is ONE wave-item: six per step -- waves 4-7 rows 0-3, waves 0-1 rows 4-5.  16 tiles: three two-row items
+    //      (wf4_transform_2rows) on waves 1-3, or the same items woven into every wave's MFMAs ----
+    constexpr int rs = 16 * S, psz = 4 * S;                      // floats per patch row, per x phase
+    // NOT PART OF THE KERNEL: nothing reads pb0.  These lines are what is left of a dropped transform's lane bases (tile = lane / 4,
+    // channel = lane % 4).  The values are dead, but the compiler merges the epilogue's lane / 4, lane % 4 and tile coordinates
+    // with them before it drops them, and that decides where those sit in 14 of the 21 instantiations: without these lines
+    // the 14 come out with other register numbers and a few instructions in another order (same instructions, same registers,
+    // LDS and scratch).  They go with the next change that is allowed to alter the device code.
+    const int ti = lane >> 2, tch = lane & 3;
+    auto item_base = [&](int &pbase) {
+        const int t_nb = ti >> lT, t_r = (ti >> LBC) & BRm;
+        int t_c = ti & BCm;
+        if (PACK && t_c >= p.tw) t_c += 1;
+        pbase = tch + (((t_nb * p.R + 4 * t_r) * 4) * S + t_c) * 4;
     };
-    int pb0, vb0, pb1, vb1;
-    item_bases(0, pb0, vb0);
-    item_bases(1, pb1, vb1);
-    // 16-byte-cell layout: a lane takes a channel PAIR of one of the block's 32 tiles (wf4_transform_row2), so a whole row of
-    // B^T d B is ONE wave-item: six per step -- waves 4-7 rows 0-3, waves 0-1 rows 4-5
+    int pb0;
+    item_base(pb0);
     int pb2 = 0, vb2 = 0;
     const int hr = lane >> 5;                                    // HALF: which row of its pair this lane transforms
     if constexpr (HALF) {
@@ -558,7 +441,7 @@ __device__ __forceinline__ void conv_wf4_body(const Wf4Args &p) {
         if (PACK && t_c >= p.tw) t_c += 1;
         pb2 = 2 * cp + (((t_nb * p.R + 4 * t_r) * 4) * S + t_c) * 4;
         vb2 = ((2 * cp * 16) + tj) * 36;
-    } else if constexpr (!PLANAR) {
+    } else {
         const int tj = lane >> 1, cp = lane & 1;
         const int t_nb = tj >> lT, t_r = (tj >> LBC) & BRm;
         int t_c = tj & BCm;
@@ -587,7 +470,7 @@ __device__ __forceinline__ void conv_wf4_body(const Wf4Args &p) {
     const float wv_c1 = wv_k0 ? 4.f : wave == 2 ? (hr ? 4.f : -4.f) : (hr ? 2.f : -2.f);
     const float wv_c2 = wv_k0 ? -5.f : wave == 2 ? -4.f : -1.f;
     const float wv_c3 = wv_k0 ? 1.f : wave == 2 ? (hr ? -1.f : 1.f) : (hr ? -2.f : 2.f);
-    auto transform_first = [&](int pbuf, int vbuf) {           // waves 4-7: a whole row (both halves)
+    auto transform_first = [&](int pbuf, int vbuf) {           // waves 4-7: a whole row each
         if constexpr (WF4_KNOCK & 4) return;
         const float *Pb = pbuf ? Ps1 : Ps0;
         float *Vb = vbuf ? Vs1 : Vs0;
@@ -595,47 +478,25 @@ __device__ __forceinline__ void conv_wf4_body(const Wf4Args &p) {
             if (wave == 1) wf4_transform_2rows<0, rs, psz>(Pb, Vb, pb2 + hr * rs, vb2 + hr * 30, hr);
             else if (wave == 2) wf4_transform_2rows<1, rs, psz>(Pb, Vb, pb2, vb2 + 6 + hr * 6, hr);
             else if (wave == 3) wf4_transform_2rows<2, rs, psz>(Pb, Vb, pb2, vb2 + 18 + hr * 6, hr);
-        } else if constexpr (!PLANAR) {
+        } else {
             if (wave == 4) wf4_transform_row2<0, rs, psz>(Pb, Vb, pb2, vb2);
             else if (wave == 5) wf4_transform_row2<1, rs, psz>(Pb, Vb, pb2, vb2);
             else if (wave == 6) wf4_transform_row2<2, rs, psz>(Pb, Vb, pb2, vb2);
             else if (wave == 7) wf4_transform_row2<3, rs, psz>(Pb, Vb, pb2, vb2);
-        } else if (wave == 4) {
-            wf4_transform_row<0, rs, psz, cst>(Pb, Vb, pb0, vb0);
-            wf4_transform_row<0, rs, psz, cst>(Pb, Vb, pb1, vb1);
-        } else if (wave == 5) {
-            wf4_transform_row<1, rs, psz, cst>(Pb, Vb, pb0, vb0);
-            wf4_transform_row<1, rs, psz, cst>(Pb, Vb, pb1, vb1);
-        } else if (wave == 6) {
-            wf4_transform_row<2, rs, psz, cst>(Pb, Vb, pb0, vb0);
-            wf4_transform_row<2, rs, psz, cst>(Pb, Vb, pb1, vb1);
-        } else if (wave == 7) {
-            wf4_transform_row<3, rs, psz, cst>(Pb, Vb, pb0, vb0);
-            wf4_transform_row<3, rs, psz, cst>(Pb, Vb, pb1, vb1);
         }
     };
-    const int pbw = (wave & 1) ? pb1 : pb0, vbw = (wave & 1) ? vb1 : vb0;
-    auto transform_last = [&](int pbuf, int vbuf) {            // waves 0-3: row 4 or 5 of one half
+    auto transform_last = [&](int pbuf, int vbuf) {            // waves 0-1: rows 4 and 5 (32-tile blocks)
         if constexpr (WF4_KNOCK & 4 || HALF) return;
         const float *Pb = pbuf ? Ps1 : Ps0;
         float *Vb = vbuf ? Vs1 : Vs0;
-        if constexpr (!PLANAR) {
-            if (wave == 0) wf4_transform_row2<4, rs, psz>(Pb, Vb, pb2, vb2);
-            else if (wave == 1) wf4_transform_row2<5, rs, psz>(Pb, Vb, pb2, vb2);
-        } else {
-            if (wave < 2) wf4_transform_row<4, rs, psz, cst>(Pb, Vb, pbw, vbw);
-            else if (wave < 4) wf4_transform_row<5, rs, psz, cst>(Pb, Vb, pbw, vbw);
-        }
+        if (wave == 0) wf4_transform_row2<4, rs, psz>(Pb, Vb, pb2, vb2);
+        else if (wave == 1) wf4_transform_row2<5, rs, psz>(Pb, Vb, pb2, vb2);
     };
 
     f32x4 acc[36];
 #pragma unroll
     for (int f = 0; f < 36; ++f) acc[f] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    const int a_off = ((wm * 4 + lk) * 16 + li) * 36;      // this lane's 36 frequencies of A[k = lk][channel 16 wm + li]
-    const int b_off = ((wn * 4 + lk) * 16 + li) * 36;      // ... of V[k = lk][tile 16 wn + li]
-    // spread: the LDS-DMA requests of chunk c + 1's filter slice (into A[buf ^ 1]) and chunk c + 2's patch (into P[buf]) go
-    // out one per MFMA group
-#if WF4_GLOBAL_A
+    const int b_off = ((wn * 4 + lk) * 16 + li) * 36;      // this lane's 36 frequencies of V[k = lk][tile 16 wn + li]
     // filter fragments: u[cout block][chunk][wm][g = 4 frequencies][lane][4] -- group g of chunk c for this wave is ONE load
     // instruction over a contiguous 1 KB; a ring of AHEAD + 1 register slots, the load for group G + AHEAD goes out when group
     // G's MFMAs do (G counts groups across K steps: 9 per step, two steps unrolled -> 18 = 3 rings of 6)
@@ -648,6 +509,7 @@ __device__ __forceinline__ void conv_wf4_body(const Wf4Args &p) {
         const int soff = (int)((((unsigned)coutblk * (unsigned)p.nchunks + (unsigned)c) * 36u + (unsigned)(wm * 9 + g)) << 10);
         ga[decltype(slot)::value] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(ursrc, ga_voff, soff, 0));
     };
+    // the phased K step's MFMAs: 9 groups of 4, chunk c + 2's patch requests behind the first groups
     auto mma_ga = [&](auto parity, int c, bool more2) {
         constexpr int par = decltype(parity)::value;
         constexpr bool NOFRAG = (WF4_KNOCK & 16) != 0, NOMMA = (WF4_KNOCK & 8) != 0;
@@ -797,51 +659,10 @@ __device__ __forceinline__ void conv_wf4_body(const Wf4Args &p) {
             }
         }
     };
-#endif
-    auto mma = [&](int buf, int c, bool more, bool more2, auto spread) {
-        const float4 *Ap = reinterpret_cast<const float4 *>((buf ? As1 : As0) + a_off);
-        const float4 *Vp = reinterpret_cast<const float4 *>((buf ? Vs1 : Vs0) + b_off);
-        // three rotating fragment slots, requested two groups (8 MFMAs) ahead; the scheduling barriers keep that distance
-        float4 fa[3], fb[3];
-        constexpr bool NOFRAG = (WF4_KNOCK & 16) != 0, NOMMA = (WF4_KNOCK & 8) != 0;
-        if constexpr (NOFRAG) {
-            fa[0] = fa[1] = fa[2] = make_float4(1.f, 2.f, 3.f, (float)c);
-            fb[0] = fb[1] = fb[2] = make_float4(1.f, 2.f, 3.f, (float)lane);
-        } else {
-            fa[0] = Ap[0]; fb[0] = Vp[0];
-            fa[1] = Ap[1]; fb[1] = Vp[1];
-        }
-#pragma unroll
-        for (int g = 0; g < 9; ++g) {
-            if (!NOFRAG && g + 2 < 9) {
-                fa[(g + 2) % 3] = Ap[g + 2];
-                fb[(g + 2) % 3] = Vp[g + 2];
-            }
-            const float4 a = fa[g % 3], b = fb[g % 3];
-            if constexpr (NOMMA) {
-                acc[4 * g + 0].x += a.x * b.x; acc[4 * g + 1].x += a.y * b.y; acc[4 * g + 2].x += a.z * b.z; acc[4 * g + 3].x += a.w * b.w;
-            } else {
-            acc[4 * g + 0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, acc[4 * g + 0], 0, 0, 0);
-            acc[4 * g + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b.y, acc[4 * g + 1], 0, 0, 0);
-            acc[4 * g + 2] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b.z, acc[4 * g + 2], 0, 0, 0);
-            acc[4 * g + 3] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b.w, acc[4 * g + 3], 0, 0, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            if constexpr (decltype(spread)::value && DMA_P) {
-                if (g < 5) {
-                    if (more) load_a_piece(c + 1, buf ^ 1, g);
-                } else if (g < 5 + WF4_P_PASSES) {
-                    if (more2) load_p_piece(c + 2, buf, g - 5);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-    };
 
-    // ---- prologue: chunk 0 in LDS and transformed, chunk 1's patch in LDS ----
+    // ---- prologue: chunk 0's patch in LDS and transformed, its first filter fragments and chunk 1's patch requested ----
     WF4_MARK(0);
     load_p(0, 0);
-#if WF4_GLOBAL_A
     {
         auto first = [&](auto sl) { ga_load(sl, 0, decltype(sl)::value); };      // groups 0 .. AHEAD - 1 of chunk 0
         first(std::integral_constant<int, 0>{});
@@ -853,72 +674,39 @@ __device__ __forceinline__ void conv_wf4_body(const Wf4Args &p) {
         if (GA_D > 6) first(std::integral_constant<int, 6 % GA_SLOTS>{});
         if (GA_D > 7) first(std::integral_constant<int, 7 % GA_SLOTS>{});
     }
-#else
-    load_a(0, 0);
-#endif
-    store_p(0);
-    store_a(0);
     __syncthreads();
     WF4_MARK(1);
     if (p.nchunks > 1) load_p(1, 1);
     transform_first(0, 0);
     transform_last(0, 0);
-    if (p.nchunks > 1) store_p(1);
     __syncthreads();
     WF4_MARK(2);
     // (cache policy of the LDS-DMA requests, measured: non-temporal patch / filter / both 41.6 / 41.3 / 42.5 us against 39.0 us for
     //  the default policy -- neighbouring workgroups share halo pixels and every workgroup the filter -- sc0 39.2 us)
-    // one K step; the buffer parity is a compile-time constant, so the compiler can tell the LDS-DMA destinations
-    // (A[nxt], P[cur]) from what the step reads and writes (A[cur], V[cur], P[nxt], V[nxt]) and lets the DMA fly
+    // one K step; the buffer parity is a compile-time constant, so the compiler can tell the LDS-DMA destination (P[cur]) from
+    // what the step reads and writes (V[cur], P[nxt], V[nxt]) and lets the DMA fly
     auto kstep = [&](auto parity, int c) {
         constexpr int cur = decltype(parity)::value, nxt = cur ^ 1;
         const bool more = c + 1 < p.nchunks, more2 = c + 2 < p.nchunks;
-        if (STAGGER) {
-            // A[nxt] was last read by the MFMAs of chunk c - 1, P[cur] by the transform of chunk c: free for the whole step.
-            // Waves 4-7 transform BEFORE they request their share of the next operands (the patch they read landed a step
-            // ago; an LDS-DMA instruction holds a wave's issue slot ~100 cycles, seven of them would delay the transform
-            // their MFMAs wait for): 38.2 -> 37.6 us
-            WF4_STEP_MARK(c, 0);
-            if (!WEAVE && more) transform_first(nxt, nxt);
-            WF4_STEP_MARK(c, 1);
-#if WF4_GLOBAL_A
-            if constexpr (WEAVE) {
-                mma_weave(parity, c, more2);           // every wave carries its item of chunk c + 1 inside its own MFMA stream
-            } else {
-                mma_ga(parity, c, more2);
-            }
-#else
-            if constexpr (SPREAD) {
-                mma(cur, c, more, more2, std::true_type{});
-            } else {
-                if (more) load_a(c + 1, nxt);
-                if (more2) load_p(c + 2, cur);
-                mma(cur, c, more, more2, std::false_type{});
-            }
-#endif
-            WF4_STEP_MARK(c, 2);
-            if (more) transform_last(nxt, nxt);
-            WF4_STEP_MARK(c, 3);
+        // P[cur] was last read by the transform of chunk c: free for the whole step.  Phased: waves 4-7 (16 tiles: 1-3) transform
+        // BEFORE they request their share of the next patch (the patch they read landed a step ago; an LDS-DMA instruction holds
+        // a wave's issue slot ~100 cycles and would delay the transform their MFMAs wait for): 38.2 -> 37.6 us
+        WF4_STEP_MARK(c, 0);
+        if (!WEAVE && more) transform_first(nxt, nxt);
+        WF4_STEP_MARK(c, 1);
+        if constexpr (WEAVE) {
+            mma_weave(parity, c, more2);           // every wave carries its item of chunk c + 1 inside its own MFMA stream
         } else {
-#if WF4_GLOBAL_A
             mma_ga(parity, c, more2);
-#else
-            if (more) load_a(c + 1, nxt);
-            if (more2) load_p(c + 2, cur);
-            mma(cur, c, more, more2, std::false_type{});
-#endif
-            if (more) {
-                transform_first(nxt, nxt);
-                transform_last(nxt, nxt);
-            }
         }
-        if (more) store_a(nxt);
-        if (more2) store_p(cur);
+        WF4_STEP_MARK(c, 2);
+        if (more) transform_last(nxt, nxt);
+        WF4_STEP_MARK(c, 3);
         __syncthreads();
         WF4_STEP_MARK(c, 4);
     };
-    // static priority for the waves that multiply first (0-3; their SIMD partners 4-7 open every step with the patch
-    // transform): 39.2 -> 38.5-38.8 us per layer1 conv; the other half at priority 1 instead: 41.3 us
+    // 32-tile blocks: static priority for the waves that multiply first (0-3; their SIMD partners 4-7 open every step with the
+    // patch transform): 39.2 -> 38.5-38.8 us per layer1 conv; the other half at priority 1 instead: 41.3 us
     if (!HALF && wave < 4) __builtin_amdgcn_s_setprio(1);
     for (int c = 0; c < p.nchunks; c += 2) {
         kstep(std::integral_constant<int, 0>{}, c);
@@ -936,15 +724,9 @@ __device__ __forceinline__ void conv_wf4_body(const Wf4Args &p) {
     const bool plain = !p.ep.bias && p.ep.scale && p.ep.shift && p.ep.act == 1 && !(p.ep.res && p.ep.res_post);
     const float4 scale = plain ? reinterpret_cast<const float4 *>(p.ep.scale)[cqc] : one4;      // the straight-line tail's
     const float4 shift = plain ? reinterpret_cast<const float4 *>(p.ep.shift)[cqc] : z4;        // parameters, held in registers
-    // the tail is the same for the whole launch: scalar branches pick the straight-line form where it applies and whether a
-    // residual is fetched
-#if WF4_GLOBAL_A
-    // the K loop is over: V (and, for half blocks, P) is free -- 4.25 KB of exchange buffer per wave
+    // the K loop is over: V (and, for 16-tile blocks, P) is free -- 4.25 KB of exchange buffer per wave
     float4 *xb = HALF ? reinterpret_cast<float4 *>(wave == 0 ? Vs0 : wave == 1 ? Vs1 : wave == 2 ? Ps0 : Ps1)
                       : reinterpret_cast<float4 *>(wave < 4 ? Vs0 : Vs1) + (wave & 3) * (4 * 68);
-#else
-    float4 *xb = reinterpret_cast<float4 *>(As0) + wave * (4 * 68);      // the K loop is over: A0 is free (8 x 4.25 KB)
-#endif
     const int te = lane >> 2, be = lane & 3;
     const int oj2 = wn * 16 + te;
     int n2 = n0 + (oj2 >> lT), ty2 = ty0 + ((oj2 >> LBC) & BRm), tx2 = tx0 + (oj2 & BCm);
@@ -974,6 +756,8 @@ __device__ __forceinline__ void conv_wf4_body(const Wf4Args &p) {
         row(std::integral_constant<int, 2>{}, res, pl);
         row(std::integral_constant<int, 3>{}, res, pl);
     };
+    // the tail is the same for the whole launch: scalar branches pick the straight-line form where it applies and whether a
+    // residual is fetched
     if (plain) {
         if (p.ep.res) rows(std::true_type{}, std::true_type{});
         else rows(std::false_type{}, std::true_type{});
@@ -988,12 +772,13 @@ __device__ __forceinline__ void conv_wf4_body(const Wf4Args &p) {
 #endif
 }
 
-template <bool DMA_A, bool PLANAR, bool STAGGER, int LBC, bool PACK = false, bool HALF = false, bool WEAVE = false>
+template <int LBC, bool PACK = false, bool HALF = false, bool WEAVE = false>
 __global__ void __launch_bounds__(HALF ? 256 : 512) __attribute__((amdgpu_waves_per_eu(2, 2))) conv_wf4_kernel(const Wf4Args p) {
-    conv_wf4_body<DMA_A, PLANAR, STAGGER, LBC, PACK, HALF, WEAVE>(p);
+    conv_wf4_body<LBC, PACK, HALF, WEAVE>(p);
 }
 
-// filter: OIHW 3x3 -> u[cout block][chunk][cb][kk][i][f] = (G g G^T)[f] of channel (64 blk + 16 cb + i, 4 chunk + kk); zero beyond Cout
+// filter: OIHW 3x3 -> u[cout block][chunk][wm][g][lane = 16 kk + i][f & 3] = (G g G^T)[f = 4 g + (f & 3)] of channel
+// (64 blk + 16 wm + i, 4 chunk + kk); zero beyond Cout
 __global__ void __launch_bounds__(256) wf4_filter_kernel(const float *w, float *u, unsigned total, int Cin, int Cout) {
     const unsigned i = blockIdx.x * 256 + threadIdx.x;   // (co, c) pair
     if (i >= total) return;
@@ -1023,14 +808,8 @@ __global__ void __launch_bounds__(256) wf4_filter_kernel(const float *w, float *
         f[a * 6 + 5] = g2;
     }
     float *blk = u + ((size_t)(co >> 6) * nchunks + (c >> 2)) * WF4_A_FLOATS;
-#if WF4_GLOBAL_A
     // [wm = 16-channel block][g = 4 frequencies][lane = k * 16 + channel][4]: what one wave loads for one MFMA group is contiguous
     float *up = blk + (((co >> 4) & 3) * 9 * 64 + (c & 3) * 16 + (co & 15)) * 4;
 #pragma unroll
     for (int q = 0; q < 36; ++q) up[(q >> 2) * 256 + (q & 3)] = f[q];
-#else
-    float *up = blk + (((((co >> 4) & 3) * 4 + (c & 3)) * 16) + (co & 15)) * 36;
-#pragma unroll
-    for (int q = 0; q < 36; ++q) up[q] = f[q];
-#endif
 }

@@ -986,15 +986,21 @@ int w1d_launch(pl_ctx *ctx, const float *xq, int N, int Cin, int H, int W, const
 }
 
 #include "conv_wf4_kernel.h"
-#ifndef WF4_HALF_DEFAULT
-#define WF4_HALF_DEFAULT 1
-#endif
-#ifndef WF4_WEAVE_DEFAULT
-#define WF4_WEAVE_DEFAULT 1
-#endif
-#ifndef WF4_STAGGER
-#define WF4_STAGGER true      // (probe builds: false = every wave multiplies first, the patch transform follows)
-#endif
+
+// the instantiation for a block width (log2 of its tile columns; one each, so that every patch read is base + immediate),
+// packed or plain (packed blocks exist at 8 and 16 columns only)
+template <bool HALF, bool WEAVE>
+void (*wf4_kernel_for(int lBC, bool packed))(const Wf4Args) {
+    switch (packed ? 10 + lBC : lBC) {
+    case 14: return conv_wf4_kernel<4, true, HALF, WEAVE>;
+    case 13: return conv_wf4_kernel<3, true, HALF, WEAVE>;
+    case 4: return conv_wf4_kernel<4, false, HALF, WEAVE>;
+    case 3: return conv_wf4_kernel<3, false, HALF, WEAVE>;
+    case 2: return conv_wf4_kernel<2, false, HALF, WEAVE>;
+    case 1: return conv_wf4_kernel<1, false, HALF, WEAVE>;
+    default: return conv_wf4_kernel<0, false, HALF, WEAVE>;
+    }
+}
 
 int wf4_launch(pl_ctx *ctx, const float *xq, int N, int Cin, int H, int W, const float *u, int Cout, const float *bias,
                float *yq, const float *scale, const float *shift, const float *resq, int act, double alpha) {
@@ -1004,12 +1010,12 @@ int wf4_launch(pl_ctx *ctx, const float *xq, int N, int Cin, int H, int W, const
     a.N = N; a.Cq = Cin / 4; a.Coq = Cout / 4; a.H = H; a.W = W;
     a.th = (H + 3) / 4; a.tw = (W + 3) / 4;
     a.nchunks = Cin / 4;
-    // blocks of 32 tiles on eight waves, or (PLANER_HIP_EXPERIMENT=wf4_half=1; needs the filter-in-registers build) of 16 tiles on
-    // four waves -- two workgroups per CU with barriers of their own
-    const bool half = WF4_GLOBAL_A && pl_experiment("wf4_half", WF4_HALF_DEFAULT) != 0;
+    // blocks of 16 tiles on four waves -- two workgroups per CU with barriers of their own -- or (PLANER_HIP_EXPERIMENT=wf4_half=0)
+    // of 32 tiles on eight waves
+    const bool half = pl_experiment("wf4_half", 1) != 0;
     // the 16-tile block's K step with each wave's transform item woven into its own MFMA stream (conv_wf4_kernel.h, WEAVE), or
     // (PLANER_HIP_EXPERIMENT=wf4_weave=0) as a phase of its own in front of the MFMAs
-    const bool weave = half && WF4_STAGGER && pl_experiment("wf4_weave", WF4_WEAVE_DEFAULT) != 0;
+    const bool weave = half && pl_experiment("wf4_weave", 1) != 0;
     const int TB = half ? 16 : 32;
     int BC = 1, BR = 1, lBC = 0, lBR = 0;
     while (BC < a.tw && BC < 16) BC *= 2, ++lBC;
@@ -1057,42 +1063,10 @@ int wf4_launch(pl_ctx *ctx, const float *xq, int N, int Cin, int H, int W, const
     a.divPlane = FastDiv(a.R * 4 * a.S); a.div4S = FastDiv(4 * a.S); a.divS = FastDiv(a.S);
     a.divCoB = FastDiv(a.cout_blocks); a.divCb = FastDiv(a.cblocks); a.divRb = FastDiv(a.rblocks);
     a.ep = make_epilogue(bias, scale, shift, resq, act, alpha);
-    // LDS-DMA operands, waves 4-7 transform before their MFMAs and waves 0-3 after (the variant that measured fastest: 48.5 us
-    // against 51.4 us for register-staged operands with the waves in step, layer1 of ResNet-18 at batch 32); one instantiation
-    // per block width, so that every patch read is base + immediate
-    void (*kern)(const Wf4Args) = nullptr;
-#if WF4_GLOBAL_A
-    if (half && weave) {
-        switch (a.pack_g ? 10 + lBC : lBC) {
-        case 14: kern = conv_wf4_kernel<true, false, true, 4, true, true, true>; break;
-        case 13: kern = conv_wf4_kernel<true, false, true, 3, true, true, true>; break;
-        case 4: kern = conv_wf4_kernel<true, false, true, 4, false, true, true>; break;
-        case 3: kern = conv_wf4_kernel<true, false, true, 3, false, true, true>; break;
-        case 2: kern = conv_wf4_kernel<true, false, true, 2, false, true, true>; break;
-        case 1: kern = conv_wf4_kernel<true, false, true, 1, false, true, true>; break;
-        default: kern = conv_wf4_kernel<true, false, true, 0, false, true, true>; break;
-        }
-    } else if (half) {
-        switch (a.pack_g ? 10 + lBC : lBC) {
-        case 14: kern = conv_wf4_kernel<true, false, WF4_STAGGER, 4, true, true>; break;
-        case 13: kern = conv_wf4_kernel<true, false, WF4_STAGGER, 3, true, true>; break;
-        case 4: kern = conv_wf4_kernel<true, false, WF4_STAGGER, 4, false, true>; break;
-        case 3: kern = conv_wf4_kernel<true, false, WF4_STAGGER, 3, false, true>; break;
-        case 2: kern = conv_wf4_kernel<true, false, WF4_STAGGER, 2, false, true>; break;
-        case 1: kern = conv_wf4_kernel<true, false, WF4_STAGGER, 1, false, true>; break;
-        default: kern = conv_wf4_kernel<true, false, WF4_STAGGER, 0, false, true>; break;
-        }
-    } else
-#endif
-    switch (a.pack_g ? 10 + lBC : lBC) {
-    case 14: kern = conv_wf4_kernel<true, false, WF4_STAGGER, 4, true>; break;
-    case 13: kern = conv_wf4_kernel<true, false, WF4_STAGGER, 3, true>; break;
-    case 4: kern = conv_wf4_kernel<true, false, WF4_STAGGER, 4>; break;
-    case 3: kern = conv_wf4_kernel<true, false, WF4_STAGGER, 3>; break;
-    case 2: kern = conv_wf4_kernel<true, false, WF4_STAGGER, 2>; break;
-    case 1: kern = conv_wf4_kernel<true, false, WF4_STAGGER, 1>; break;
-    default: kern = conv_wf4_kernel<true, false, WF4_STAGGER, 0>; break;
-    }
+    // three forms of the block: 16 tiles woven (what ships), 16 tiles phased, 32 tiles (phased)
+    void (*const kern)(const Wf4Args) = weave  ? wf4_kernel_for<true, true>(lBC, a.pack_g != 0)
+                                        : half ? wf4_kernel_for<true, false>(lBC, a.pack_g != 0)
+                                               : wf4_kernel_for<false, false>(lBC, a.pack_g != 0);
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(half ? 256 : 512), 0, ctx->stream, a);      // LDS: static
     PL_LAUNCH_CHECK();
     char buf[96];

@@ -141,3 +141,40 @@ def test_fused_f4x4_through_the_plan_compiler(pa):
     ref.load_json(g["input"], g["inits"], g["layers"], g["flow"])
     ref.load_weights(b)
     assert_close(y, ref(x.copy()), RTOL, "resnet18 with the fused F(4x4,3x3) kernel")
+
+
+def test_prepared_filter_layout_stated_in_numpy(pa):
+    """The one layout pl_conv2d_prepare_wf4_f32 writes (w_layout 9), stated outside the kernel: U = G g G^T of channel (co, c),
+    frequency f = 6 a + b, sits at float
+        ((co >> 6) * (Cin / 4) + (c >> 2)) * 9216 + ((((co >> 4) & 3) * 9 + (f >> 2)) * 64 + (c & 3) * 16 + (co & 15)) * 4 + (f & 3)
+    -- [cout block][chunk][wm][g][lane = 16 k + i][4] -- and every float that is no channel's is exactly 0.  Cout = 80, Cin = 8:
+    two cout blocks, the second three quarters padding (channels 80..127), two chunks.
+    Tolerance, per element, derived: wf4_filter_kernel applies G in two stages (columns, then rows) without contraction.  In a stage
+    a term of a sum meets at most 4 roundings -- the constant (1/6, 1/12, 1/24; 1/4 is exact), the product, and two sums (a row of
+    G has at most three terms) -- each of relative size 2^-24, so two stages give at most 8 * 2^-24 of (|G| |g| |G|^T)[f]."""
+    from planer_amd import _lib
+    import ctypes
+    cout, cin = 80, 8
+    rng = np.random.default_rng(80 + 8)
+    g = rng.standard_normal((cout, cin, 3, 3)).astype(np.float32)
+    n = ctypes.c_size_t()
+    _lib.call("pl_conv2d_wf4_filter_elems", cout, cin, ctypes.byref(n))
+    assert n.value == 2 * (cin // 4) * 9216
+    k = pa.asarray(g)
+    out = pa.asarray(np.full(n.value, np.nan, np.float32))          # (poisoned: the padding's zeros must be written, not found)
+    _lib.call("pl_conv2d_prepare_wf4_f32", k.ctx.handle, k.ptr, cout, cin, out.ptr)
+    u = out.get()
+    G = np.array([[1 / 4, 0, 0], [-1 / 6, -1 / 6, -1 / 6], [-1 / 6, 1 / 6, -1 / 6], [1 / 24, 1 / 12, 1 / 6], [1 / 24, -1 / 12, 1 / 6], [0, 0, 1]])
+    g64 = g.astype(np.float64)
+    U = np.einsum("ai,ocij,bj->ocab", G, g64, G).reshape(cout, cin, 36)
+    mag = np.einsum("ai,ocij,bj->ocab", np.abs(G), np.abs(g64), np.abs(G)).reshape(cout, cin, 36)
+    co, c, f = np.meshgrid(np.arange(cout), np.arange(cin), np.arange(36), indexing="ij")
+    idx = ((co >> 6) * (cin // 4) + (c >> 2)) * 9216 + ((((co >> 4) & 3) * 9 + (f >> 2)) * 64 + (c & 3) * 16 + (co & 15)) * 4 + (f & 3)
+    assert np.unique(idx).size == idx.size
+    err = np.abs(u[idx].astype(np.float64) - U)
+    print("prepared wf4 filter: max error / ((|G| |g| |G|^T) 2^-24) = %.3f (bound 8)" % (err / (mag * 2.0 ** -24)).max())
+    assert (err <= 8 * 2.0 ** -24 * mag).all()
+    rest = np.ones(u.size, bool)
+    rest[idx.ravel()] = False
+    assert rest.sum() == 48 * cin * 36
+    assert (u[rest].view(np.uint32) == 0).all()

@@ -1,8 +1,9 @@
 #!/bin/bash
 # Probe builds of the fused F(4x4,3x3) kernel: one library per (tag, compiler flags) pair under planer_amd/build/knock/, e.g.
-# knock-out masks (-DWF4_KNOCK=<mask>: bit 0 no filter loads, 1 no patch LDS-DMA, 2 no patch transform, 3 no MFMAs, 4 no V
-# fragment reads, 5 no output rows; bits 2-4 act on the shipped 16-tile form too, woven or phased); "run" times each with the K
-# sweep (tools/wf4_ksweep.py --tail).
+# knock-out masks (-DWF4_KNOCK=<mask>: bit 0 unused -- it dropped the filter's LDS-DMA while the filter slice was staged in LDS,
+# the form profiles/r04_wf4_knockout.md measured; the numbering stays -- 1 no patch LDS-DMA, 2 no patch transform, 3 no MFMAs,
+# 4 no V fragment reads, 5 no output rows; bits 2-4 act on both forms of the K step, woven and phased); "run" times each with
+# the K sweep (tools/wf4_ksweep.py --tail).
 #   tools/wf4_knock.sh build base "" k4 "-DWF4_KNOCK=4" ...     (here)
 #   tools/wf4_knock.sh run                                       (on the GPU box; writes gpurun_out/wf4_knock.txt)
 set -e
