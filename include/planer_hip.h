@@ -443,6 +443,17 @@ int pl_instancenorm_q4_f32(pl_ctx *ctx, float *xq, const float *scale, const flo
 int pl_refold_q4_f32(pl_ctx *ctx, const float *xq, float *yq, int N, int C, int H, int W, int dh_in, int dw_in, int dh_out,
                      int dw_out);
 
+/* Pixel shuffle / unshuffle (depth-to-space / space-to-depth) of a Q4 tensor in one pass.  N, C, H, W describe the
+ * NARROW side -- the output of a shuffle (inverse = 0), the input of an unshuffle (inverse = 1); the other side is the Q4 tensor
+ * (N, C r^2, H / r, W / r).  order 0, CRD (PyTorch PixelShuffle / PixelUnshuffle): wide channel c r^2 + i r + j <-> narrow channel
+ * c at pixel (h r + i, w r + j), any C.  order 1, DCR (ONNX DepthToSpace / SpaceToDepth): wide channel (i r + j) C + c, C % 4 == 0
+ * only.  r = 2, 3, 4.  nchw_out (shuffles only): y is the plain (N, C, H, W) tensor instead of a Q4 one.  Every lane of a Q4
+ * output is written, padding lanes as +0 whatever the input's hold; wide quads past ceil(C r^2 / 4) do not exist and are never
+ * touched.  Bits are moved, not computed on.  xq != y, both 16-byte aligned; 2^29 quads or more on either side, another r, or DCR
+ * with C % 4 != 0: PL_EUNSUPPORTED. */
+int pl_pixel_shuffle_q4_f32(pl_ctx *ctx, const float *xq, float *y, int N, int C, int H, int W, int r, int order, int inverse,
+                            int nchw_out);
+
 /* First call for a new conv shape times every applicable tile configuration
  * and remembers the fastest (on by default; PLANER_HIP_AUTOTUNE=0 or 0 here
  * selects the static heuristic). Never runs during graph capture. */

@@ -6,6 +6,7 @@
 #include "common.h"
 #include "device_utils.h"
 #include "instnorm_q4_kernel.h"
+#include "pixel_shuffle_q4_kernel.h"
 
 namespace {
 
@@ -835,6 +836,17 @@ __global__ void __launch_bounds__(TPB) tile_normalise_kernel(float *buf, const f
     for (unsigned i = blockIdx.x * TPB + threadIdx.x; i < total; i += stride) buf[i] = __fdiv_rn(buf[i], count[divC.div(i)]);
 }
 
+// one launch of pixel_shuffle_q4_kernel.h for (r, order), the form picked by direction and output layout
+template <int R, int ORDER>
+void launch_pixel_shuffle_q4(pl_ctx *ctx, const float *xq, float *y, unsigned total, const pixel_shuffle_q4::Geom &g, int inverse,
+                                    int nchw_out) {
+    namespace ps = pixel_shuffle_q4;
+    const unsigned grid = stream_grid(ctx, total);
+    if (inverse) ps::pixel_shuffle_q4_kernel<R, ORDER, true, false><<<grid, TPB, 0, ctx->stream>>>((const float4 *)xq, y, total, g);
+    else if (nchw_out) ps::pixel_shuffle_q4_kernel<R, ORDER, false, true><<<grid, TPB, 0, ctx->stream>>>((const float4 *)xq, y, total, g);
+    else ps::pixel_shuffle_q4_kernel<R, ORDER, false, false><<<grid, TPB, 0, ctx->stream>>>((const float4 *)xq, y, total, g);
+}
+
 }  // namespace
 
 unsigned pl_stream_grid(int cu_count, size_t work_items) {
@@ -1278,6 +1290,57 @@ int pl_refold_q4_f32(pl_ctx *ctx, const float *xq, float *yq, int N, int C, int 
     refold_q4_kernel<<<stream_grid(ctx, total), TPB, 0, ctx->stream>>>(
         (const float4 *)xq, (float4 *)yq, (unsigned)total, Cq, H, W, Hi, Wi, dh_in, dw_in, dh_out, dw_out, FastDiv(Wo), FastDiv(Ho),
         FastDiv(Cq), FastDiv(dw_out), FastDiv(dh_out), FastDiv(dh_in), FastDiv(dw_in));
+    PL_LAUNCH_CHECK();
+    return PL_OK;
+}
+
+// Pixel shuffle / unshuffle of a Q4 tensor (pixel_shuffle_q4_kernel.h).  N, C, H, W: the NARROW side -- a shuffle's
+// output, an unshuffle's input; the other side is (N, C r^2, H / r, W / r).
+int pl_pixel_shuffle_q4_f32(pl_ctx *ctx, const float *xq, float *y, int N, int C, int H, int W, int r, int order, int inverse,
+                            int nchw_out) {
+    namespace ps = pixel_shuffle_q4;
+    PL_REQUIRE(ctx && xq && y, PL_EINVAL, "pl_pixel_shuffle_q4_f32: null argument");
+    PL_REQUIRE(N >= 0 && C > 0 && H > 0 && W > 0, PL_EINVAL, "pl_pixel_shuffle_q4_f32: bad shape");
+    PL_REQUIRE(order == 0 || order == 1, PL_EINVAL, "pl_pixel_shuffle_q4_f32: order is 0 (CRD) or 1 (DCR)");
+    PL_REQUIRE(r >= 2 && r <= 4, PL_EUNSUPPORTED, "pl_pixel_shuffle_q4_f32: r = 2, 3, 4 supported, got %d", r);
+    PL_REQUIRE(H % r == 0 && W % r == 0, PL_EINVAL, "pl_pixel_shuffle_q4_f32: H and W (the narrow side's) must be multiples of r");
+    PL_REQUIRE(order == 0 || C % 4 == 0, PL_EUNSUPPORTED, "pl_pixel_shuffle_q4_f32: DCR order needs C %% 4 == 0, got C = %d", C);
+    PL_REQUIRE(!(nchw_out && inverse), PL_EINVAL, "pl_pixel_shuffle_q4_f32: nchw_out goes with a shuffle (inverse = 0) only");
+    PL_REQUIRE(aligned16(xq) && aligned16(y), PL_EINVAL, "pl_pixel_shuffle_q4_f32: tensors must be 16-byte aligned");
+    PL_REQUIRE(xq != y, PL_EINVAL, "pl_pixel_shuffle_q4_f32: not an in-place operation");
+    const size_t lim = 1ull << 29;
+    // quads of one side, saturating at 2^29: every factor is checked before the next multiplication
+    auto quads = [&](size_t cq, size_t h, size_t w) {
+        size_t t = (size_t)N;
+        for (size_t f : {cq, h, w}) {
+            if (t >= lim) return lim;
+            t *= f;                                             // t < 2^29, f < 2^33
+        }
+        return t < lim ? t : lim;
+    };
+    ps::Geom g;
+    g.C = C;
+    g.Cq = (C + 3) / 4;
+    const size_t cqw = ((size_t)C * r * r + 3) / 4;              // C < 2^31, r^2 <= 16
+    g.Hs = H / r;
+    g.Ws = W / r;
+    const size_t narrow = quads((size_t)g.Cq, (size_t)H, (size_t)W), wide = quads(cqw, (size_t)g.Hs, (size_t)g.Ws);
+    const size_t total = quads((size_t)g.Cq, (size_t)g.Hs, (size_t)g.Ws);       // one thread per (narrow quad, small pixel)
+    PL_REQUIRE(narrow < lim && wide < lim && loop32_ok(ctx, total), PL_EUNSUPPORTED,
+               "pl_pixel_shuffle_q4_f32: Q4 tensor of 2^29 pixel quads (8 GiB) or more");
+    if (!total) return PL_OK;
+    g.CqW = (int)cqw;                                            // wide < 2^29 and total > 0: cqw < 2^29
+    g.divWs = FastDiv(g.Ws); g.divHs = FastDiv(g.Hs); g.divCq = FastDiv(g.Cq);
+    CtxGuard guard(ctx);
+    const unsigned n = (unsigned)total;
+    switch (r * 2 + order) {
+    case 4: launch_pixel_shuffle_q4<2, 0>(ctx, xq, y, n, g, inverse, nchw_out); break;
+    case 5: launch_pixel_shuffle_q4<2, 1>(ctx, xq, y, n, g, inverse, nchw_out); break;
+    case 6: launch_pixel_shuffle_q4<3, 0>(ctx, xq, y, n, g, inverse, nchw_out); break;
+    case 7: launch_pixel_shuffle_q4<3, 1>(ctx, xq, y, n, g, inverse, nchw_out); break;
+    case 8: launch_pixel_shuffle_q4<4, 0>(ctx, xq, y, n, g, inverse, nchw_out); break;
+    default: launch_pixel_shuffle_q4<4, 1>(ctx, xq, y, n, g, inverse, nchw_out); break;
+    }
     PL_LAUNCH_CHECK();
     return PL_OK;
 }

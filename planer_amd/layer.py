@@ -571,6 +571,41 @@ def Reshape(x, shp):
     return x.reshape(shp)
 
 
+# ---- pixel shuffle / unshuffle as an exporter writes them: reshape -> transpose -> reshape -----------------------
+# (order, inverse) -> the 6-D transpose.  CRD is PyTorch's PixelShuffle / PixelUnshuffle, DCR ONNX's DepthToSpace / SpaceToDepth.
+PIXEL_SHUFFLE_AXES = {("crd", False): [0, 1, 4, 2, 5, 3], ("dcr", False): [0, 3, 4, 1, 5, 2],
+                      ("crd", True): [0, 1, 3, 5, 2, 4], ("dcr", True): [0, 3, 5, 1, 2, 4]}
+
+
+def pixel_shuffle_shapes(shape, r, order="crd", inverse=False):
+    """(6-D shape, result shape) of the trio on a 4-D input `shape`, or None where r does not divide what it has to."""
+    n, c, h, w = [int(v) for v in shape]
+    r = int(r)
+    if r < 1 or (order, bool(inverse)) not in PIXEL_SHUFFLE_AXES:
+        return None
+    if inverse:
+        if h % r or w % r:
+            return None
+        return (n, c, h // r, r, w // r, r), (n, c * r * r, h // r, w // r)
+    if c % (r * r):
+        return None
+    cn = c // (r * r)
+    return ((n, cn, r, r, h, w) if order == "crd" else (n, r, r, cn, h, w)), (n, cn, h * r, w * r)
+
+
+def PixelShuffle(x, r, order="crd", inverse=False):
+    """The plan-internal kind `pixelshuffle` (plan.fuse_pixel_shuffle): a pixel shuffle by r (inverse: an unshuffle) in CRD or
+    DCR channel order on an NCHW tensor, as EXACTLY the three steps it replaces -- Reshape, Transpose (pl_transpose_f32), Reshape --
+    so a plan whose input never becomes channel-quad runs the kernel it ran before.  q4.PixelShuffleQ4 is the one-pass form."""
+    _f32(x)
+    if x.ndim != 4:
+        raise ValueError("pixelshuffle: a 4-D activation, got %s" % (x.shape,))
+    shp = pixel_shuffle_shapes(x.shape, r, order, inverse)
+    if shp is None:
+        raise ValueError("pixelshuffle: r = %s, order %r does not fit the input %s" % (r, order, x.shape))
+    return Transpose(x.reshape(shp[0]), PIXEL_SHUFFLE_AXES[(order, bool(inverse))]).reshape(shp[1])
+
+
 def Squeeze(x, axes=[0]):
     """layer.Squeeze (layer.py:133-134): np.squeeze(x, axis=axes[0])"""
     a = axes[0] + x.ndim if axes[0] < 0 else axes[0]
@@ -1171,7 +1206,7 @@ layer_map = {"dense": Dense, "conv": Conv2d, "relu": ReLU, "leakyrelu": LeakyReL
              "erf": Erf, "instancenormalization": InstanceNormalization,
              "scatternd": Scatternd, "nonzero": NonZero, "topk": TopK, "lstm": LSTM,
              # plan-compiler internal
-             "conv_fused": ConvFused, "convt_fused": ConvTransposeFused}
+             "conv_fused": ConvFused, "convt_fused": ConvTransposeFused, "pixelshuffle": PixelShuffle}
 # integer shape arithmetic: the same kinds, evaluated on host mirrors when no activation is involved
 for _k, _ref in (("add", lambda a, b: a + b), ("sub", lambda a, b: a - b), ("mul", lambda a, b: a * b),
                  ("div", lambda a, b: a / b), ("concat", lambda *xs, axis=0: numpy.concatenate(xs, axis=axis)),

@@ -31,7 +31,7 @@ from .conv_layouts import (CONV_KINDS, CONVT_KINDS, DIRECT_Q4, IGEMM_NCHW, LAYOU
                            WINO43_Q4, choose, suffix)
 from .layer import layer_map, wrap
 from .plan import (assign_layouts, chain_winograd, fold_dilated, fuse_conv1x1_wino_in, fuse_flow, fuse_instnorm_q4, fuse_linear_add,
-                   pair_sibling_convs)
+                   fuse_pixel_shuffle, pair_sibling_convs, pixel_shuffle_enabled)
 
 _q4.register(layer_map)
 
@@ -346,6 +346,7 @@ class Net:
         self.conv_wino_fused = 0     # 1x1 convs the last plan runs inside the next conv's Winograd input transform
         self.instnorm_fused = 0      # add / relu steps the last plan runs inside a channel-quad instance norm
         self.linear_adds_fused = 0   # add steps the last plan runs inside a channel-quad linear upsample / resize
+        self.pixel_shuffles_fused = 0  # reshape / transpose / reshape trios the last plan runs as one pixelshuffle step
         # force_algo: w_layout (int) every eligible 3x3/s1/p1 conv must use, or None = pick by timing
         fa = os.environ.get("PLANER_HIP_CONV_ALGO")
         self.force_algo = int(fa) if fa else None
@@ -515,6 +516,10 @@ class Net:
         else:
             body, flow, nfused = [list(b) for b in self.layer], [list(f) for f in self.flow], 0
         if self.use_q4:
+            self.pixel_shuffles_fused = 0
+            if pixel_shuffle_enabled():
+                # reshape -> transpose -> reshape that is a pixel shuffle / unshuffle as one step, which has a one-pass Q4 kernel
+                body, flow, self.pixel_shuffles_fused = fuse_pixel_shuffle(body, flow, shapes)
             wmap = dict(zip(self.inits, self.weights))
             body, flow, _ = assign_layouts(body, flow, self.inits, shapes, force=self.use_q4 == "force",
                                            values=lambda key: wmap[key].host if key in wmap else None)

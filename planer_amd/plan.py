@@ -16,7 +16,7 @@ chain was, so a residual operand produced after the conv is still available.
 import os
 
 from .conv_layouts import DIRECT_Q4, STAGED_LAYOUTS, convt_phase_eligible, dw_q4_eligible, q4_conv_eligible
-from .layer import _nearest_shift
+from .layer import PIXEL_SHUFFLE_AXES, _nearest_shift, pixel_shuffle_shapes
 
 ACT_NONE, ACT_RELU, ACT_LEAKY = 0, 1, 2
 ACT_RES_AFTER = 16      # OR-ed into `act`: the residual is added after the activation
@@ -131,7 +131,7 @@ def fuse_flow(layers, flow, init_names, shapes):
 # downstream of a conv -- and everything else reads NCHW, with a conversion step inserted where a
 # value is needed in the layout it was not produced in (converted copies are cached per value).
 Q4_POINTWISE = ("maxpool", "averagepool", "gap", "upsample", "batchnorm", "relu", "leakyrelu", "sigmoid",
-                "add", "concat", "clip", "instancenormalization", "pad", "resize")
+                "add", "concat", "clip", "instancenormalization", "pad", "resize", "pixelshuffle")
 # the kinds of instance-normalised generators (fast-neural-style, CycleGAN ...): PLANER_HIP_INSTNORM_Q4=0 takes them out again,
 # which gives the program of a compiler without them
 INSTNORM_Q4_KINDS = ("instancenormalization", "pad")
@@ -242,6 +242,11 @@ def _q4_pointwise_ok(kind, srcs, para, inits, shapes, values=None):
             cv = values(srcs[2])
             cv = None if cv is None or len(cv.reshape(-1)) != 1 else float(cv.reshape(-1)[0])
         return pv is not None and cv is not None and pad_q4_ok(c, list(pv.reshape(-1)), cv, para.get("mode", "constant"))
+    if kind == "pixelshuffle":              # CRD for any channel count; DCR where every narrow quad is one aligned wide quad
+        r = int(para.get("r", 0))
+        narrow = c if para.get("inverse") else c // max(1, r * r)
+        return (list(srcs) == acts and r in PIXEL_SHUFFLE_R and (para.get("order") == "crd" or (para.get("order") == "dcr" and narrow % 4 == 0))
+                and pixel_shuffle_shapes(shapes[acts[0]], r, para.get("order"), para.get("inverse")) is not None)
     if kind == "add":
         return len(srcs) == 2 and len(acts) == 2 and tuple(shapes[srcs[0]]) == tuple(shapes[srcs[1]])
     if kind == "concat":
@@ -386,13 +391,16 @@ def assign_layouts(body, flow, init_names, shapes, force=False, values=None):
             as_q4 = True
             args = [need(k, True) for k in srcs]
             new_kind = kind + "_q4"
+            if kind == "pixelshuffle" and not para.get("inverse") and ends_program(i, dst):
+                # a shuffle that ends the program (an ESPCN tail) writes NCHW itself: no Q4 result, no from_q4 behind it
+                para = dict(para, nchw_out=True)
         if not as_q4:
             args = [need(k, False) for k in srcs]
             new_kind = kind
         if kind in ("relu", "clip", "instancenormalization"):   # in place (layer.py:46, 217-226, 250-251): cached copies of
             drop_copies(srcs[0])                                # the input go stale
         out_key = dst
-        produces_q4 = as_q4 and kind != "gap"
+        produces_q4 = as_q4 and kind != "gap" and not (kind == "pixelshuffle" and para.get("nchw_out"))
         if produces_q4 and i == last:
             out_key = dst + "@q4"                # the program's result is handed back as NCHW below
         add_layer([name, new_kind, para])
@@ -561,6 +569,99 @@ def fuse_linear_add(body, flow, shapes):
     return out_body, [[srcs, [name], dst] for srcs, name, kind, para, dst in out], len(fused_at)
 
 
+# ---- pixel shuffle / unshuffle ---------------------------------------------------------------------------------------------------
+# planer has no depth-to-space kind (the operator table is the reference's): a sub-pixel convolution's shuffle arrives as what an
+# exporter writes, reshape -> transpose (6-D) -> reshape.  As three steps it drops out of Q4 -- from_q4, the 6-D transpose, to_q4
+# -- on the largest tensors of a super-resolution net.  fuse_pixel_shuffle names the trio (`pixelshuffle`, layer.PixelShuffle: the
+# same three steps) so that assign_layouts can give it its one-pass Q4 kernel (q4.PixelShuffleQ4).
+# PLANER_HIP_PIXEL_SHUFFLE_Q4=0 skips the pass: the program of a compiler without it.
+PIXEL_SHUFFLE_R = (2, 3, 4)
+
+
+def pixel_shuffle_enabled():
+    return os.environ.get("PLANER_HIP_PIXEL_SHUFFLE_Q4", "1") != "0"
+
+
+def match_pixel_shuffle(s_in, s_mid, axis, s_out):
+    """-> {"r", "order", "inverse"} where reshape(s_in -> s_mid), transpose(axis), reshape(-> s_out) is a pixel shuffle or
+    unshuffle by r = 2, 3, 4 (the four forms of layer.PIXEL_SHUFFLE_AXES, both r extents equal, every shape as the form has it),
+    else None."""
+    if s_in is None or s_mid is None or s_out is None or len(s_in) != 4 or len(s_mid) != 6 or len(s_out) != 4:
+        return None
+    for (order, inverse), ax in PIXEL_SHUFFLE_AXES.items():
+        if [int(a) for a in axis] != ax:
+            continue
+        r = int(s_mid[3] if inverse else s_mid[2] if order == "crd" else s_mid[1])
+        if r not in PIXEL_SHUFFLE_R:
+            return None
+        want = pixel_shuffle_shapes(s_in, r, order, inverse)
+        if want is None or tuple(s_mid) != want[0] or tuple(s_out) != want[1]:
+            return None
+        return {"r": r, "order": order, "inverse": inverse}
+    return None
+
+
+def fuse_pixel_shuffle(body, flow, shapes):
+    """-> (body', flow', number of trios).  Runs on fuse_flow's program, in front of assign_layouts.  A `reshape` of a 4-D tensor
+    to 6-D, a `transpose` of that by one of the four permutations, and a `reshape` back to 4-D become ONE `pixelshuffle` step
+    {r, order, inverse} where the traced `shapes` say so (match_pixel_shuffle) -- the shapes alone, so a shape operand computed by
+    shape-domain steps is as good as a constant one -- and both intermediates have exactly one writer and one reader.  The step
+    sits where the last reshape was and reads the first reshape's input there: not fused where a step between rewrites that input
+    in place or writes it.  Steps that only fed the reshapes' shape operands stay where they are."""
+    kinds = {name: (kind, para) for name, kind, para in body}
+    steps = expand_steps(flow)
+    readers, writers = {}, {}
+    for i, (srcs, _, dst) in enumerate(steps):
+        for k in set(srcs):
+            readers.setdefault(k, []).append(i)
+        for k in _as_list(dst):
+            writers[k] = writers.get(k, 0) + 1
+
+    def only_reader(i, dst, kind):
+        """The one step that reads `dst` (written once, by step i), where it comes later and is of `kind` with `dst` its first operand."""
+        r = readers.get(dst, [])
+        if not isinstance(dst, str) or len(r) != 1 or writers.get(dst, 0) != 1 or r[0] <= i:
+            return None
+        jsrcs, jname, jdst = steps[r[0]]
+        return r[0] if kinds[jname][0] == kind and jsrcs[0] == dst and jsrcs.count(dst) == 1 and isinstance(jdst, str) else None
+
+    consumed, fused_at, names = set(), {}, {b[0] for b in body}
+    for i, (srcs, name, dst) in enumerate(steps):
+        if kinds[name][0] != "reshape" or i in consumed or len(srcs) != 2:
+            continue
+        j = only_reader(i, dst, "transpose")
+        if j is None or j in consumed or len(steps[j][0]) != 1:
+            continue
+        k = only_reader(j, steps[j][2], "reshape")
+        if k is None or k in consumed or len(steps[k][0]) != 2:
+            continue
+        x, out = srcs[0], steps[k][2]
+        form = match_pixel_shuffle(shapes.get(x), shapes.get(dst), kinds[steps[j][1]][1].get("axis", ()), shapes.get(out))
+        if form is None or tuple(shapes.get(steps[j][2]) or ()) != tuple(shapes[dst][a] for a in PIXEL_SHUFFLE_AXES[(form["order"], form["inverse"])]):
+            continue
+        if any((x in steps[t][0] and kinds[steps[t][1]][0] in _IN_PLACE) or x in _as_list(steps[t][2])
+               for t in range(i + 1, k) if t != j):
+            continue
+        new = steps[j][1] + "+"
+        while new in names:                      # a transpose layer that serves several steps: one pixelshuffle layer per trio
+            new += "+"
+        names.add(new)
+        consumed.update((i, j, k))
+        fused_at[k] = ([x], new, form, out)
+    out_body, out_flow, seen = [], [], set()
+    for i, (srcs, name, dst) in enumerate(steps):
+        if i in fused_at:
+            srcs, name, para, dst = fused_at[i]
+            out_body.append([name, "pixelshuffle", para])
+        elif i in consumed:
+            continue
+        elif name not in seen:
+            seen.add(name)
+            out_body.append([name] + list(kinds[name]))
+        out_flow.append([list(srcs), [name], dst])
+    return out_body, out_flow, len(fused_at)
+
+
 # ---- Winograd chaining ------------------------------------------------------------------------------
 # A conv_q4 step that runs F(4x4,3x3) (w_layout 7) is three kernels: input transform (x -> V), the 36
 # grouped GEMMs (V, U -> M) and output transform + fused tail (M -> y).  When the y of one such conv
@@ -571,7 +672,8 @@ def fuse_linear_add(body, flow, shapes):
 _PURE_READERS = ("conv_q4", "convt_q4", "wino4_in", "wino4_gemm", "wino4_out", "wino4_chain", "wino43_in", "wino43_gemm", "wino43_out",
                  "wino43_chain", "conv1x1_wino_in", "conv_q4_pair", "add_q4", "maxpool_q4",
                  "averagepool_q4", "gap_q4", "upsample_q4", "concat_q4", "upconcat_q4", "batchnorm_q4",
-                 "leakyrelu_q4", "sigmoid_q4", "from_q4", "pad_q4", "refold_q4", "resize_q4", "upsample_add_q4", "resize_add_q4")
+                 "leakyrelu_q4", "sigmoid_q4", "from_q4", "pad_q4", "refold_q4", "resize_q4", "upsample_add_q4", "resize_add_q4",
+                 "pixelshuffle_q4")
 
 
 def chain_winograd(body, flow, supported=lambda key: True, chain=True):

@@ -24,8 +24,8 @@ from .conv_layouts import (dw_q4_eligible, prepare_dw_q4_weights, prepare_q4_wei
                            stem_pool_eligible, stem_pool_nchw_eligible, w1d_q4_eligible, winograd43_eligible, winograd_q4_eligible)
 from .conv_layouts import convt_phase_eligible as convt_q4_eligible, prepare_convt_weights as prepare_convt_q4_weights
 from .hip import DeviceArray, _f32, asarray, empty
-from .layer import (ACT_NONE, _PAD_MODES, _contig_strides, _full, _host_values, _linear_positions, _linear_weights,
-                    _ptr, _strided_map, conv_out_hw, convt_out_hw, convt_q4_call)
+from .layer import (ACT_NONE, PIXEL_SHUFFLE_AXES, _PAD_MODES, _contig_strides, _full, _host_values, _linear_positions, _linear_weights,
+                    _ptr, _strided_map, conv_out_hw, convt_out_hw, convt_q4_call, pixel_shuffle_shapes)
 from .plan import ACT_RELU, pad_q4_ok, resize_nearest_q4_ok
 
 
@@ -583,6 +583,33 @@ def ResizeAddQ4(xq, roi, k, size, resq, **para):
     return ResizeQ4(xq, roi, k, size, resq=resq, **para)
 
 
+def PixelShuffleQ4(xq, r, order="crd", inverse=False, nchw_out=False):
+    """layer.PixelShuffle on a Q4 tensor in one pass (pl_pixel_shuffle_q4_f32): r = 2, 3, 4; CRD order for any channel
+    count, DCR where the narrow side has C % 4 == 0.  `nchw_out` (shuffles only): the result is the plain NCHW tensor -- what a
+    shuffle that ends the program is compiled to, instead of a Q4 result and a from_q4 behind it.  A folded input (refold_q4)
+    raises: the shuffle moves pixels between phases."""
+    _f32(xq)
+    if not is_q4(xq):
+        raise TypeError("PixelShuffleQ4 needs a Q4 activation (planer_amd.q4.to_q4)")
+    if xq.fold is not None:
+        raise ValueError("PixelShuffleQ4: the input is folded by %s; a pixel shuffle has no folded form" % (tuple(xq.fold[:2]),))
+    r, inverse = int(r), bool(inverse)
+    if (order, inverse) not in PIXEL_SHUFFLE_AXES:
+        raise ValueError("PixelShuffleQ4: order is 'crd' or 'dcr', got %r" % (order,))
+    if nchw_out and inverse:
+        raise ValueError("PixelShuffleQ4: nchw_out goes with a shuffle only")
+    shp = pixel_shuffle_shapes(logical_shape(xq), r, order, inverse)
+    if shp is None:
+        raise ValueError("pixelshuffle: r = %s, order %r does not fit the input %s" % (r, order, logical_shape(xq)))
+    n, c, h, w = shp[1]
+    y = empty(shp[1], ctx=xq.ctx) if nchw_out else _new_q4(n, c, h, w, xq.ctx)
+    narrow = logical_shape(xq) if inverse else shp[1]
+    if y.size:
+        _lib.call("pl_pixel_shuffle_q4_f32", xq.ctx.handle, xq.ptr, y.ptr, narrow[0], narrow[1], narrow[2], narrow[3], r,
+                  0 if order == "crd" else 1, int(inverse), int(bool(nchw_out)))
+    return y
+
+
 def BatchNormQ4(xq, K, B):
     """layer.BatchNorm (layer.py:125-127) on a Q4 tensor (only reached when it could not be fused)."""
     _f32(xq, K, B)
@@ -723,7 +750,7 @@ def UpConcatQ4(aq, k, bq, mode="nearest", axis=1):
 Q4_LAYERS = {"maxpool": MaxpoolQ4, "averagepool": AveragePoolQ4, "gap": GlobalAveragePoolQ4,
              "upsample": UpSampleQ4, "batchnorm": BatchNormQ4, "relu": ReLUQ4, "leakyrelu": LeakyReLUQ4,
              "sigmoid": SigmoidQ4, "add": AddQ4, "concat": ConcatenateQ4, "clip": ClipQ4,
-             "instancenormalization": InstanceNormQ4, "pad": PadQ4, "resize": ResizeQ4}
+             "instancenormalization": InstanceNormQ4, "pad": PadQ4, "resize": ResizeQ4, "pixelshuffle": PixelShuffleQ4}
 
 
 def register(layer_map):
