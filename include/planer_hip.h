@@ -432,6 +432,16 @@ int pl_scale_shift_q4_f32(pl_ctx *ctx, const float *xq, float *yq, const float *
 #define PL_INSTNORM_Q4_CHUNK_PIXELS 2048
 int pl_instancenorm_q4_f32(pl_ctx *ctx, float *xq, const float *scale, const float *bias, const float *resq,
                            int N, int C, int HW, double eps, int act);
+/* Group normalisation of a Q4 tensor IN PLACE, as the five steps an exporter writes for it (reshape to (N, G, -1),
+ * InstanceNormalization with the G values gscale / gbias, reshape back, mul by gamma, add beta) with the tail in the
+ * write pass: x = IN_g(x) [* gamma] [+ beta] [+ resq] [relu].  gamma, beta (C values each) and resq may be null; every operation
+ * is rounded on its own, in that order.  Statistics per (image, group) in the centred form, no atomics.  The form depends on
+ * cpg = C / G and HW alone: cpg % 4 == 0 (a group is one run of cpg / 4 * HW float4s), cpg == 2 (two groups per quad) or
+ * cpg == 1 (the instance norm's geometry); runs / planes of up to PL_INSTNORM_Q4_ONE_WG_PIXELS float4s are held by one workgroup,
+ * longer ones go through chunk partials merged in chunk order.  Padding lanes of a partial last quad are written as +0.0.
+ * Any other cpg (3, 6, 10, ...) or more than 2^29 quads: PL_EUNSUPPORTED, before any launch.  C % G != 0: PL_EINVAL. */
+int pl_groupnorm_q4_f32(pl_ctx *ctx, float *xq, const float *gscale, const float *gbias, const float *gamma, const float *beta,
+                        const float *resq, int N, int C, int HW, int G, double eps, int act);
 /* Pixel-phase re-layout of a Q4 tensor.  The (N, C, H, W) activation "folded by (dh, dw)" is the Q4
  * tensor of logical shape (N*dh*dw, C, ceil(H/dh), ceil(W/dw)): image (n*dh + i)*dw + j holds at pixel (r, c) the quads of
  * x[n, :, r*dh + i, c*dw + j], and zero in all four lanes where that coordinate lies outside H x W.  A 3x3 / stride 1 conv with

@@ -172,6 +172,7 @@ SIGNATURES = {
     "pl_erf_lut_f32": [_P, _P, _P, _P, _Z],
     "pl_instancenorm_f32": [_P, _P, _P, _P, _I, _I, _I, c_double],
     "pl_instancenorm_q4_f32": [_P, _P, _P, _P, _P, _I, _I, _I, c_double, _I],
+    "pl_groupnorm_q4_f32": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, c_double, _I],
     "pl_refold_q4_f32": [_P, _P, _P] + [_I] * 8,
     "pl_pixel_shuffle_q4_f32": [_P, _P, _P] + [_I] * 8,
     "pl_scatter_rows_f32": [_P, _P, _P, _P, _P, _I, _I],

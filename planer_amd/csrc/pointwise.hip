@@ -6,6 +6,7 @@
 #include "common.h"
 #include "device_utils.h"
 #include "instnorm_q4_kernel.h"
+#include "groupnorm_q4_kernel.h"
 #include "pixel_shuffle_q4_kernel.h"
 
 namespace {
@@ -1467,3 +1468,83 @@ int pl_splitk_reduce_f32(pl_ctx *ctx, const float *ws, int splits, float *y, int
 }
 
 }  // extern "C"
+
+// Group normalisation on a Q4 tensor, in place: y = IN_g(x) [* gamma] [+ beta] [+ res] [relu] (groupnorm_q4_kernel.h).
+// The form depends on cpg = C / G and HW alone: wide (cpg % 4 == 0: a group is one run of cpg / 4 * HW float4s), pair (cpg == 2)
+// or single (cpg == 1) rows; one workgroup per row up to PL_INSTNORM_Q4_ONE_WG_PIXELS float4s, chunk statistics into a pool block +
+// merge-and-apply above.
+template <int LANES>
+static hipError_t groupnorm_q4_launch(pl_ctx *ctx, float4 *x, float4 *part, const float *gs, const float *gb, const float *gamma,
+                                      const float *beta, const float4 *res, size_t rows, int rpi, int C, int cpg, int L, int HW, int S,
+                                      float e, int tail_id) {
+    namespace gq = groupnorm_q4;
+    const dim3 block(gq::TPB);
+    const FastDiv divHW((unsigned)HW);
+    if (!part) {
+        const dim3 grid((unsigned)rows);
+        switch (tail_id) {
+        case 0: gq::groupnorm_q4_one_wg_kernel<LANES, false, false><<<grid, block, 0, ctx->stream>>>(x, gs, gb, gamma, beta, res, rpi, C, cpg, L, divHW, e); break;
+        case 1: gq::groupnorm_q4_one_wg_kernel<LANES, false, true><<<grid, block, 0, ctx->stream>>>(x, gs, gb, gamma, beta, res, rpi, C, cpg, L, divHW, e); break;
+        case 2: gq::groupnorm_q4_one_wg_kernel<LANES, true, false><<<grid, block, 0, ctx->stream>>>(x, gs, gb, gamma, beta, res, rpi, C, cpg, L, divHW, e); break;
+        default: gq::groupnorm_q4_one_wg_kernel<LANES, true, true><<<grid, block, 0, ctx->stream>>>(x, gs, gb, gamma, beta, res, rpi, C, cpg, L, divHW, e); break;
+        }
+        return hipGetLastError();
+    }
+    const int A = S < gq::APPLY_MAX_WG_PER_ROW ? S : gq::APPLY_MAX_WG_PER_ROW;
+    gq::groupnorm_q4_stats_kernel<LANES><<<dim3((unsigned)(rows * S)), block, 0, ctx->stream>>>(x, part, S, L);
+    hipError_t le = hipGetLastError();
+    if (le != hipSuccess) return le;
+    const dim3 grid((unsigned)(rows * A));
+    switch (tail_id) {
+    case 0: gq::groupnorm_q4_apply_kernel<LANES, false, false><<<grid, block, 0, ctx->stream>>>(x, part, gs, gb, gamma, beta, res, rpi, C, cpg, L, divHW, S, A, e); break;
+    case 1: gq::groupnorm_q4_apply_kernel<LANES, false, true><<<grid, block, 0, ctx->stream>>>(x, part, gs, gb, gamma, beta, res, rpi, C, cpg, L, divHW, S, A, e); break;
+    case 2: gq::groupnorm_q4_apply_kernel<LANES, true, false><<<grid, block, 0, ctx->stream>>>(x, part, gs, gb, gamma, beta, res, rpi, C, cpg, L, divHW, S, A, e); break;
+    default: gq::groupnorm_q4_apply_kernel<LANES, true, true><<<grid, block, 0, ctx->stream>>>(x, part, gs, gb, gamma, beta, res, rpi, C, cpg, L, divHW, S, A, e); break;
+    }
+    return hipGetLastError();
+}
+
+extern "C" int pl_groupnorm_q4_f32(pl_ctx *ctx, float *xq, const float *gscale, const float *gbias, const float *gamma, const float *beta,
+                                   const float *resq, int N, int C, int HW, int G, double eps, int act) {
+    PL_REQUIRE(ctx && xq && gscale && gbias, PL_EINVAL, "pl_groupnorm_q4_f32: null argument");
+    PL_REQUIRE(N >= 0 && C > 0 && HW >= 0 && G > 0, PL_EINVAL, "pl_groupnorm_q4_f32: bad shape");
+    PL_REQUIRE(C % G == 0, PL_EINVAL, "pl_groupnorm_q4_f32: the group count must divide the channel count");
+    PL_REQUIRE(act == PL_ACT_NONE || act == PL_ACT_RELU, PL_EINVAL, "pl_groupnorm_q4_f32: act must be 0 (none) or 1 (relu)");
+    PL_REQUIRE(aligned16(xq) && aligned16(resq), PL_EINVAL, "pl_groupnorm_q4_f32: Q4 tensors must be 16-byte aligned");
+    const int cpg = C / G;
+    PL_REQUIRE(cpg % 4 == 0 || cpg == 2 || cpg == 1, PL_EUNSUPPORTED,
+               "pl_groupnorm_q4_f32: %d channels per group split a channel quad unevenly (1, 2 or a multiple of 4 have a Q4 form)", cpg);
+    const int Cq = (C + 3) / 4;
+    const size_t total = (size_t)N * Cq * (size_t)HW;
+    if (!total) return PL_OK;
+    PL_REQUIRE(total <= (1ull << 29), PL_EUNSUPPORTED, "groupnorm: tensor too large");
+    CtxGuard g(ctx);
+    const int lanes = cpg % 4 == 0 ? 4 : cpg;
+    const int rpi = lanes == 4 ? G : Cq;                                  // rows per image
+    const size_t rows = (size_t)N * rpi;
+    const int L = (int)(total / rows);                                    // float4s per row: cpg / 4 * HW, or HW
+    const int tail_id = (resq ? 2 : 0) | (act == PL_ACT_RELU ? 1 : 0);
+    const bool chunked = L > PL_INSTNORM_Q4_ONE_WG_PIXELS;
+    // rows * S <= total / CHUNK + rows < 2^30: one-dimensional grids
+    const int S = chunked ? (L + PL_INSTNORM_Q4_CHUNK_PIXELS - 1) / PL_INSTNORM_Q4_CHUNK_PIXELS : 1;
+    float4 *part = nullptr;
+    if (chunked) {
+        int rc = pl_alloc(ctx, rows * S * 2 * sizeof(float4), (void **)&part);
+        if (rc != PL_OK) return rc;
+    }
+    float4 *x = (float4 *)xq;
+    const float4 *res = (const float4 *)resq;
+    const float e = (float)eps;
+    hipError_t le;
+    if (lanes == 4) le = groupnorm_q4_launch<4>(ctx, x, part, gscale, gbias, gamma, beta, res, rows, rpi, C, cpg, L, HW, S, e, tail_id);
+    else if (lanes == 2) le = groupnorm_q4_launch<2>(ctx, x, part, gscale, gbias, gamma, beta, res, rows, rpi, C, cpg, L, HW, S, e, tail_id);
+    else le = groupnorm_q4_launch<1>(ctx, x, part, gscale, gbias, gamma, beta, res, rows, rpi, C, cpg, L, HW, S, e, tail_id);
+    if (part) pl_free(ctx, part);  // stream-ordered: safe to recycle after the enqueue
+    if (le != hipSuccess) {
+        pl_set_error("pl_groupnorm_q4_f32: kernel launch -> %s", hipGetErrorString(le));
+        return PL_EHIP;
+    }
+    ctx->last_plan = std::string("groupnorm-q4 ") + (lanes == 4 ? "wide" : lanes == 2 ? "pair" : "single") +
+                     (chunked ? " chunks=" + std::to_string(S) : std::string(" one-wg"));
+    return PL_OK;
+}

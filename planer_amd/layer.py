@@ -606,6 +606,23 @@ def PixelShuffle(x, r, order="crd", inverse=False):
     return Transpose(x.reshape(shp[0]), PIXEL_SHUFFLE_AXES[(order, bool(inverse))]).reshape(shp[1])
 
 
+def GroupNorm(x, s, bias, gamma=None, beta=None, groups=1, epsilon=1e-5):
+    """The plan-internal kind `groupnorm` (plan.fuse_groupnorm): group normalisation of an NCHW tensor as EXACTLY the five steps it
+    replaces -- Reshape to (N, G, -1), InstanceNormalization with the G values s / bias (pl_instancenorm_f32, in place on x like the
+    original), Reshape back, Mul by gamma, Add beta (the broadcast binaries on the inits as they are shaped; either may be absent) -- so a plan whose input never
+    becomes channel-quad runs the kernels it ran before.  q4.GroupNormQ4 is the one-launch form."""
+    _f32(x, s, bias, gamma, beta)
+    groups = int(groups)
+    if x.ndim != 4 or groups < 1 or x.shape[1] % groups:
+        raise ValueError("groupnorm: a 4-D activation whose channels %d groups divide, got %s" % (groups, x.shape))
+    y = InstanceNormalization(x.reshape((x.shape[0], groups, -1)), s, bias, epsilon=epsilon).reshape(x.shape)
+    if gamma is not None:
+        y = Mul(y, gamma)
+    if beta is not None:
+        y = Add(y, beta)
+    return y
+
+
 def Squeeze(x, axes=[0]):
     """layer.Squeeze (layer.py:133-134): np.squeeze(x, axis=axes[0])"""
     a = axes[0] + x.ndim if axes[0] < 0 else axes[0]
@@ -1206,7 +1223,7 @@ layer_map = {"dense": Dense, "conv": Conv2d, "relu": ReLU, "leakyrelu": LeakyReL
              "erf": Erf, "instancenormalization": InstanceNormalization,
              "scatternd": Scatternd, "nonzero": NonZero, "topk": TopK, "lstm": LSTM,
              # plan-compiler internal
-             "conv_fused": ConvFused, "convt_fused": ConvTransposeFused, "pixelshuffle": PixelShuffle}
+             "conv_fused": ConvFused, "convt_fused": ConvTransposeFused, "pixelshuffle": PixelShuffle, "groupnorm": GroupNorm}
 # integer shape arithmetic: the same kinds, evaluated on host mirrors when no activation is involved
 for _k, _ref in (("add", lambda a, b: a + b), ("sub", lambda a, b: a - b), ("mul", lambda a, b: a * b),
                  ("div", lambda a, b: a / b), ("concat", lambda *xs, axis=0: numpy.concatenate(xs, axis=axis)),

@@ -30,8 +30,8 @@ from . import q4 as _q4
 from .conv_layouts import (CONV_KINDS, CONVT_KINDS, DIRECT_Q4, IGEMM_NCHW, LAYOUTS, ROWPACK_Q4, STEM_POOL, STEM_POOL_NCHW, WINO4_Q4,
                            WINO43_Q4, choose, suffix)
 from .layer import layer_map, wrap
-from .plan import (assign_layouts, chain_winograd, fold_dilated, fuse_conv1x1_wino_in, fuse_flow, fuse_instnorm_q4, fuse_linear_add,
-                   fuse_pixel_shuffle, pair_sibling_convs, pixel_shuffle_enabled)
+from .plan import (assign_layouts, chain_winograd, fold_dilated, fuse_conv1x1_wino_in, fuse_flow, fuse_groupnorm, fuse_instnorm_q4,
+                   fuse_linear_add, fuse_pixel_shuffle, groupnorm_enabled, pair_sibling_convs, pixel_shuffle_enabled)
 
 _q4.register(layer_map)
 
@@ -347,6 +347,7 @@ class Net:
         self.instnorm_fused = 0      # add / relu steps the last plan runs inside a channel-quad instance norm
         self.linear_adds_fused = 0   # add steps the last plan runs inside a channel-quad linear upsample / resize
         self.pixel_shuffles_fused = 0  # reshape / transpose / reshape trios the last plan runs as one pixelshuffle step
+        self.groupnorms_fused = 0    # reshape / instance norm / reshape / mul / add runs the last plan runs as one groupnorm step
         # force_algo: w_layout (int) every eligible 3x3/s1/p1 conv must use, or None = pick by timing
         fa = os.environ.get("PLANER_HIP_CONV_ALGO")
         self.force_algo = int(fa) if fa else None
@@ -464,9 +465,10 @@ class Net:
                                    "extents": list(ctx_.last_conv_extents()), "x": list(xshape)})
                     if getattr(args[0], "fold", None) is not None:       # a conv on a folded tensor: `x` is the folded shape
                         record[-1]["fold"] = list(args[0].fold)
-                if record is not None and obj.name == "instancenormalization_q4":
-                    # the form taken ("instnorm-q4 one-wg" / "instnorm-q4 chunks=S"), as the entry point left it
-                    record.append({"layer": name, "kind": obj.name, "w_layout": None, "algo": "instnorm-q4",
+                if record is not None and obj.name in ("instancenormalization_q4", "groupnorm_q4"):
+                    # the form taken ("instnorm-q4 one-wg" / "instnorm-q4 chunks=S", "groupnorm-q4 wide one-wg" ...), as the entry
+                    # point left it
+                    record.append({"layer": name, "kind": obj.name, "w_layout": None, "algo": "instnorm-q4" if obj.name == "instancenormalization_q4" else "groupnorm-q4",
                                    "plan": args[0].ctx.last_conv_plan() if args[0].size else "", "extents": [],
                                    "x": list(_q4.logical_shape(args[0]))})
                 del args
@@ -520,6 +522,10 @@ class Net:
             if pixel_shuffle_enabled():
                 # reshape -> transpose -> reshape that is a pixel shuffle / unshuffle as one step, which has a one-pass Q4 kernel
                 body, flow, self.pixel_shuffles_fused = fuse_pixel_shuffle(body, flow, shapes)
+            self.groupnorms_fused = 0
+            if groupnorm_enabled():
+                # reshape -> instancenormalization -> reshape -> [mul] -> [add] that is a group norm as one step, which has a Q4 kernel
+                body, flow, self.groupnorms_fused = fuse_groupnorm(body, flow, shapes, self.inits)
             wmap = dict(zip(self.inits, self.weights))
             body, flow, _ = assign_layouts(body, flow, self.inits, shapes, force=self.use_q4 == "force",
                                            values=lambda key: wmap[key].host if key in wmap else None)

@@ -131,7 +131,7 @@ def fuse_flow(layers, flow, init_names, shapes):
 # downstream of a conv -- and everything else reads NCHW, with a conversion step inserted where a
 # value is needed in the layout it was not produced in (converted copies are cached per value).
 Q4_POINTWISE = ("maxpool", "averagepool", "gap", "upsample", "batchnorm", "relu", "leakyrelu", "sigmoid",
-                "add", "concat", "clip", "instancenormalization", "pad", "resize", "pixelshuffle")
+                "add", "concat", "clip", "instancenormalization", "pad", "resize", "pixelshuffle", "groupnorm")
 # the kinds of instance-normalised generators (fast-neural-style, CycleGAN ...): PLANER_HIP_INSTNORM_Q4=0 takes them out again,
 # which gives the program of a compiler without them
 INSTNORM_Q4_KINDS = ("instancenormalization", "pad")
@@ -188,6 +188,16 @@ def pad_q4_ok(c, pads, constant_value=0, mode="constant", **_):
     return mode != "constant" or c % 4 == 0 or float(constant_value) == 0.0
 
 
+def groupnorm_q4_ok(c, groups):
+    """GroupNormQ4 takes the channels-per-group counts that do not split a channel quad unevenly: a multiple of 4 (a group is whole
+    quad planes), 2 (two groups per quad) or 1 (the instance norm's geometry).  3, 6, 10 ... have no channel-quad form."""
+    c, groups = int(c), int(groups)
+    if groups < 1 or c < 1 or c % groups:
+        return False
+    cpg = c // groups
+    return cpg % 4 == 0 or cpg in (1, 2)
+
+
 def _linear_factors_ok(fh, fw, h, w):
     """The geometries the linear channel-quad kernels take (q4._upsample_linear_q4): integer factors other than 1 x 1 with at
     most 64 weights, or fractional ones on a map of at least 2 x 2 pixels."""
@@ -233,6 +243,9 @@ def _q4_pointwise_ok(kind, srcs, para, inits, shapes, values=None):
     c = shapes[acts[0]][1]
     if kind == "instancenormalization":     # constant scale and bias
         return len(srcs) == 3 and len(acts) == 1 and acts[0] == srcs[0] and srcs[1] in inits and srcs[2] in inits
+    if kind == "groupnorm":                 # constant scale, bias, gamma and beta; a group count that keeps quads whole
+        return (len(srcs) == 5 and acts == [srcs[0]] and all(k in inits for k in srcs[1:3])
+                and all(k == "None" or k in inits for k in srcs[3:5]) and groupnorm_q4_ok(c, para.get("groups", 0)))
     if kind == "pad":                       # constant pads (and value): their numbers decide, so the caller must supply them
         if values is None or len(srcs) not in (2, 3) or acts != [srcs[0]] or srcs[1] not in inits:
             return False
@@ -397,8 +410,8 @@ def assign_layouts(body, flow, init_names, shapes, force=False, values=None):
         if not as_q4:
             args = [need(k, False) for k in srcs]
             new_kind = kind
-        if kind in ("relu", "clip", "instancenormalization"):   # in place (layer.py:46, 217-226, 250-251): cached copies of
-            drop_copies(srcs[0])                                # the input go stale
+        if kind in ("relu", "clip", "instancenormalization", "groupnorm"):   # in place (layer.py:46, 217-226, 250-251): cached
+            drop_copies(srcs[0])                                             # copies of the input go stale
         out_key = dst
         produces_q4 = as_q4 and kind != "gap" and not (kind == "pixelshuffle" and para.get("nchw_out"))
         if produces_q4 and i == last:
@@ -434,11 +447,16 @@ def assign_layouts(body, flow, init_names, shapes, force=False, values=None):
     return out_body, out_flow, nq4
 
 
-# ---- instance norm tails ------------------------------------------------------------------------------
+# ---- instance norm and group norm tails ------------------------------------------------------------------
+# the channel-quad norms whose kernels take [+ res] [relu] in their write pass -> the number of sources of an unfused step
+_NORM_Q4_SRCS = {"instancenormalization_q4": 3, "groupnorm_q4": 5}
+
+
 def fuse_instnorm_q4(body, flow, shapes):
     """-> (body', flow', number of absorbed steps).  Runs on assign_layouts' program (one layer per step).  Folds
     instancenormalization_q4 -> [add_q4 with an operand of the same shape] -> [relu_q4]  into ONE instancenormalization_q4 step
-    with `res` and `act` set (q4.InstanceNormQ4: the tail goes into the kernel's write pass).  The order is fixed -- residual,
+    with `res` and `act` set (q4.InstanceNormQ4: the tail goes into the kernel's write pass), and groupnorm_q4 likewise
+    (q4.GroupNormQ4: `res` behind gamma and beta).  The order is fixed -- residual,
     then activation -- so a relu that comes first ends the chain and the add behind it stays a step of its own.  As in
     fuse_flow a link is absorbed only when the tensor between has one reader and one writer, and the fused step sits where the
     last link was.  The norm works in place, so it is only moved when nothing else ever reads the tensor it rewrites."""
@@ -459,7 +477,7 @@ def fuse_instnorm_q4(body, flow, shapes):
     consumed, fused_at, nfused = set(), {}, 0
     for i, (srcs, name, dst) in enumerate(steps):
         _, kind, para = kinds[name]
-        if kind != "instancenormalization_q4" or i in consumed or not isinstance(dst, str) or len(srcs) != 3:
+        if _NORM_Q4_SRCS.get(kind) != len(srcs) or i in consumed or not isinstance(dst, str):
             continue
         if readers.get(srcs[0]) != [i] or writers.get(srcs[0], 0) > 1:
             continue
@@ -488,13 +506,13 @@ def fuse_instnorm_q4(body, flow, shapes):
             cur = jdst
         if len(chain) > 1:
             consumed.update(chain)
-            fused_at[chain[-1]] = (srcs, name, para, res, act, cur)
+            fused_at[chain[-1]] = (srcs, name, kind, para, res, act, cur)
             nfused += len(chain) - 1
     out = []
     for i, (srcs, name, dst) in enumerate(steps):
         if i in fused_at:
-            isrcs, iname, para, res, act, cur = fused_at[i]
-            out.append((isrcs + [res], iname + "+", "instancenormalization_q4", dict(para, act=act), cur))
+            isrcs, iname, ikind, para, res, act, cur = fused_at[i]
+            out.append((isrcs + [res], iname + "+", ikind, dict(para, act=act), cur))
         elif i not in consumed:
             out.append((srcs, name, kinds[name][1], kinds[name][2], dst))
     out_body, seen = [], set()
@@ -662,6 +680,118 @@ def fuse_pixel_shuffle(body, flow, shapes):
     return out_body, out_flow, len(fused_at)
 
 
+# ---- group normalisation -----------------------------------------------------------------------------------------------------------
+# planer has no group-norm kind (the operator table is the reference's): below opset 18 an exporter writes one as reshape (N, G, -1)
+# -> instancenormalization (G scales / biases, ones and zeros) -> reshape back -> mul gamma (C, 1, 1) -> add beta (C, 1, 1).  reshape
+# and mul have no channel-quad kind and add only for equal shapes, so between two convs the five steps ran NCHW between a from_q4 and
+# a to_q4.  fuse_groupnorm names them (`groupnorm`, layer.GroupNorm: the same five steps) so that assign_layouts can give the norm
+# its one-launch Q4 kernel (q4.GroupNormQ4).  PLANER_HIP_GROUPNORM_Q4=0 skips the pass: the program of a compiler
+# without it.
+def groupnorm_enabled():
+    return os.environ.get("PLANER_HIP_GROUPNORM_Q4", "1") != "0"
+
+
+def _per_channel(shape, c):
+    """An operand that squeezes to c values on the channel axis of an NCHW tensor: (c, 1, 1) or (1, c, 1, 1)."""
+    return shape is not None and tuple(int(v) for v in shape) in ((c, 1, 1), (1, c, 1, 1))
+
+
+def fuse_groupnorm(body, flow, shapes, init_names=None):
+    """-> (body', flow', number of norms).  Runs on fuse_flow's program, in front of assign_layouts.  A `reshape` of a 4-D
+    (N, C, H, W) tensor x to (N, G, *rest) with G | C, an `instancenormalization` of that with constant scale and bias of G values, a
+    `reshape` back to exactly x's shape, then optionally a `mul` and optionally an `add` whose other operand -- in either position
+    -- is a constant of C values shaped (C, 1, 1) or (1, C, 1, 1), become ONE `groupnorm` step {groups, epsilon} with sources
+    [x, scale, bias, gamma | "None", beta | "None"].  Matched on the traced `shapes`, so a shape operand computed by shape-domain
+    steps is as good as a constant one.  Every intermediate has one writer and one reader; the norm rewrites x in place, so x must
+    have no reader but the first reshape, and nothing may write it between the first step and the last.  A constant is a key no
+    step writes (and one of `init_names` where they are given).  The step sits where the last link was; steps that only fed the
+    reshapes' shape operands stay where they are."""
+    kinds = {name: (kind, para) for name, kind, para in body}
+    steps = expand_steps(flow)
+    inits = None if init_names is None else set(init_names)
+    readers, writers = {}, {}
+    for i, (srcs, _, dst) in enumerate(steps):
+        for k in set(srcs):
+            readers.setdefault(k, []).append(i)
+        for k in _as_list(dst):
+            writers[k] = writers.get(k, 0) + 1
+
+    def const(key):
+        return key != "None" and key not in writers and (inits is None or key in inits)
+
+    def only_reader(i, dst):
+        """The one step that reads `dst` (written once, by step i), where it comes later and writes one tensor."""
+        r = readers.get(dst, [])
+        if not isinstance(dst, str) or len(r) != 1 or writers.get(dst, 0) != 1 or r[0] <= i or r[0] in consumed:
+            return None
+        return r[0] if isinstance(steps[r[0]][2], str) else None
+
+    def channel_operand(j, cur, kind, c):
+        """The constant per-channel operand of step j where that is a `kind` of `cur` and such a constant, else None."""
+        if j is None:
+            return None
+        jsrcs, jname, _ = steps[j]
+        if kinds[jname][0] != kind or len(jsrcs) != 2 or jsrcs.count(cur) != 1:
+            return None
+        other = jsrcs[1 - jsrcs.index(cur)]
+        return other if const(other) and _per_channel(shapes.get(other), c) else None
+
+    consumed, fused_at, names = set(), {}, {b[0] for b in body}
+    for i, (srcs, name, dst) in enumerate(steps):
+        if kinds[name][0] != "reshape" or i in consumed or len(srcs) != 2:
+            continue
+        x = srcs[0]
+        sx, sm = shapes.get(x), shapes.get(dst)
+        if sx is None or sm is None or len(sx) != 4 or len(sm) < 3 or readers.get(x) != [i] or writers.get(x, 0) > 1:
+            continue
+        n, c = int(sx[0]), int(sx[1])
+        g = int(sm[1])
+        if int(sm[0]) != n or g < 1 or c % g:
+            continue
+        j = only_reader(i, dst)
+        if j is None or kinds[steps[j][1]][0] != "instancenormalization":
+            continue
+        nsrcs, nname, ndst = steps[j]
+        if (len(nsrcs) != 3 or nsrcs[0] != dst or not all(const(k) and tuple(shapes.get(k) or ()) == (g,) for k in nsrcs[1:])):
+            continue
+        k = only_reader(j, ndst)
+        if (k is None or kinds[steps[k][1]][0] != "reshape" or len(steps[k][0]) != 2 or steps[k][0][0] != ndst
+                or tuple(shapes.get(steps[k][2]) or ()) != tuple(sx)):
+            continue
+        chain, cur, gamma, beta = [i, j, k], steps[k][2], "None", "None"
+        m = only_reader(k, cur)
+        got = channel_operand(m, cur, "mul", c)
+        if got is not None:
+            chain, cur, gamma = chain + [m], steps[m][2], got
+            m = only_reader(m, cur)
+        got = channel_operand(m, cur, "add", c)
+        if got is not None:
+            chain, cur, beta = chain + [m], steps[m][2], got
+        if any(x in _as_list(steps[t][2]) for t in range(i + 1, chain[-1] + 1) if t not in chain):
+            continue
+        new = nname + "+"
+        while new in names:                      # a norm layer that serves several steps: one groupnorm layer per pattern
+            new += "+"
+        names.add(new)
+        consumed.update(chain)
+        para = {"groups": g, "epsilon": kinds[nname][1].get("epsilon", 1e-5)}
+        fused_at[chain[-1]] = ([x, nsrcs[1], nsrcs[2], gamma, beta], new, para, cur)
+    if not fused_at:
+        return [list(b) for b in body], [[list(s) if isinstance(s, (list, tuple)) else s, n, d] for s, n, d in flow], 0
+    out_body, out_flow, seen = [], [], set()
+    for i, (srcs, name, dst) in enumerate(steps):
+        if i in fused_at:
+            srcs, name, para, dst = fused_at[i]
+            out_body.append([name, "groupnorm", para])
+        elif i in consumed:
+            continue
+        elif name not in seen:
+            seen.add(name)
+            out_body.append([name] + list(kinds[name]))
+        out_flow.append([list(srcs), [name], dst])
+    return out_body, out_flow, len(fused_at)
+
+
 # ---- Winograd chaining ------------------------------------------------------------------------------
 # A conv_q4 step that runs F(4x4,3x3) (w_layout 7) is three kernels: input transform (x -> V), the 36
 # grouped GEMMs (V, U -> M) and output transform + fused tail (M -> y).  When the y of one such conv
@@ -785,7 +915,8 @@ def fuse_conv1x1_wino_in(body, flow, kshape=lambda key: None, small=lambda key: 
 # the stride-2 3x3 conv and the 1x1 stride-2 projection -- both run in ONE launch (q4.ConvQ4Pair,
 # csrc/conv_q4_kernel.h conv_q4_pair_kernel).  The second conv moves up to the first one's place; it only needs the
 # shared input and constants, so that is legal unless something rewrites the input in place in between.
-_IN_PLACE = ("relu", "relu_q4", "clip", "clip_q4", "erf", "instancenormalization", "instancenormalization_q4")
+_IN_PLACE = ("relu", "relu_q4", "clip", "clip_q4", "erf", "instancenormalization", "instancenormalization_q4", "groupnorm",
+             "groupnorm_q4")
 
 
 def pair_sibling_convs(body, flow, kshape=lambda key: None):

@@ -26,7 +26,7 @@ from .conv_layouts import convt_phase_eligible as convt_q4_eligible, prepare_con
 from .hip import DeviceArray, _f32, asarray, empty
 from .layer import (ACT_NONE, PIXEL_SHUFFLE_AXES, _PAD_MODES, _contig_strides, _full, _host_values, _linear_positions, _linear_weights,
                     _ptr, _strided_map, conv_out_hw, convt_out_hw, convt_q4_call, pixel_shuffle_shapes)
-from .plan import ACT_RELU, pad_q4_ok, resize_nearest_q4_ok
+from .plan import ACT_RELU, groupnorm_q4_ok, pad_q4_ok, resize_nearest_q4_ok
 
 
 def is_q4(a):
@@ -659,6 +659,37 @@ def InstanceNormQ4(xq, s, bias, resq=None, epsilon=1e-5, act=ACT_NONE):
     return xq
 
 
+def GroupNormQ4(xq, s, bias, gamma=None, beta=None, resq=None, groups=None, epsilon=1e-5, act=ACT_NONE):
+    """layer.GroupNorm -- reshape (N, G, -1), InstanceNormalization with the G values s / bias, reshape back, [mul gamma], [add
+    beta] -- on a Q4 tensor, IN PLACE like the instance norm inside it, with the tail the plan compiler folds in
+    (plan.fuse_instnorm_q4): xq = GN(xq) [+ resq] [relu].  One launch where the group's run (C / G a multiple of 4) or the plane
+    (C / G of 2 or 1) has up to _lib.INSTNORM_Q4_ONE_WG_PIXELS float4s, chunk statistics + merge-and-apply above
+    (pl_groupnorm_q4_f32).  Other C / G have no channel-quad form (groupnorm_q4_ok) and raise."""
+    _f32(xq, s, bias, gamma, beta, resq)
+    if not is_q4(xq) or (resq is not None and not is_q4(resq)):
+        raise TypeError("GroupNormQ4 needs Q4 activations (planer_amd.q4.to_q4)")
+    n, c, h, w = logical_shape(xq)
+    if groups is None or int(groups) < 1 or c % int(groups):
+        raise ValueError("groupnorm: %r groups do not divide %d channels" % (groups, c))
+    groups = int(groups)
+    if s.size != groups or bias.size != groups:
+        raise ValueError("groupnorm: one scale / bias value per group")
+    if any(p is not None and p.size != c for p in (gamma, beta)):
+        raise ValueError("groupnorm: one gamma / beta value per channel")
+    if resq is not None and (resq.shape != xq.shape or resq.chan != c):
+        raise ValueError("fused residual shape %s != groupnorm input %s" % (resq.shape, xq.shape))
+    if int(act) not in (ACT_NONE, ACT_RELU):
+        raise ValueError("GroupNormQ4: act is 0 (none) or 1 (relu)")
+    if not groupnorm_q4_ok(c, groups):
+        raise NotImplementedError("GroupNormQ4: %d channels per group split a channel quad unevenly; 1, 2 or a multiple of 4 have a "
+                                  "channel-quad form" % (c // groups))
+    if h * w == 0 or xq.size == 0:                      # numpy leaves an empty x as it is
+        return xq
+    _lib.call("pl_groupnorm_q4_f32", xq.ctx.handle, xq.ptr, s.ptr, bias.ptr, _ptr(gamma), _ptr(beta), _ptr(resq), n, c, h * w, groups,
+              float(epsilon), int(act))
+    return xq
+
+
 def PadQ4(xq, pads, constant_value=0, mode="constant"):
     """layer.Pad (layer.py:241-245) of the pixel axes of a Q4 tensor: the strided-map kernel on the 5-D view (N, quads, H, W, 4),
     whose last axis -- the four lanes of a pixel -- is copied as it is.  Only scheduled where plan.pad_q4_ok holds: no padding of
@@ -750,7 +781,8 @@ def UpConcatQ4(aq, k, bq, mode="nearest", axis=1):
 Q4_LAYERS = {"maxpool": MaxpoolQ4, "averagepool": AveragePoolQ4, "gap": GlobalAveragePoolQ4,
              "upsample": UpSampleQ4, "batchnorm": BatchNormQ4, "relu": ReLUQ4, "leakyrelu": LeakyReLUQ4,
              "sigmoid": SigmoidQ4, "add": AddQ4, "concat": ConcatenateQ4, "clip": ClipQ4,
-             "instancenormalization": InstanceNormQ4, "pad": PadQ4, "resize": ResizeQ4, "pixelshuffle": PixelShuffleQ4}
+             "instancenormalization": InstanceNormQ4, "pad": PadQ4, "resize": ResizeQ4, "pixelshuffle": PixelShuffleQ4,
+             "groupnorm": GroupNormQ4}
 
 
 def register(layer_map):
