@@ -27,11 +27,9 @@ from . import _lib
 from . import hip
 from .hip import DeviceArray
 from . import q4 as _q4
-from .conv_layouts import (CONV_KINDS, CONVT_KINDS, DIRECT_Q4, IGEMM_NCHW, LAYOUTS, ROWPACK_Q4, STEM_POOL, STEM_POOL_NCHW, WINO4_Q4,
-                           WINO43_Q4, choose, suffix)
+from .conv_layouts import DIRECT_Q4, IGEMM_NCHW, LAYOUTS, STEM_POOL, STEM_POOL_NCHW, WINO4_Q4, WINO43_Q4, suffix
 from .layer import layer_map, wrap
-from .plan import (assign_layouts, chain_winograd, fold_dilated, fuse_conv1x1_wino_in, fuse_flow, fuse_groupnorm, fuse_instnorm_q4,
-                   fuse_linear_add, fuse_pixel_shuffle, groupnorm_enabled, pair_sibling_convs, pixel_shuffle_enabled)
+from .plan import compile_front, fuse_upsample_concat, lower
 
 _q4.register(layer_map)
 
@@ -512,165 +510,84 @@ class Net:
 
     # ---- plan compiler -----------------------------------------------------------------
     def _fuse(self, shapes, fuse=True):
-        """Plan program: fused epilogues + tap-major filter copies for the fast conv kernel."""
-        if fuse:
-            body, flow, nfused = fuse_flow(self.layer, self.flow, self.inits, shapes)
-        else:
-            body, flow, nfused = [list(b) for b in self.layer], [list(f) for f in self.flow], 0
-        if self.use_q4:
-            self.pixel_shuffles_fused = 0
-            if pixel_shuffle_enabled():
-                # reshape -> transpose -> reshape that is a pixel shuffle / unshuffle as one step, which has a one-pass Q4 kernel
-                body, flow, self.pixel_shuffles_fused = fuse_pixel_shuffle(body, flow, shapes)
-            self.groupnorms_fused = 0
-            if groupnorm_enabled():
-                # reshape -> instancenormalization -> reshape -> [mul] -> [add] that is a group norm as one step, which has a Q4 kernel
-                body, flow, self.groupnorms_fused = fuse_groupnorm(body, flow, shapes, self.inits)
-            wmap = dict(zip(self.inits, self.weights))
-            body, flow, _ = assign_layouts(body, flow, self.inits, shapes, force=self.use_q4 == "force",
+        """Plan program: fused epilogues + tap-major filter copies for the fast conv kernel.  The passes and their order are
+        plan.compile_front's and plan.lower's; this reads the switches, answers what needs the device or the weights, and keeps
+        the counters."""
+        wmap = dict(zip(self.inits, self.weights))
+        worth = None
+        if self.fold_dilated:
+            worth = (lambda xs, ks, para: True) if self.fold_dilated == "force" else self._fold_worth
+        body, flow, counts = compile_front(self.layer, self.flow, self.inits, shapes, fuse=fuse, q4=self.use_q4, worth=worth,
                                            values=lambda key: wmap[key].host if key in wmap else None)
-            # instancenormalization_q4 -> [add_q4] -> [relu_q4] as one step: the tail goes into the norm's write pass
-            body, flow, self.instnorm_fused = fuse_instnorm_q4(body, flow, shapes)
-            # linear upsample_q4 / resize_q4 -> add_q4 as one step: the add goes into the upsample's write pass
-            body, flow, self.linear_adds_fused = fuse_linear_add(body, flow, shapes)
-            if self.fold_dilated:
-                worth = (lambda xs, ks, para: True) if self.fold_dilated == "force" else self._fold_worth
-                body, flow, regions = fold_dilated(body, flow, shapes, worth)
-                self.dilated_folds = sum(len(r["heads"]) for r in regions)
-                refold_layers = {b[0] for b in body if b[1] == "refold_q4"}
-                self.refolds = sum(1 for f in flow if f[1][0] in refold_layers)
+        if self.use_q4:
+            self.pixel_shuffles_fused = counts.get("fuse_pixel_shuffle", 0)
+            self.groupnorms_fused = counts.get("fuse_groupnorm", 0)
+            self.instnorm_fused, self.linear_adds_fused = counts["fuse_instnorm_q4"], counts["fuse_linear_add"]
+        if "fold_dilated" in counts:
+            self.dilated_folds = sum(len(r["heads"]) for r in counts["fold_dilated"])
+            refold_layers = {b[0] for b in body if b[1] == "refold_q4"}
+            self.refolds = sum(1 for f in flow if f[1][0] in refold_layers)
         if os.environ.get("PLANER_HIP_TAPMAJOR", "1") != "0":
             body, flow = self._prepare_filters(body, flow, shapes)
-        return _Program(body, flow), nfused
+        return _Program(body, flow), counts.get("fuse_flow", 0)
 
     def _prepare_filters(self, body, flow, shapes):
         """Give every eligible conv a prepared copy of its (constant) filter: tap-major for the
         fast implicit-GEMM kernel, or Winograd-domain where that measures faster for this shape."""
         wmap = dict(zip(self.inits, self.weights))
-        kinds = {b[0]: b for b in body}
-        out_body = {b[0]: list(b) for b in body}
-        out_flow = []
-        for src, names, dst in flow:
-            name = names[0] if isinstance(names, list) else names
-            _, kind, para = kinds[name]
-            srcs = list(src) if isinstance(src, list) else [src]
-            K = wmap[srcs[1]] if kind == "conv_q4" else wmap.get(srcs[1]) if len(srcs) >= 2 else None
-            if K is not None and (kind not in CONV_KINDS or K.dtype == numpy.float32):
-                # (an NCHW conv looks its input up by key: one on a converted copy, key@nchw, is not timed)
-                xs = shapes.get(srcs[0].split("@")[0] if kind == "conv_q4" else srcs[0])
-                got = choose(kind, K.shape, para, xs, para.get("rowpack"),
-                             lambda cands: self._pick_conv_algo(cands, K, srcs, para, shapes, q4=kind == "conv_q4"))
-                if got is not None:
-                    lay, key = got[0], srcs[1] + got[1]
-                    if key not in self._extra:
-                        self._extra[key] = LAYOUTS[lay].prepare(K, **para)
-                    srcs[1] = key
-                    new_kind = kind if kind in ("conv_q4", "convt_q4") else "convt_fused" if kind in CONVT_KINDS else "conv_fused"
-                    out_body[name] = [name, new_kind, dict(para, w_layout=lay)]
-            out_flow.append([srcs, [name], dst])
-        # the row-packed stem conv whose only reader is maxpool(3x3 / s2 / p1): one kernel that writes the pooled tensor only
-        # (csrc/conv_stem_pool_kernel.h); PLANER_HIP_STEM_POOL=0 keeps the two kernels
-        if os.environ.get("PLANER_HIP_STEM_POOL", "1") != "0":
-            out_flow = self._fuse_stem_pool(out_body, out_flow, shapes)
-        out_flow = self._fuse_upsample_concat(out_body, out_flow)
-        used = {n for _, names, _ in out_flow for n in names}
-        out_list = [out_body[b[0]] for b in body if b[0] in used]
-        # two direct convs on one tensor (a resolution-changing ResNet block) -> one launch; PLANER_HIP_PAIR=0 turns it off
-        if os.environ.get("PLANER_HIP_PAIR", "1") != "0":
-            out_list, out_flow, self.conv_pairs = pair_sibling_convs(
-                out_list, out_flow, lambda key: shapes.get(key.split("@")[0]))
-        # F(4x4,3x3) convs as explicit stages, consecutive ones sharing a transform kernel (plan.chain_winograd);
-        # PLANER_HIP_WINO_CHAIN: "1" chain (default), "stages" explicit stages without chaining, "0" one call per conv
-        mode = os.environ.get("PLANER_HIP_WINO_CHAIN", "1")
-        if mode != "0":
-            def fits(key):
-                # whole planes per workgroup: the plane must fit the LDS kernel, and there must be enough (image,
-                # channel quad) planes to fill the chip (a batch-1 detection net has 32-256 of them: not worth it)
-                shp = shapes.get(key.split("@")[0])
-                return (shp is not None and len(shp) == 4 and shp[0] * (shp[1] // 4) >= self.ctx.cu_count // 2
-                        and _q4.wino4_chain_supported(tuple(shp), self.ctx))
-            out_list, out_flow, self.wino_chains = chain_winograd(out_list, out_flow, fits, chain=mode != "stages")
-            # a 1x1 conv whose only reader is such a conv's input transform writes V itself (detection nets at small maps: one
-            # launch less per 3x3 conv); PLANER_HIP_CONV1X1_WINO=0 turns it off, =<tiles> moves the size limit
-            lim = os.environ.get("PLANER_HIP_CONV1X1_WINO", "4096")
-            if lim != "0":
-                def small(key):
-                    shp = shapes.get(key.split("@")[0])
-                    return shp is not None and len(shp) == 4 and shp[0] * (-(-shp[2] // 4)) * (-(-shp[3] // 4)) <= int(lim)
-                out_list, out_flow, self.conv_wino_fused = fuse_conv1x1_wino_in(out_list, out_flow, self._shape_of_init, small)
-        return out_list, out_flow
+        env = lambda name, default="1": os.environ.get("PLANER_HIP_" + name, default)          # noqa: E731
 
-    @staticmethod
-    def _fuse_upsample_concat(body, flow):
-        """upsample_q4 whose only reader is a two-input concat_q4 (axis 1) that takes it FIRST -> one upconcat_q4 step
-        (detection-net routes: the upsampled tensor is written once, into its place in the concatenation)."""
-        readers = {}
-        for i, (src, names, dst) in enumerate(flow):
-            for k in (src if isinstance(src, list) else [src]):
-                readers.setdefault(k, []).append(i)
-        drop, out = set(), {}
-        for i, (src, names, dst) in enumerate(flow):
-            entry = body[names[0]]
-            if (entry[1] == "upsample_q4" and isinstance(dst, str) and isinstance(src, list) and len(src) == 2
-                    and entry[2].get("mode", "nearest") == "nearest" and len(readers.get(dst, [])) == 1):
-                j = readers[dst][0]
-                csrc, cnames, cdst = flow[j]
-                ce = body[cnames[0]]
-                if (ce[1] == "concat_q4" and len(cnames) == 1 and isinstance(csrc, list) and len(csrc) == 2 and csrc[0] == dst
-                        and int(ce[2].get("axis", 0)) == 1 and i < j
-                        # the upsample now reads its source at step j: nobody may touch it in between (in-place ReLU)
-                        and not any(src[0] in (f[0] if isinstance(f[0], list) else [f[0]]) for f in flow[i + 1:j])):
-                    body[cnames[0]] = [ce[0], "upconcat_q4", {"mode": "nearest", "axis": 1}]
-                    out[j] = [[src[0], src[1], csrc[1]], cnames, cdst]
-                    drop.add(i)
-        return [out.get(i, f) for i, f in enumerate(flow) if i not in drop]
+        def kshape(key):
+            # an init or a prepared copy of one; a filter that is not float32 is left to the kernel that converts it
+            K = wmap.get(key, self._extra.get(key))
+            return K.shape if K is not None and K.dtype == numpy.float32 else None
 
-    def _fuse_stem_pool(self, body, flow, shapes):
-        """conv_q4 (row-packed stem, w_layout 6, no residual) whose only reader is maxpool_q4(w=3x3, strides 2, pads 1) -> one
-        conv_pool_q4 step: the full-resolution tensor is never written."""
-        readers = {}
-        for i, (src, names, dst) in enumerate(flow):
-            for k in (src if isinstance(src, list) else [src]):
-                readers.setdefault(k, []).append(i)
-        drop, out = set(), []
-        for i, (src, names, dst) in enumerate(flow):
-            entry = body[names[0]]
-            if (entry[1] == "conv_q4" and entry[2].get("w_layout") == ROWPACK_Q4 and isinstance(dst, str)
-                    and (len(src) < 6 or src[5] == "None") and len(readers.get(dst, [])) == 1 and i != len(flow) - 1):
-                j = readers[dst][0]
-                psrc, pnames, pdst = flow[j]
-                pe = body[pnames[0]]
-                xs, ks = shapes.get(src[0].split("@")[0]), self._shape_of_init(src[1])
-                para = {k: v for k, v in entry[2].items() if k in ("group", "strides", "dilations", "pads")}
-                if (pe[1] == "maxpool_q4" and len(pnames) == 1 and (psrc == dst or psrc == [dst]) and xs is not None
-                        and [int(v) for v in pe[2].get("w", (2, 2))] == [3, 3]
-                        and [int(v) for v in pe[2].get("strides", (2, 2))] == [2, 2]
-                        and [int(v) for v in pe[2].get("pads", (0, 0, 0, 0))] == [1, 1, 1, 1]
-                        and int(entry[2].get("act", 0)) in (0, 1, 2) and _q4.stem_pool_eligible(tuple(xs), tuple(ks), **para)):
-                    lay, fsrc, packed = STEM_POOL, list(src[:5]), suffix(ROWPACK_Q4, para)
-                    if (os.environ.get("PLANER_HIP_STEM_NCHW", "1") != "0" and src[1].endswith(packed)
-                            and _q4.stem_pool_nchw_eligible(tuple(xs), tuple(ks), **para)):
-                        # W % 4 == 0: the kernel reads the NCHW batch itself (no row-packed copy), filter in its own k order
-                        lay, init = STEM_POOL_NCHW, src[1][:-len(packed)]
-                        key = init + suffix(lay, para)
-                        if key not in self._extra:
-                            self._extra[key] = LAYOUTS[lay].prepare(dict(zip(self.inits, self.weights))[init])
-                        fsrc[1] = key
-                    extra = {}
-                    if lay == STEM_POOL_NCHW and self._pick_mode == "throughput" and os.environ.get("PLANER_HIP_STEM_ROWS14", "1") != "0":
-                        # throughput plans: strips of 14 pooled rows where that still leaves half a chip of workgroups -- 15
-                        # conv-row pairs instead of 2 x 8, on half the CUs for longer (160 against 91 us alone; +0.8 ... +1.2 % on
-                        # seven replicas: the other replicas' kernels take the rest of the chip, DESIGN 4.7 item 9)
-                        hq = ((xs[2] + 6 - 7) // 2 + 1 + 1) // 2
-                        if xs[0] * (-(-hq // 14)) * (-(-ks[0] // 64)) * 2 >= self.ctx.cu_count:
-                            extra["strip_rows"] = 14
-                    body[names[0]] = [entry[0], "conv_pool_q4", dict(entry[2], w_layout=lay, **extra)]
-                    out.append([fsrc, names, pdst])
-                    drop.add(j)
-                    continue
-            if i not in drop:
-                out.append([src, names, dst])
-        return out
+        def prepare(lay, init, para):
+            key = init + suffix(lay, para)
+            if key not in self._extra:
+                self._extra[key] = LAYOUTS[lay].prepare(wmap[init], **para)
+            return key
+
+        def stem_pool(xs, ks, para):
+            if not _q4.stem_pool_eligible(xs, ks, **para):
+                return None
+            # W % 4 == 0: the kernel reads the NCHW batch itself; PLANER_HIP_STEM_NCHW=0 keeps the row-packed copy
+            if env("STEM_NCHW") == "0" or not _q4.stem_pool_nchw_eligible(xs, ks, **para):
+                return STEM_POOL, {}
+            extra = {}
+            if self._pick_mode == "throughput" and env("STEM_ROWS14") != "0":
+                # throughput plans: strips of 14 pooled rows where that still leaves half a chip of workgroups -- 15
+                # conv-row pairs instead of 2 x 8, on half the CUs for longer (160 against 91 us alone; +0.8 ... +1.2 % on
+                # seven replicas: the other replicas' kernels take the rest of the chip, DESIGN 4.7 item 9)
+                hq = ((xs[2] + 6 - 7) // 2 + 1 + 1) // 2
+                if xs[0] * (-(-hq // 14)) * (-(-ks[0] // 64)) * 2 >= self.ctx.cu_count:
+                    extra["strip_rows"] = 14
+            return STEM_POOL_NCHW, extra
+
+        def fits(key):
+            # whole planes per workgroup: the plane must fit the LDS kernel, and there must be enough (image,
+            # channel quad) planes to fill the chip (a batch-1 detection net has 32-256 of them: not worth it)
+            shp = shapes.get(key.split("@")[0])
+            return (shp is not None and len(shp) == 4 and shp[0] * (shp[1] // 4) >= self.ctx.cu_count // 2
+                    and _q4.wino4_chain_supported(tuple(shp), self.ctx))
+
+        lim = env("CONV1X1_WINO", "4096")            # =0 turns the 1x1 -> Winograd input transform step off, =<tiles> moves the limit
+
+        def small(key):
+            shp = shapes.get(key.split("@")[0])
+            return shp is not None and len(shp) == 4 and shp[0] * (-(-shp[2] // 4)) * (-(-shp[3] // 4)) <= int(lim)
+
+        body, flow, counts = lower(
+            body, flow, self.inits, shapes, kshape=kshape, prepare=prepare, fits=fits, small=small if lim != "0" else None,
+            pick=lambda cands, kind, srcs, para: self._pick_conv_algo(cands, wmap[srcs[1]], srcs, para, shapes, q4=kind == "conv_q4"),
+            stem_pool=stem_pool if env("STEM_POOL") != "0" else None, pair=env("PAIR") != "0", wino_chain=env("WINO_CHAIN"))
+        for name, attr in (("pair_sibling_convs", "conv_pairs"), ("chain_winograd", "wino_chains"),
+                           ("fuse_conv1x1_wino_in", "conv_wino_fused")):
+            if name in counts:                       # (a pass switched off leaves its counter as it was)
+                setattr(self, attr, counts[name])
+        return body, flow
+
+    _fuse_upsample_concat = staticmethod(fuse_upsample_concat)      # the name callers outside the package know it by
 
     def _pick_conv_algo(self, cands, K, srcs, para, shapes, q4=False):
         """Time the candidate w_layouts (conv_layouts.candidates) for this conv's real shape and epilogue; the first is the

@@ -15,7 +15,8 @@ chain was, so a residual operand produced after the conv is still available.
 """
 import os
 
-from .conv_layouts import DIRECT_Q4, STAGED_LAYOUTS, convt_phase_eligible, dw_q4_eligible, q4_conv_eligible
+from .conv_layouts import (CONVT_KINDS, DIRECT_Q4, ROWPACK_Q4, STAGED_LAYOUTS, STEM_POOL, STEM_POOL_NCHW, choose, conv_para,
+                           convt_phase_eligible, dw_q4_eligible, q4_conv_eligible, suffix)
 from .layer import PIXEL_SHUFFLE_AXES, _nearest_shift, pixel_shuffle_shapes
 
 ACT_NONE, ACT_RELU, ACT_LEAKY = 0, 1, 2
@@ -808,7 +809,7 @@ _PURE_READERS = ("conv_q4", "convt_q4", "wino4_in", "wino4_gemm", "wino4_out", "
 
 def chain_winograd(body, flow, supported=lambda key: True, chain=True):
     """-> (body', flow', number of chained pairs).  `flow` holds one layer per step (as made by
-    assign_layouts / Net._prepare_filters); `supported(key)` says whether the LDS transform kernel
+    assign_layouts / lower); `supported(key)` says whether the LDS transform kernel
     can take the activation `key` (whole planes must fit a workgroup's LDS)."""
     kinds = {b[0]: b for b in body}
     steps = []                      # [srcs, name, kind, para, dst]
@@ -920,7 +921,7 @@ _IN_PLACE = ("relu", "relu_q4", "clip", "clip_q4", "erf", "instancenormalization
 
 
 def pair_sibling_convs(body, flow, kshape=lambda key: None):
-    """-> (body', flow', number of pairs).  One layer per step, as made by Net._prepare_filters.  `kshape(key)` gives
+    """-> (body', flow', number of pairs).  One layer per step, as made by lower.  `kshape(key)` gives
     the OIHW shape of a filter key; only the projection pattern is paired -- equal strides > 1, one of the two a 1x1 --
     because both convs then have the same output map and neither wants a split-K plan of its own."""
     kinds = {b[0]: b for b in body}
@@ -1145,3 +1146,162 @@ def fold_dilated(body, flow, shapes, worth=lambda x_shape, k_shape, para: True):
     if not regions:
         return [list(b) for b in body], [[list(s) if isinstance(s, (list, tuple)) else s, n, d] for s, n, d in flow], []
     return out_body, named, regions
+
+
+# ---- peepholes behind the filter choice (`body` is {name: entry} there and is rewritten in place) ---------------------------------
+def fuse_upsample_concat(body, flow):
+    """upsample_q4 whose only reader is a two-input concat_q4 (axis 1) that takes it FIRST -> one upconcat_q4 step
+    (detection-net routes: the upsampled tensor is written once, into its place in the concatenation)."""
+    readers = {}
+    for i, (src, names, dst) in enumerate(flow):
+        for k in (src if isinstance(src, list) else [src]):
+            readers.setdefault(k, []).append(i)
+    drop, out = set(), {}
+    for i, (src, names, dst) in enumerate(flow):
+        entry = body[names[0]]
+        if (entry[1] == "upsample_q4" and isinstance(dst, str) and isinstance(src, list) and len(src) == 2
+                and entry[2].get("mode", "nearest") == "nearest" and len(readers.get(dst, [])) == 1):
+            j = readers[dst][0]
+            csrc, cnames, cdst = flow[j]
+            ce = body[cnames[0]]
+            if (ce[1] == "concat_q4" and len(cnames) == 1 and isinstance(csrc, list) and len(csrc) == 2 and csrc[0] == dst
+                    and int(ce[2].get("axis", 0)) == 1 and i < j
+                    # the upsample now reads its source at step j: nobody may touch it in between (in-place ReLU)
+                    and not any(src[0] in (f[0] if isinstance(f[0], list) else [f[0]]) for f in flow[i + 1:j])):
+                body[cnames[0]] = [ce[0], "upconcat_q4", {"mode": "nearest", "axis": 1}]
+                out[j] = [[src[0], src[1], csrc[1]], cnames, cdst]
+                drop.add(i)
+    return [out.get(i, f) for i, f in enumerate(flow) if i not in drop]
+
+
+def fuse_stem_pool(body, flow, shapes, kshape, eligible, prepare):
+    """conv_q4 (row-packed stem, w_layout 6, no residual) whose only reader is maxpool_q4(w=3x3, strides 2, pads 1) -> one
+    conv_pool_q4 step: the full-resolution tensor is never written.  `eligible(x shape, filter shape, para)` -> None, or the
+    w_layout that takes the conv and its extra parameters (lower's `stem_pool`); STEM_POOL_NCHW reads the NCHW batch itself (no
+    row-packed copy) with the filter in its own k order, which `prepare` makes."""
+    readers = {}
+    for i, (src, names, dst) in enumerate(flow):
+        for k in (src if isinstance(src, list) else [src]):
+            readers.setdefault(k, []).append(i)
+    drop, out = set(), []
+    for i, (src, names, dst) in enumerate(flow):
+        entry = body[names[0]]
+        if (entry[1] == "conv_q4" and entry[2].get("w_layout") == ROWPACK_Q4 and isinstance(dst, str)
+                and (len(src) < 6 or src[5] == "None") and len(readers.get(dst, [])) == 1 and i != len(flow) - 1):
+            j = readers[dst][0]
+            psrc, pnames, pdst = flow[j]
+            pe = body[pnames[0]]
+            xs, ks = shapes.get(src[0].split("@")[0]), kshape(src[1])
+            para = conv_para(entry[2])
+            got = None
+            if (pe[1] == "maxpool_q4" and len(pnames) == 1 and (psrc == dst or psrc == [dst]) and xs is not None
+                    and [int(v) for v in pe[2].get("w", (2, 2))] == [3, 3]
+                    and [int(v) for v in pe[2].get("strides", (2, 2))] == [2, 2]
+                    and [int(v) for v in pe[2].get("pads", (0, 0, 0, 0))] == [1, 1, 1, 1]
+                    and int(entry[2].get("act", 0)) in (0, 1, 2)):
+                got = eligible(tuple(xs), tuple(ks), para)
+            if got is not None:
+                (lay, extra), fsrc, packed = got, list(src[:5]), suffix(ROWPACK_Q4, para)
+                if lay == STEM_POOL_NCHW and src[1].endswith(packed):
+                    fsrc[1] = prepare(lay, src[1][:-len(packed)], para)
+                elif lay == STEM_POOL_NCHW:
+                    lay, extra = STEM_POOL, {}
+                body[names[0]] = [entry[0], "conv_pool_q4", dict(entry[2], w_layout=lay, **extra)]
+                out.append([fsrc, names, pdst])
+                drop.add(j)
+                continue
+        if i not in drop:
+            out.append([src, names, dst])
+    return out
+
+
+# ---- the compiler: the passes in the order they run ------------------------------------------------------------------------------
+# Net._fuse and the host tests both compile through compile_front and lower, so the order is written here only.  What needs a
+# device or the weights -- timing conv candidates, preparing filters, kernel limits -- comes in through the caller; the defaults
+# are what a host without either answers.
+FRONT = ("fuse_flow", "fuse_pixel_shuffle", "fuse_groupnorm", "assign_layouts", "fuse_instnorm_q4", "fuse_linear_add", "fold_dilated")
+
+
+def compile_front(layers, flow, inits, shapes, fuse=True, q4=True, values=None, worth=None, stop=None):
+    """The front half of a compile: the passes of FRONT in that order, up to and including `stop` (a name in FRONT; None: all).
+    -> (body, flow, {pass that ran: the third value it returned}).  fuse: epilogue fusion (fuse_flow).  q4: channel-quad
+    activations, False / True / "force" (assign_layouts' `force`); without it only fuse_flow runs.  values: key -> host array of
+    an init, or None.  worth: fold_dilated's callback; None leaves dilated convs as they are.  PLANER_HIP_PIXEL_SHUFFLE_Q4 and
+    PLANER_HIP_GROUPNORM_Q4 are read here, at each call."""
+    run = {
+        "fuse_flow": fuse and (lambda b, f: fuse_flow(b, f, inits, shapes)),
+        # reshape -> transpose -> reshape that is a pixel shuffle / unshuffle as one step, which has a one-pass Q4 kernel
+        "fuse_pixel_shuffle": q4 and pixel_shuffle_enabled() and (lambda b, f: fuse_pixel_shuffle(b, f, shapes)),
+        # reshape -> instancenormalization -> reshape -> [mul] -> [add] that is a group norm as one step, which has a Q4 kernel
+        "fuse_groupnorm": q4 and groupnorm_enabled() and (lambda b, f: fuse_groupnorm(b, f, shapes, inits)),
+        "assign_layouts": q4 and (lambda b, f: assign_layouts(b, f, inits, shapes, force=q4 == "force", values=values)),
+        # instancenormalization_q4 -> [add_q4] -> [relu_q4] as one step: the tail goes into the norm's write pass
+        "fuse_instnorm_q4": q4 and (lambda b, f: fuse_instnorm_q4(b, f, shapes)),
+        # linear upsample_q4 / resize_q4 -> add_q4 as one step: the add goes into the upsample's write pass
+        "fuse_linear_add": q4 and (lambda b, f: fuse_linear_add(b, f, shapes)),
+        # dilated 3x3 convs folded by pixel phase onto the Winograd kernels, where `worth` agrees
+        "fold_dilated": q4 and worth is not None and (lambda b, f: fold_dilated(b, f, shapes, worth)),
+    }
+    body, flow, counts = [list(b) for b in layers], [list(f) for f in flow], {}
+    for name in FRONT[:FRONT.index(stop) + 1 if stop else None]:
+        if run[name]:
+            body, flow, counts[name] = run[name](body, flow)
+    return body, flow, counts
+
+
+def lower(body, flow, inits, shapes, kshape=None, pick=lambda cands, kind, srcs, para: cands[0], prepare=None, stem_pool=None,
+          pair=True, wino_chain="1", fits=lambda key: True, small=lambda key: True):
+    """The back half of a compile: every eligible conv gets a w_layout and the key of its prepared filter (conv_layouts.choose),
+    then the stem-pool and upsample/concat peepholes, pair_sibling_convs, chain_winograd and fuse_conv1x1_wino_in.
+    -> (body, flow, {pass that ran: the third value it returned}).  The answers of the caller:
+      kshape(key)                        the OIHW shape of a filter key, None for what no kernel takes as a filter
+                                         (host: the shape of the init the key was made from);
+      pick(cands, kind, srcs, para)      the w_layout of a conv several apply to (host: the first; Net times them);
+      prepare(w_layout, init key, para)  -> the key of the init's filter prepared for that layout (host: key + suffix; Net makes
+                                         the copy);
+      stem_pool(x shape, filter shape, para) -> None, or (STEM_POOL or STEM_POOL_NCHW, extra parameters such as strip_rows) where
+                                         the stem + max-pool kernel takes the conv (host, and PLANER_HIP_STEM_POOL=0: None);
+      pair                               sibling convs in one launch (PLANER_HIP_PAIR);
+      wino_chain                         "1" staged Winograd convs chained, "stages" explicit stages only, "0" one call per conv
+                                         (PLANER_HIP_WINO_CHAIN);
+      fits(key)                          whether the chained transform kernel takes that activation (host: yes);
+      small(key)                         whether a 1x1 conv on that activation is small enough to run inside the next conv's input
+                                         transform (host: yes; None, PLANER_HIP_CONV1X1_WINO=0: no such step)."""
+    inits = set(inits)
+    kshape = kshape or (lambda key: shapes.get(key.split("@")[0]) if key.split("@")[0] in inits else None)
+    prepare = prepare or (lambda lay, key, para: key + suffix(lay, para))
+    kinds = {b[0]: b for b in body}
+    out_body = {b[0]: list(b) for b in body}
+    out_flow = []
+    for src, names, dst in flow:
+        name = names[0] if isinstance(names, list) else names
+        _, kind, para = kinds[name]
+        srcs = list(src) if isinstance(src, list) else [src]
+        ks = kshape(srcs[1]) if len(srcs) >= 2 and srcs[1] in inits else None
+        if ks is not None:
+            # (an NCHW conv looks its input up by key: one on a converted copy, key@nchw, is not timed)
+            xs = shapes.get(srcs[0].split("@")[0] if kind == "conv_q4" else srcs[0])
+            got = choose(kind, ks, para, xs, para.get("rowpack"), lambda cands: pick(cands, kind, srcs, para))
+            if got is not None:
+                srcs[1] = prepare(got[0], srcs[1], para)
+                new_kind = kind if kind in ("conv_q4", "convt_q4") else "convt_fused" if kind in CONVT_KINDS else "conv_fused"
+                out_body[name] = [name, new_kind, dict(para, w_layout=got[0])]
+        out_flow.append([srcs, [name], dst])
+    # the row-packed stem conv whose only reader is maxpool(3x3 / s2 / p1): one kernel that writes the pooled tensor only
+    # (csrc/conv_stem_pool_kernel.h)
+    if stem_pool is not None:
+        out_flow = fuse_stem_pool(out_body, out_flow, shapes, kshape, stem_pool, prepare)
+    out_flow = fuse_upsample_concat(out_body, out_flow)
+    used = {n for _, names, _ in out_flow for n in names}
+    body, flow, counts = [out_body[b[0]] for b in body if b[0] in used], out_flow, {}
+    # two direct convs on one tensor (a resolution-changing ResNet block) -> one launch
+    if pair:
+        body, flow, counts["pair_sibling_convs"] = pair_sibling_convs(body, flow, kshape)
+    # F(4x4,3x3) convs as explicit stages, consecutive ones sharing a transform kernel
+    if wino_chain != "0":
+        body, flow, counts["chain_winograd"] = chain_winograd(body, flow, fits, chain=wino_chain != "stages")
+        # a 1x1 conv whose only reader is such a conv's input transform writes V itself (detection nets at small maps: one
+        # launch less per 3x3 conv)
+        if small is not None:
+            body, flow, counts["fuse_conv1x1_wino_in"] = fuse_conv1x1_wino_in(body, flow, kshape, small)
+    return body, flow, counts

@@ -220,7 +220,7 @@ def ConvPoolQ4(x, Kq, B=None, scale=None, shift=None, group=1, strides=(1, 1), d
                act=ACT_NONE, alpha=0.0, w_layout=STEM_POOL, out=None, src_ptr=None, ctx=None, strip_rows=0, **_):
     """Row-packed stem conv (ConvQ4 w_layout 6: NCHW input, filter from prepare_rowpack_weights) with its fused tail, followed
     by layer.Maxpool(w=(3, 3), strides=(2, 2), pads=(1, 1, 1, 1)) (layer.py:71-72), in ONE kernel: only the pooled Q4 tensor is
-    written.  Emitted by the plan compiler (Net._fuse_stem_pool) where the max-pool is the conv's only reader.
+    written.  Emitted by the plan compiler (plan.fuse_stem_pool) where the max-pool is the conv's only reader.
     w_layout 12: the kernel reads the NCHW tensor itself (filter from prepare_stem_nchw_weights; W % 4 == 0) -- no row-packed
     copy.  A plan's static input then carries `x.prefed = (feed, pooled)`: whoever feeds the plan runs this kernel from the
     caller's batch straight into `pooled` (`out` / `src_ptr` / `ctx` below), and the captured pass starts behind it."""

@@ -1,6 +1,6 @@
 """Shared pieces of the group-norm tests (tests/test_plan_groupnorm.py on the host, tests/test_gpu_groupnorm.py on the GPU): the
 five steps an exporter writes -- reshape (N, G, -1), instancenormalization, reshape back, mul gamma, add beta -- as conv -> norm ->
-conv graphs, the compile pipeline of Net._fuse up to fuse_linear_add with plan.fuse_groupnorm in it, the oracle stand-in, and the
+conv graphs, the compiler's front half up to fuse_linear_add, the oracle stand-in, and the
 float64 reference with its per-element bound.
 
 The bound is tests/ref64_ops.instancenorm_bound on the rows (N G, cpg HW) -- a group is contiguous in NCHW -- carried through the
@@ -13,11 +13,10 @@ relu is exact and 1-Lipschitz.  A term is there only where its operation is.  No
 import numpy as np
 
 from oracle import planer_np as onp
-from planer_amd.plan import (assign_layouts, fuse_flow, fuse_groupnorm, fuse_instnorm_q4, fuse_linear_add, fuse_pixel_shuffle,
-                             groupnorm_enabled, pixel_shuffle_enabled)
+from tests import plan_audit as PA
 from tests import ref64_ops as R
-from tests.linear_q4_ref import Small, kinds_of, steps_of, values_of      # noqa: F401
-from tests.test_plan_fusion import _q4_standins, shapes_of
+from tests.linear_q4_ref import Small
+from tests.plan_audit import cpu_front, kinds_of, steps_of      # noqa: F401
 
 F32 = np.float32
 
@@ -67,20 +66,9 @@ def make_x(n=2, hw=(6, 7), seed=3):
 
 
 def compile_plan(g, b, x, force=True):
-    """fuse_flow -> [fuse_pixel_shuffle] -> [fuse_groupnorm] -> assign_layouts -> fuse_instnorm_q4 -> fuse_linear_add, as Net._fuse
-    runs them.  -> (body, flow, number of norms fused, shapes)."""
-    shapes = shapes_of(g, b, x)
-    inits = [i[0] for i in g["inits"]]
-    body, flow, _ = fuse_flow(g["layers"], g["flow"], inits, shapes)
-    ngn = 0
-    if pixel_shuffle_enabled():
-        body, flow, _ = fuse_pixel_shuffle(body, flow, shapes)
-    if groupnorm_enabled():
-        body, flow, ngn = fuse_groupnorm(body, flow, shapes, inits)
-    body, flow, _ = assign_layouts(body, flow, inits, shapes, force=force, values=values_of(g, b))
-    body, flow, _ = fuse_instnorm_q4(body, flow, shapes)
-    body, flow, _ = fuse_linear_add(body, flow, shapes)
-    return body, flow, ngn, shapes
+    """plan.compile_front up to fuse_linear_add.  -> (body, flow, number of norms fused, shapes)."""
+    body, flow, counts, shapes = cpu_front(g, b, x, force, stop="fuse_linear_add")
+    return body, flow, counts.get("fuse_groupnorm", 0), shapes
 
 
 def groupnorm_np(x, s, bias, gamma=None, beta=None, res=None, groups=1, epsilon=1e-5, act=0, mid="3d"):
@@ -103,17 +91,7 @@ def groupnorm_np(x, s, bias, gamma=None, beta=None, res=None, groups=1, epsilon=
 def run_on_oracle(g, b, x, body, flow, mid="3d"):
     """The program (body, flow) on the numpy oracle: plan-internal kinds as their NCHW operators, groupnorm[_q4] as the five steps."""
     from functools import partial
-    saved = dict(onp.OPS)
-    onp.OPS.update(_q4_standins())
-    onp.OPS.update({"groupnorm": partial(groupnorm_np, mid=mid), "groupnorm_q4": partial(groupnorm_np, mid=mid)})
-    try:
-        net = onp.OracleNet()
-        net.load_json(g["input"], g["inits"], body, flow)
-    finally:
-        onp.OPS.clear()
-        onp.OPS.update(saved)
-    net.load_weights(b)
-    return net(x.copy())
+    return PA.run_on_oracle(g, b, x, body, flow, groupnorm=partial(groupnorm_np, mid=mid), groupnorm_q4=partial(groupnorm_np, mid=mid))
 
 
 # ---- float64 reference, bound, float32 emulation -------------------------------------------------------------------------------

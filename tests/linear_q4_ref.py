@@ -1,65 +1,29 @@
 """Shared pieces of the tests of linear upsample / resize in channel-quad (Q4) plans (tests/test_plan_linear_q4.py on the host,
-tests/test_gpu_linear_q4.py on the GPU): the compile pipeline of Net._fuse up to fuse_linear_add, small graphs, the bit-pattern
+tests/test_gpu_linear_q4.py on the GPU): the compiler's front half up to fuse_linear_add, small graphs, the bit-pattern
 comparison, and the per-step check tests/plan_audit.py does not have (it refuses linear upsamples and does not know resize_q4).
 """
 import numpy as np
 
 from oracle import planer_np as onp
 from planer_amd.irgen.builder import GraphBuilder
-from planer_amd.plan import assign_layouts, fuse_flow, fuse_instnorm_q4, fuse_linear_add
-from tests.test_plan_fusion import _q4_standins, shapes_of
+from tests import plan_audit as PA
+from tests.plan_audit import cpu_front, kinds_of, nchw, steps_of      # noqa: F401
 
 LINEAR_KINDS = ("upsample_q4", "resize_q4", "upsample_add_q4", "resize_add_q4")
 CONV = dict(group=1, strides=[1, 1], dilations=[1, 1], pads=[1, 1, 1, 1])
 
 
-def values_of(graph, blob):
-    """key -> host array of an init, as Net._fuse hands them to assign_layouts."""
-    out, pos = {}, 0
-    for name, shape, dt in graph["inits"]:
-        n = int(np.prod(shape, dtype=np.int64)) * np.dtype(dt).itemsize
-        out[name] = blob[pos:pos + n].view(dt).reshape(shape)
-        pos += n
-    return lambda key: out.get(key)
-
-
 def compile_plan(g, b, x, force=True):
-    """fuse_flow -> assign_layouts -> fuse_instnorm_q4 -> fuse_linear_add, as Net._fuse runs them.
-    -> (body, flow, number of adds fuse_linear_add absorbed, shapes)."""
-    shapes = shapes_of(g, b, x)
-    inits = [i[0] for i in g["inits"]]
-    body, flow, _ = fuse_flow(g["layers"], g["flow"], inits, shapes)
-    body, flow, _ = assign_layouts(body, flow, inits, shapes, force=force, values=values_of(g, b))
-    body, flow, _ = fuse_instnorm_q4(body, flow, shapes)
-    body, flow, nadd = fuse_linear_add(body, flow, shapes)
-    return body, flow, nadd, shapes
-
-
-def steps_of(body, flow):
-    """[(kind, para, srcs, dst)] in flow order."""
-    k = {b[0]: b for b in body}
-    return [(k[names[0]][1], k[names[0]][2], list(src) if isinstance(src, (list, tuple)) else [src], dst) for src, names, dst in flow]
-
-
-def kinds_of(body, flow):
-    return [s[0] for s in steps_of(body, flow)]
+    """plan.compile_front up to fuse_linear_add.  -> (body, flow, number of adds fuse_linear_add absorbed, shapes)."""
+    body, flow, counts, shapes = cpu_front(g, b, x, force, stop="fuse_linear_add")
+    return body, flow, counts["fuse_linear_add"], shapes
 
 
 def run_on_oracle(g, b, x, body, flow):
     """The program (body, flow) on the numpy oracle, plan-internal kinds replaced by their NCHW operators."""
-    saved = dict(onp.OPS)
-    onp.OPS.update(_q4_standins())
-    onp.OPS.update({"resize_q4": onp.OPS["resize"],
-                    "upsample_add_q4": lambda x, k, res, **kw: onp.OPS["upsample"](x, k, **kw) + res,
-                    "resize_add_q4": lambda x, roi, k, size, res, **kw: onp.OPS["resize"](x, roi, k, size, **kw) + res})
-    try:
-        net = onp.OracleNet()
-        net.load_json(g["input"], g["inits"], body, flow)
-    finally:
-        onp.OPS.clear()
-        onp.OPS.update(saved)
-    net.load_weights(b)
-    return net(x.copy())
+    return PA.run_on_oracle(g, b, x, body, flow, resize_q4=onp.OPS["resize"],
+                            upsample_add_q4=lambda x, k, res, **kw: onp.OPS["upsample"](x, k, **kw) + res,
+                            resize_add_q4=lambda x, roi, k, size, res, **kw: onp.OPS["resize"](x, roi, k, size, **kw) + res)
 
 
 class Small:
@@ -119,7 +83,6 @@ def check_linear_steps(pa, trace, inits):
     layer (and layer.Add for a fused add) applied on the device to the step's own captured inputs.  `inits`: key -> host array
     (plan_audit.host_inits).  -> number of steps checked."""
     from planer_amd import layer
-    from tests.plan_audit import nchw
     n = 0
     for st in trace:
         if st.kind not in LINEAR_KINDS:

@@ -1,13 +1,11 @@
 """Shared pieces of the pixel shuffle / unshuffle tests (tests/test_plan_pixel_shuffle.py on the host,
 tests/test_gpu_pixel_shuffle.py on the GPU): numpy's own reshape / transpose / reshape as the reference, the four forms as
-conv -> trio -> conv graphs, and the compile pipeline of Net._fuse up to fuse_linear_add with plan.fuse_pixel_shuffle in it."""
+conv -> trio -> conv graphs, and the compiler's front half up to fuse_linear_add."""
 import numpy as np
 
-from oracle import planer_np as onp
-from planer_amd.plan import (assign_layouts, fuse_flow, fuse_instnorm_q4, fuse_linear_add, fuse_pixel_shuffle,
-                             pixel_shuffle_enabled)
-from tests.linear_q4_ref import Small, kinds_of, steps_of, values_of      # noqa: F401
-from tests.test_plan_fusion import _q4_standins, shapes_of
+from tests import plan_audit as PA
+from tests.linear_q4_ref import Small
+from tests.plan_audit import cpu_front, kinds_of, steps_of      # noqa: F401
 
 # (order, inverse) -> the 6-D permutation, as the issue's table has them
 AXES = {("crd", False): [0, 1, 4, 2, 5, 3], ("dcr", False): [0, 3, 4, 1, 5, 2],
@@ -67,30 +65,11 @@ def make_x(n=2, hw=(6, 8), seed=3):
 
 
 def compile_plan(g, b, x, force=True):
-    """fuse_flow -> [fuse_pixel_shuffle] -> assign_layouts -> fuse_instnorm_q4 -> fuse_linear_add, as Net._fuse runs them.
-    -> (body, flow, number of trios fused, shapes)."""
-    shapes = shapes_of(g, b, x)
-    inits = [i[0] for i in g["inits"]]
-    body, flow, _ = fuse_flow(g["layers"], g["flow"], inits, shapes)
-    nps = 0
-    if pixel_shuffle_enabled():
-        body, flow, nps = fuse_pixel_shuffle(body, flow, shapes)
-    body, flow, _ = assign_layouts(body, flow, inits, shapes, force=force, values=values_of(g, b))
-    body, flow, _ = fuse_instnorm_q4(body, flow, shapes)
-    body, flow, _ = fuse_linear_add(body, flow, shapes)
-    return body, flow, nps, shapes
+    """plan.compile_front up to fuse_linear_add.  -> (body, flow, number of trios fused, shapes)."""
+    body, flow, counts, shapes = cpu_front(g, b, x, force, stop="fuse_linear_add")
+    return body, flow, counts.get("fuse_pixel_shuffle", 0), shapes
 
 
 def run_on_oracle(g, b, x, body, flow):
     """The program (body, flow) on the numpy oracle: plan-internal kinds as their NCHW operators, pixelshuffle[_q4] as numpy's trio."""
-    saved = dict(onp.OPS)
-    onp.OPS.update(_q4_standins())
-    onp.OPS.update({"pixelshuffle": shuffle_np, "pixelshuffle_q4": shuffle_np})
-    try:
-        net = onp.OracleNet()
-        net.load_json(g["input"], g["inits"], body, flow)
-    finally:
-        onp.OPS.clear()
-        onp.OPS.update(saved)
-    net.load_weights(b)
-    return net(x.copy())
+    return PA.run_on_oracle(g, b, x, body, flow, pixelshuffle=shuffle_np, pixelshuffle_q4=shuffle_np)

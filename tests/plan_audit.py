@@ -1,8 +1,8 @@
 """Step-by-step float64 audit of a compiled plan program.
 
 The per-family tests (tests/ref64.py, tests/ref64_ops.py) call each kernel on operands the test built; a forward pass runs
-them on operands the plan compiler built (plan.fuse_flow, assign_layouts, conv_layouts.choose, pair_sibling_convs,
-chain_winograd, fuse_conv1x1_wino_in, Net._fuse_stem_pool, the upsample/concat peephole).  The audit runs the program a
+them on operands the plan compiler built (plan.compile_front and plan.lower: fuse_flow, assign_layouts, conv_layouts.choose,
+pair_sibling_convs, chain_winograd, fuse_conv1x1_wino_in, the stem + max-pool and upsample/concat peepholes).  The audit runs the program a
 captured plan runs, step by step, and checks every step against float64 computed from the inputs that step really read:
 
 * `capture(net, xs, mode)` builds the program exactly as Net._compile does for one sub-batch (under `net.picking(mode)`) and
@@ -25,8 +25,9 @@ captured plan runs, step by step, and checks every step against float64 computed
   A failure names the step, its kind, w_layout and launch plan, and the worst element (n, c, y, x) with its err / tol.
   -> {family: worst err / tol}, plus the census of w_layouts the program ran.
 
-The CPU tests (tests/test_plan_audit.py) feed the same audit a trace made by `cpu_trace`: the program built with the host
-passes and interpreted with numpy stand-ins (the oracle's float32 ops, Q4 values packed by numpy)."""
+The CPU tests (tests/test_plan_audit.py) feed the same audit a trace made by `cpu_trace`: the program built by the same
+two functions with the host's answers (`cpu_program`) and interpreted with numpy stand-ins (the oracle's float32 ops, Q4
+values packed by numpy)."""
 import collections
 
 import numpy as np
@@ -368,39 +369,52 @@ def _conv_np(x, K, B=None, scale=None, shift=None, res=None, act=0, alpha=0.0, *
     return conv_fused_np(np.asarray(x, np.float32), K, B, scale, shift, res, act, alpha, **conv)
 
 
-def cpu_program(graph, blob, x, pick=lambda cands: cands[0], force_q4=False):
-    """The host passes of Net._fuse on this graph: fuse_flow, assign_layouts, conv_layouts.choose (with `pick` in place of
-    the timing), the upsample/concat peephole, pair_sibling_convs, chain_winograd (every map supported) and
-    fuse_conv1x1_wino_in.  -> (body, flow, shapes)"""
-    from planer_amd.net import Net
-    from planer_amd.plan import assign_layouts, chain_winograd, fuse_conv1x1_wino_in, fuse_flow, pair_sibling_convs
+def cpu_front(graph, blob, x, force=False, **kw):
+    """plan.compile_front on this graph, as Net._fuse calls it: shapes from one oracle pass, `values` from the blob; `kw`: its
+    `stop`, `worth`, `fuse`.  -> (body, flow, counts, shapes)"""
+    from planer_amd.plan import compile_front
     from tests.test_plan_fusion import shapes_of
     shapes = shapes_of(graph, blob, x)
-    inits = [i[0] for i in graph["inits"]]
-    body, flow, _ = fuse_flow(graph["layers"], graph["flow"], inits, shapes)
-    body, flow, _ = assign_layouts(body, flow, inits, shapes, force=force_q4)
-    kinds = {b[0]: list(b) for b in body}
-    out_flow = []
-    for src, names, dst in flow:
-        name = names[0]
-        _, kind, para = kinds[name]
-        srcs = list(src) if isinstance(src, list) else [src]
-        if len(srcs) >= 2 and srcs[1] in inits and kind in cl.CONV_KINDS + cl.CONVT_KINDS + ("conv_q4", "convt_q4"):
-            xs = shapes.get(srcs[0].split("@")[0] if kind == "conv_q4" else srcs[0])
-            got = cl.choose(kind, shapes[srcs[1]], para, xs, para.get("rowpack"), pick)
-            if got is not None:
-                srcs[1] += got[1]
-                new_kind = kind if kind in ("conv_q4", "convt_q4") else "convt_fused" if kind in cl.CONVT_KINDS else "conv_fused"
-                kinds[name] = [name, new_kind, dict(para, w_layout=got[0])]
-        out_flow.append([srcs, [name], dst])
-    out_flow = Net._fuse_upsample_concat(kinds, out_flow)
-    used = {n for _, names, _ in out_flow for n in names}
-    body = [kinds[b[0]] for b in body if b[0] in used]
-    kshape = lambda key: shapes.get(key.split("@")[0])          # noqa: E731
-    body, flow, _ = pair_sibling_convs(body, out_flow, kshape)
-    body, flow, _ = chain_winograd(body, flow)
-    body, flow, _ = fuse_conv1x1_wino_in(body, flow, kshape)
+    body, flow, counts = compile_front(graph["layers"], graph["flow"], [i[0] for i in graph["inits"]], shapes,
+                                       q4="force" if force else True, values=blob_inits(graph, blob).get, **kw)
+    return body, flow, counts, shapes
+
+
+def cpu_program(graph, blob, x, pick=lambda cands: cands[0], force_q4=False):
+    """The program Net compiles for this graph, on the host: plan.compile_front, then plan.lower with `pick` in place of the
+    timing and the host's answers for the rest (no stem + max-pool kernel, every map fits the chained transform).
+    -> (body, flow, shapes)"""
+    from planer_amd.plan import lower
+    body, flow, _, shapes = cpu_front(graph, blob, x, force_q4)
+    body, flow, _ = lower(body, flow, [i[0] for i in graph["inits"]], shapes, pick=lambda cands, *_: pick(cands))
     return body, flow, shapes
+
+
+def steps_of(body, flow):
+    """[(kind, para, srcs, dst, name)] in flow order."""
+    k = {b[0]: b for b in body}
+    return [(k[names[0]][1], k[names[0]][2], _as_list(src), dst, names[0]) for src, names, dst in flow]
+
+
+def kinds_of(body, flow):
+    return [s[0] for s in steps_of(body, flow)]
+
+
+def run_on_oracle(graph, blob, x, body, flow, **standins):
+    """The program (body, flow) on the numpy oracle: plan-internal kinds as their NCHW operators (test_plan_fusion._q4_standins),
+    plus the stand-ins given by kind."""
+    from tests.test_plan_fusion import _q4_standins
+    saved = dict(onp.OPS)
+    onp.OPS.update(_q4_standins())
+    onp.OPS.update(standins)
+    try:
+        net = onp.OracleNet()
+        net.load_json(graph["input"], graph["inits"], body, flow)
+    finally:
+        onp.OPS.clear()
+        onp.OPS.update(saved)
+    net.load_weights(blob)
+    return net(x.copy())
 
 
 Q4_OUT = ("conv_q4", "convt_q4", "conv_pool_q4", "upconcat_q4", "to_q4", "wino4_out", "wino43_out", "wino4_chain", "wino43_chain")

@@ -10,7 +10,7 @@ import pytest
 from planer_amd import conv_layouts as cl
 from planer_amd import net as net_mod
 from planer_amd.irgen import customnet, mobilenetv2, resnet18, unet, yolov3
-from planer_amd.plan import assign_layouts, fuse_flow
+from planer_amd.plan import compile_front
 from tests.conftest import ROOT
 from tests.test_plan_fusion import shapes_of
 
@@ -104,15 +104,13 @@ def test_switches_take_candidates_out_and_winograd_0_times_nothing(monkeypatch):
 
 
 def _decisions(mod, batch, size, q4=True, **kw):
-    """What Net._prepare_filters decides for every conv of a generator net at this batch, with the picker taking the first
+    """What plan.lower decides for every conv of a generator net at this batch, with the picker taking the first
     and the last candidate: Counter of (kind, w_layout, suffix, candidates) per pick."""
     g, b = mod.build(**kw)
     inits = [i[0] for i in g["inits"]]
     shapes = {k: ((batch,) + tuple(s[1:]) if k not in inits and s is not None and len(s) and s[0] == 1 else s)
               for k, s in shapes_of(g, b, mod.make_input(1, size=size)).items()}
-    body, flow, _ = fuse_flow(g["layers"], g["flow"], inits, shapes)
-    if q4:
-        body, flow, _ = assign_layouts(body, flow, inits, shapes)
+    body, flow, _ = compile_front(g["layers"], g["flow"], inits, shapes, q4=q4, stop="assign_layouts")
     kinds = {e[0]: e for e in body}
     out = []
     for first in (True, False):

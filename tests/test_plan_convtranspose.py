@@ -12,7 +12,8 @@ from planer_amd.irgen import unet
 from planer_amd.layer import convt_out_hw, convt_phase_eligible
 from planer_amd.plan import ACT_RELU, assign_layouts, fuse_flow
 from tests.conftest import assert_close
-from tests.test_plan_fusion import _q4_standins, conv_fused_np, shapes_of
+from tests.plan_audit import cpu_front, run_on_oracle
+from tests.test_plan_fusion import conv_fused_np
 
 
 def phase_convt(x, K, B=None, strides=(2, 2), pads=(0, 0, 0, 0), output_padding=(0, 0)):
@@ -121,14 +122,12 @@ def test_generator_parameters_and_op_census(up):
 def _program(up, size):
     g, b = unet.build(up=up)
     x = unet.make_input(1, size=size)
-    shapes = shapes_of(g, b, x)
-    inits = [i[0] for i in g["inits"]]
-    body, flow, nf = fuse_flow(g["layers"], g["flow"], inits, shapes)
-    fused = (body, flow, nf)
-    body, flow, nq4 = assign_layouts(body, flow, inits, shapes)
+    body, flow, counts, _ = cpu_front(g, b, x, stop="fuse_flow")
+    fused = (body, flow, counts["fuse_flow"])
+    body, flow, counts, _ = cpu_front(g, b, x, stop="assign_layouts")
     kinds = {b_[0]: b_[1] for b_ in body}
     paras = {b_[0]: b_[2] for b_ in body}
-    return g, b, x, fused, [(kinds[f[1][0]], f[0], f[2], paras[f[1][0]]) for f in flow], nq4
+    return g, b, x, fused, [(kinds[f[1][0]], f[0], f[2], paras[f[1][0]]) for f in flow], counts["assign_layouts"]
 
 
 @pytest.mark.parametrize("up", ["k2", "k3"])
@@ -209,28 +208,16 @@ def convt_fused_np(x, K, B=None, scale=None, shift=None, res=None, act=0, alpha=
 
 @pytest.mark.parametrize("up", ["k2", "k3"])
 def test_unet_fused_and_layout_assigned_flow_matches_the_oracle(up):
-    g, b, x, _, _, _ = _program(up, 32)
-    shapes = shapes_of(g, b, x)
-    inits = [i[0] for i in g["inits"]]
-    body, flow, _ = fuse_flow(g["layers"], g["flow"], inits, shapes)
-    body, flow, nq4 = assign_layouts(body, flow, inits, shapes)
-    assert nq4 > 0 and any(b_[1] == "convt_q4" for b_ in body)
+    g, b = unet.build(up=up)
+    x = unet.make_input(1, size=32)
+    body, flow, counts, _ = cpu_front(g, b, x, stop="assign_layouts")
+    assert counts["assign_layouts"] > 0 and any(b_[1] == "convt_q4" for b_ in body)
 
     ref = onp.OracleNet()
     ref.load_json(g["input"], g["inits"], g["layers"], g["flow"])
     ref.load_weights(b)
     want = ref(x.copy())
 
-    saved = dict(onp.OPS)
-    onp.OPS.update(_q4_standins())
-    onp.OPS.update({"convt_q4": convt_fused_np, "convt_fused": convt_fused_np})
-    try:
-        net = onp.OracleNet()
-        net.load_json(g["input"], g["inits"], body, flow)
-    finally:
-        onp.OPS.clear()
-        onp.OPS.update(saved)
-    net.load_weights(b)
-    got = net(x.copy())
+    got = run_on_oracle(g, b, x, body, flow, convt_q4=convt_fused_np, convt_fused=convt_fused_np)
     assert got.shape == want.shape == (1, 2, 32, 32)
     assert_close(np.ascontiguousarray(got), np.ascontiguousarray(want), 1e-5)

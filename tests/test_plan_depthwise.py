@@ -6,9 +6,10 @@ import numpy as np
 
 from oracle import planer_np as onp
 from planer_amd.irgen import mobilenetv2
-from planer_amd.plan import assign_layouts, fuse_flow
+from planer_amd.plan import assign_layouts
 from tests.conftest import assert_close
-from tests.test_plan_fusion import _layout_program, _q4_standins, shapes_of
+from tests.plan_audit import cpu_front, run_on_oracle
+from tests.test_plan_fusion import _layout_program, _q4_standins
 
 
 def test_generator_parameters_and_op_census():
@@ -97,28 +98,15 @@ def _run_flow(layers, flow, env):
 def test_mobilenetv2_fused_and_layout_assigned_flow_matches_the_oracle():
     g, b = mobilenetv2.build()
     x = mobilenetv2.make_input(1, size=64)
-    shapes = shapes_of(g, b, x)
-    inits = [i[0] for i in g["inits"]]
-    body, flow, nf = fuse_flow(g["layers"], g["flow"], inits, shapes)
-    assert nf == 52 + 10                       # every batchnorm and every residual add folds into its conv
-    body, flow, nq4 = assign_layouts(body, flow, inits, shapes)
-    assert nq4 > 0
+    body, flow, counts, _ = cpu_front(g, b, x, stop="assign_layouts")
+    assert counts["fuse_flow"] == 52 + 10      # every batchnorm and every residual add folds into its conv
+    assert counts["assign_layouts"] > 0
 
     ref = onp.OracleNet()
     ref.load_json(g["input"], g["inits"], g["layers"], g["flow"])
     ref.load_weights(b)
     want = ref(x.copy())
 
-    saved = dict(onp.OPS)
-    onp.OPS.update(_q4_standins())
-    onp.OPS["clip_q4"] = onp.OPS["clip"]
-    try:
-        net = onp.OracleNet()
-        net.load_json(g["input"], g["inits"], body, flow)
-    finally:
-        onp.OPS.clear()
-        onp.OPS.update(saved)
-    net.load_weights(b)
-    got = net(x.copy())
+    got = run_on_oracle(g, b, x, body, flow, clip_q4=onp.OPS["clip"])
     assert got.shape == want.shape == (1, 1000)
     assert_close(np.ascontiguousarray(got), np.ascontiguousarray(want), 1e-5)

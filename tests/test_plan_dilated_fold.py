@@ -16,12 +16,11 @@ import pytest
 
 from planer_amd.irgen import drn
 from planer_amd.irgen.builder import GraphBuilder
-from planer_amd.plan import assign_layouts, fold_dilated, folded_key, fuse_flow, fuse_instnorm_q4
+from planer_amd.plan import fold_dilated, folded_key
 from tests import ref64
 from tests.conftest import GOLDEN
 from tests.fold_ref import fold_np, folded_shape, refold_np, unfold_np
-from tests.test_plan_fusion import shapes_of
-from tests.test_plan_instancenorm import _values
+from tests.plan_audit import cpu_front, steps_of
 
 ALWAYS = lambda xs, ks, para: True          # noqa: E731
 NEVER = lambda xs, ks, para: False          # noqa: E731
@@ -120,22 +119,14 @@ def _evaluate(graph, blob, x, body, flow):
 
 
 def _compile(g, b, x, worth=ALWAYS):
-    shapes = shapes_of(g, b, x)
-    inits = [i[0] for i in g["inits"]]
-    body, flow, _ = fuse_flow(g["layers"], g["flow"], inits, shapes)
-    body, flow, _ = assign_layouts(body, flow, inits, shapes, force=True, values=_values(g, b))
-    body, flow, _ = fuse_instnorm_q4(body, flow, shapes)
+    """The compiler's front half up to the pass (forced Q4), and what the pass makes of that program."""
+    body, flow, _, shapes = cpu_front(g, b, x, force=True, stop="fuse_linear_add")
     fbody, fflow, regions = fold_dilated(body, flow, shapes, worth)
     return (body, flow), (fbody, fflow), regions, shapes
 
 
-def _steps(body, flow):
-    k = {b[0]: b for b in body}
-    return [(k[names[0]][1], k[names[0]][2], src, dst, names[0]) for src, names, dst in flow]
-
-
 def _refolds(body, flow):
-    return [(src[0], tuple(p["from"]), tuple(p["to"]), dst) for kind, p, src, dst, _ in _steps(body, flow) if kind == "refold_q4"]
+    return [(src[0], tuple(p["from"]), tuple(p["to"]), dst) for kind, p, src, dst, _ in steps_of(body, flow) if kind == "refold_q4"]
 
 
 class _Ints:
@@ -230,8 +221,8 @@ def test_generator_op_census():
 
 def test_all_seven_heads_run_at_dilation_one_on_their_own_filter_keys(drn_plan):
     size, g, before, after, regions, shapes = drn_plan
-    was = {s[4]: s for s in _steps(*before)}
-    heads = [s for s in _steps(*after) if s[0] == "conv_q4" and was[s[4]][1]["dilations"] != [1, 1]]
+    was = {s[4]: s for s in steps_of(*before)}
+    heads = [s for s in steps_of(*after) if s[0] == "conv_q4" and was[s[4]][1]["dilations"] != [1, 1]]
     assert [s[4][:4] for s in heads] == HEADS
     for kind, para, src, dst, name in heads:
         d = was[name][1]["dilations"]
@@ -256,11 +247,11 @@ def test_regions_and_refolds_on_dividing_maps():
     assert _refolds(*after) == [("l30a_r", (1, 1), (2, 2), "l30a_r~2x2"), ("l30d_b", (1, 1), (2, 2), "l30d_b~2x2"),
                                 ("l40a_r~2x2", (2, 2), (4, 4), "l40a_r~4x4"), ("l40d_b~2x2", (2, 2), (4, 4), "l40d_b~4x4"),
                                 ("head~4x4", (4, 4), (1, 1), "head")]
-    names = [s[0] for s in _steps(*after)]
+    names = [s[0] for s in steps_of(*after)]
     assert names[-3:] == ["from_q4", "upsample", "return"] and names[-4] == "refold_q4"
     assert tuple(shapes["l40_o~4x4"]) == (16, 512, 2, 2) and tuple(shapes["l31_o~2x2"]) == (4, 256, 4, 4)
     # the 1x1 projection of layer4.0 and the head conv joined: they read and write folded tensors
-    s = {x[4]: x for x in _steps(*after)}
+    s = {x[4]: x for x in steps_of(*after)}
     assert s["l40d_conv+"][2][0] == "l31_o~2x2" and s["l40d_conv+"][3] == "l40d_b~2x2"
     assert s["head_conv"][2][0] == "l41_o~4x4" and s["head_conv"][3] == "head~4x4"
 
@@ -274,7 +265,7 @@ def test_every_conv_folds_alone_on_maps_the_dilation_does_not_divide():
     assert len(re) == 16 and len(outs) == 7 and len(ins) == 9 and not [r for r in re if (1, 1) not in r[1:3]]
     # seven inputs and the residuals of layer3.0 / layer4.0 (their projections); the other two residuals are cached copies
     assert [r[0] for r in ins] == ["l30a_r", "l30d_b", "l30_o", "l31a_r", "l31_o", "l40a_r", "l40d_b", "l40_o", "l41a_r"]
-    steps = _steps(*after)
+    steps = steps_of(*after)
     for i, s in enumerate(steps):
         if s[0] == "conv_q4" and s[4][:4] in HEADS:          # in, conv, out: the junk-tailed output has one reader, its unfold
             assert steps[i + 1][0] == "refold_q4" and steps[i + 1][2] == [s[3]] and steps[i + 1][1]["to"] == [1, 1]
@@ -309,15 +300,11 @@ def test_worth_is_asked_per_head_with_the_unfolded_shapes():
 
 def test_switch_off_program_is_the_parents(drn_plan):
     """tests/golden/drn_plan_before.json: fuse_flow + assign_layouts + fuse_instnorm_q4 on DRN at sizes 64 and 40, written by the
-    plan compiler before it had the pass.  With the switch off Net._fuse does not call it."""
+    plan compiler before it had the pass.  With the switch off Net._fuse gives plan.compile_front no `worth`, which leaves it out."""
     size = drn_plan[0]
     g, b = drn.build()
-    x = drn.make_input(1, size=size)
-    shapes = shapes_of(g, b, x)
-    inits = [i[0] for i in g["inits"]]
-    body, flow, nf = fuse_flow(g["layers"], g["flow"], inits, shapes)
-    body, flow, nq4 = assign_layouts(body, flow, inits, shapes, values=_values(g, b))
-    body, flow, _ = fuse_instnorm_q4(body, flow, shapes)
+    body, flow, counts, _ = cpu_front(g, b, drn.make_input(1, size=size))
+    nf, nq4 = counts["fuse_flow"], counts["assign_layouts"]
     want = json.load(open(os.path.join(GOLDEN, "drn_plan_before.json")))[str(size)]
     assert (nf, nq4) == (want["nfused"], want["nq4"])
     assert json.loads(json.dumps(body)) == want["body"] and json.loads(json.dumps(flow)) == want["flow"]
@@ -345,7 +332,7 @@ def test_in_place_relu_on_a_folded_tensor_with_a_later_unfolded_reader():
     y = m.g.op("add", [r, u], "sum", name="add")
     g, b, x = m.finish(y, 1, 8)
     before, after, regions, _ = _compile(g, b, x)
-    steps = _steps(*after)
+    steps = steps_of(*after)
     kinds = [s[0] for s in steps]
     assert kinds.count("relu_q4") == 1 and steps[kinds.index("relu_q4")][2] == ["h_b~2x2"] and steps[kinds.index("relu_q4")][3] == "r~2x2"
     # (fuse_flow made the add the residual of conv u, which is no member: both its operands are unfolded, behind the relu)
@@ -411,7 +398,7 @@ def test_a_region_that_ends_the_program_is_unfolded(side):
     flow = [[["x", "w", "None", "None", "None", "None"], ["c1"], "y1"], [["y1", "w", "None", "None", "None", "x"], ["c2"], "y2"]]
     shapes = {"x": (1, 4, side, side), "w": (4, 4, 3, 3), "y1": (1, 4, side, side), "y2": (1, 4, side, side)}
     fbody, fflow, regions = fold_dilated(body, flow, shapes)
-    assert _steps(fbody, fflow)[-1][0] == "refold_q4" and fflow[-1][2] == "y2" and len(_refolds(fbody, fflow)) == (2 if side == 8 else 4)
+    assert steps_of(fbody, fflow)[-1][0] == "refold_q4" and fflow[-1][2] == "y2" and len(_refolds(fbody, fflow)) == (2 if side == 8 else 4)
     x = ref64.int_tensor(rng, (1, 4, side, side))
     _same(g, K.view(np.uint8).reshape(-1), x, (body, flow), (fbody, fflow))
 

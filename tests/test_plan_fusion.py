@@ -7,6 +7,7 @@ from oracle import planer_np as onp
 from planer_amd.irgen import customnet, resnet18, yolov3
 from planer_amd.plan import ACT_LEAKY, ACT_RELU, ACT_RES_AFTER, assign_layouts, fuse_flow
 from tests.conftest import assert_close
+from tests.plan_audit import cpu_front, run_on_oracle
 
 
 def conv_fused_np(x, K, B=None, scale=None, shift=None, res=None, act=0, alpha=0.0, **conv):
@@ -138,14 +139,10 @@ def test_add_after_activation_needs_a_free_residual_slot():
 
 # ---- activation layout assignment (channel-quad plans) ----------------------------------------
 def _layout_program(mod, x):
-    g, b = mod.build()
-    shapes = shapes_of(g, b, x)
-    inits = [i[0] for i in g["inits"]]
-    body, flow, _ = fuse_flow(g["layers"], g["flow"], inits, shapes)
-    body, flow, nq4 = assign_layouts(body, flow, inits, shapes)
+    body, flow, counts, _ = cpu_front(*mod.build(), x, stop="assign_layouts")
     kinds = {b_[0]: b_[1] for b_ in body}
     paras = {b_[0]: b_[2] for b_ in body}
-    return [(kinds[f[1][0]], f[0], f[2], paras[f[1][0]]) for f in flow], nq4
+    return [(kinds[f[1][0]], f[0], f[2], paras[f[1][0]]) for f in flow], counts["assign_layouts"]
 
 
 def test_layouts_resnet18_one_conversion_in_none_out():
@@ -212,16 +209,7 @@ def _q4_standins():
 
 
 def _run(graph, blob, x, body, flow):
-    saved = dict(onp.OPS)
-    onp.OPS.update(_q4_standins())
-    try:
-        net = onp.OracleNet()
-        net.load_json(graph["input"], graph["inits"], body, flow)
-    finally:
-        onp.OPS.clear()
-        onp.OPS.update(saved)
-    net.load_weights(blob)
-    out = net(x)
+    out = run_on_oracle(graph, blob, x, body, flow)
     return out if isinstance(out, tuple) else (out,)
 
 
@@ -252,9 +240,9 @@ def test_random_graphs_fusion_and_layout_assignment_preserve_the_flow():
 
 
 def test_upsample_concat_peephole_and_its_guards():
-    """Net._fuse_upsample_concat (host logic): upsample_q4 -> concat_q4 becomes one upconcat_q4 step, unless the
+    """plan.fuse_upsample_concat: upsample_q4 -> concat_q4 becomes one upconcat_q4 step, unless the
     upsampled tensor has another reader, is not the concat's first input, or its source is touched in between."""
-    from planer_amd.net import Net
+    from planer_amd.plan import fuse_upsample_concat
 
     def prog(extra_reader=False, first=True, touch=False):
         body = {"up": ["up", "upsample_q4", {"mode": "nearest"}], "cat": ["cat", "concat_q4", {"axis": 1}],
@@ -268,11 +256,11 @@ def test_upsample_concat_peephole_and_its_guards():
         return body, flow
 
     body, flow = prog()
-    out = Net._fuse_upsample_concat(body, flow)
+    out = fuse_upsample_concat(body, flow)
     assert out == [[["a", "k", "b"], ["cat"], "c"]] and body["cat"][1] == "upconcat_q4"
     for kw in ({"extra_reader": True}, {"first": False}, {"touch": True}):
         body, flow = prog(**kw)
-        assert Net._fuse_upsample_concat(body, flow) == flow and body["cat"][1] == "concat_q4", kw
+        assert fuse_upsample_concat(body, flow) == flow and body["cat"][1] == "concat_q4", kw
 
 
 # ---- Winograd chaining (plan.chain_winograd): pure host logic ------------------------------------------

@@ -9,13 +9,12 @@ import numpy as np
 import pytest
 
 from planer_amd.irgen import resnet_gn
-from planer_amd.plan import (_FOLD_POINTWISE, _IN_PLACE, _PURE_READERS, Q4_POINTWISE, assign_layouts, fuse_flow, fuse_groupnorm,
-                             fuse_instnorm_q4, fuse_linear_add, groupnorm_q4_ok)
+from planer_amd import plan
+from planer_amd.plan import _FOLD_POINTWISE, _IN_PLACE, _PURE_READERS, Q4_POINTWISE, fuse_groupnorm, groupnorm_q4_ok
 from tests import ref64_ops as R
-from tests.groupnorm_ref import (compile_plan, emulate, five_steps, kinds_of, make_x, operands, reference, run_on_oracle, sandwich,
-                                 steps_of, values_of)
+from tests.groupnorm_ref import (compile_plan, cpu_front, emulate, five_steps, kinds_of, make_x, operands, reference, run_on_oracle,
+                                 sandwich, steps_of)
 from tests.linear_q4_ref import Small, assert_same_bits
-from tests.test_plan_fusion import shapes_of
 
 ONE_STEP = ["to_q4", "conv_q4", "groupnorm_q4", "conv_q4", "from_q4", "return"]
 
@@ -30,10 +29,8 @@ def _norm(flow):
 
 def _fused(g, b, x):
     """fuse_flow's program and what fuse_groupnorm makes of it -> (body, flow, body', flow', n)."""
-    shapes = shapes_of(g, b, x)
-    inits = [i[0] for i in g["inits"]]
-    body, flow, _ = fuse_flow(g["layers"], g["flow"], inits, shapes)
-    return (body, flow) + tuple(fuse_groupnorm(body, flow, shapes, inits))
+    body, flow, _, shapes = cpu_front(g, b, x, stop="fuse_flow")
+    return (body, flow) + tuple(fuse_groupnorm(body, flow, shapes, [i[0] for i in g["inits"]]))
 
 
 def _left_alone(g, b, x):
@@ -250,12 +247,9 @@ def test_a_residual_rewritten_between_the_add_and_the_relu_breaks_the_chain():
 def test_switch_off_gives_the_program_without_the_pass(monkeypatch):
     g, b = sandwich()
     x = make_x()
-    shapes = shapes_of(g, b, x)
-    inits = [i[0] for i in g["inits"]]
-    body, flow, _ = fuse_flow(g["layers"], g["flow"], inits, shapes)
-    body, flow, _ = assign_layouts(body, flow, inits, shapes, force=True, values=values_of(g, b))
-    body, flow, _ = fuse_instnorm_q4(body, flow, shapes)
-    want = fuse_linear_add(body, flow, shapes)[:2]
+    with monkeypatch.context() as m:             # the compiler with the pass taken out
+        m.setattr(plan, "fuse_groupnorm", lambda body, flow, *_: (body, flow, 0))
+        want = compile_plan(g, b, x)[:2]
     monkeypatch.setenv("PLANER_HIP_GROUPNORM_Q4", "0")
     got = compile_plan(g, b, x)
     assert got[2] == 0 and (got[0], got[1]) == want

@@ -12,41 +12,21 @@ import pytest
 from oracle import planer_np as onp
 from planer_amd.irgen import stylenet
 from planer_amd.irgen.builder import GraphBuilder
-from planer_amd.plan import ACT_NONE, ACT_RELU, assign_layouts, fuse_flow, fuse_instnorm_q4, pad_q4_ok
+from planer_amd.plan import ACT_NONE, ACT_RELU, assign_layouts, fuse_instnorm_q4, pad_q4_ok
 from tests.conftest import GOLDEN, assert_close
-from tests.test_plan_fusion import _q4_standins, shapes_of
-
-
-def _values(graph, blob):
-    """key -> host array of an init, as Net._fuse hands them to assign_layouts."""
-    out, pos = {}, 0
-    for name, shape, dt in graph["inits"]:
-        n = int(np.prod(shape, dtype=np.int64)) * np.dtype(dt).itemsize
-        out[name] = blob[pos:pos + n].view(dt).reshape(shape)
-        pos += n
-    return lambda key: out.get(key)
+from tests.plan_audit import blob_inits, cpu_front, run_on_oracle, steps_of
+from tests.test_plan_fusion import shapes_of
 
 
 def _compile(g, b, x, fuse=True, force=False):
-    shapes = shapes_of(g, b, x)
-    inits = [i[0] for i in g["inits"]]
-    body, flow, _ = fuse_flow(g["layers"], g["flow"], inits, shapes)
-    body, flow, nq4 = assign_layouts(body, flow, inits, shapes, force=force, values=_values(g, b))
-    nf = 0
-    if fuse:
-        body, flow, nf = fuse_instnorm_q4(body, flow, shapes)
-    return body, flow, nq4, nf, shapes
+    body, flow, counts, shapes = cpu_front(g, b, x, force, stop="fuse_instnorm_q4" if fuse else "assign_layouts")
+    return body, flow, counts["assign_layouts"], counts.get("fuse_instnorm_q4", 0), shapes
 
 
 @pytest.fixture(scope="module")
 def style():
     g, b = stylenet.build()
     return g, b, stylenet.make_input(1, size=32)
-
-
-def _kinds(body, flow):
-    k = {b[0]: b for b in body}
-    return [(k[names[0]][1], k[names[0]][2], src, dst) for src, names, dst in flow]
 
 
 def test_generator_parameters_and_op_census(style):
@@ -61,7 +41,7 @@ def test_generator_parameters_and_op_census(style):
 def test_style_net_is_one_q4_run_with_fused_norm_tails(style):
     g, b, x = style
     body, flow, nq4, nf, _ = _compile(g, b, x)
-    steps = _kinds(body, flow)
+    steps = steps_of(body, flow)
     names = [s[0] for s in steps]
     first_conv = names.index("conv_q4")
     # no conversion between the first conv and the single final from_q4 (ahead of `return`)
@@ -86,17 +66,7 @@ def _in_q4(x, s, b, res=None, epsilon=1e-5, act=0):
 
 
 def _run(g, b, x, body, flow):
-    saved = dict(onp.OPS)
-    onp.OPS.update(_q4_standins())
-    onp.OPS.update({"instancenormalization_q4": _in_q4, "pad_q4": onp.OPS["pad"]})
-    try:
-        net = onp.OracleNet()
-        net.load_json(g["input"], g["inits"], body, flow)
-    finally:
-        onp.OPS.clear()
-        onp.OPS.update(saved)
-    net.load_weights(b)
-    return net(x.copy())
+    return run_on_oracle(g, b, x, body, flow, instancenormalization_q4=_in_q4, pad_q4=onp.OPS["pad"])
 
 
 def test_compiled_style_program_matches_the_oracle(style):
@@ -131,11 +101,11 @@ def _fused_norm(tail, force=True):
     g, b, x = _small(tail)
     shapes = shapes_of(g, b, x)
     inits = [i[0] for i in g["inits"]]
-    body, flow, _ = assign_layouts(g["layers"], g["flow"], inits, shapes, force=force, values=_values(g, b))
+    body, flow, _ = assign_layouts(g["layers"], g["flow"], inits, shapes, force=force, values=blob_inits(g, b).get)
     body2, flow2, nf = fuse_instnorm_q4(body, flow, shapes)
     want = _run(g, b, x, g["layers"], g["flow"])
     assert_close(np.ascontiguousarray(_run(g, b, x, body2, flow2)), np.ascontiguousarray(want), 1e-5)
-    return _kinds(body2, flow2), nf
+    return steps_of(body2, flow2), nf
 
 
 def test_fuse_residual_then_relu():
@@ -221,7 +191,7 @@ def test_converted_copies_are_dropped_when_an_nchw_norm_rewrites_their_tensor(mo
     graph, blob = g.finish(["sum"])
     shapes = shapes_of(graph, blob, x)
     inits = [i[0] for i in graph["inits"]]
-    body, flow, _ = assign_layouts(graph["layers"], graph["flow"], inits, shapes, force=True, values=_values(graph, blob))
+    body, flow, _ = assign_layouts(graph["layers"], graph["flow"], inits, shapes, force=True, values=blob_inits(graph, blob).get)
     text = _flow_text(body, flow)
     assert text.count("to_q4 x -> x@q4") == 2 and text.index("instancenormalization x,s,t -> n") < len(text) - 1 - text[::-1].index("to_q4 x -> x@q4"), text
     assert_close(_run(graph, blob, x, body, flow), _run(graph, blob, x, graph["layers"], graph["flow"]), 1e-5)
@@ -240,7 +210,7 @@ def test_converted_copies_are_dropped_when_an_nchw_norm_rewrites_their_tensor(mo
     graph, blob = g.finish(["all"])
     shapes = shapes_of(graph, blob, x)
     inits = [i[0] for i in graph["inits"]]
-    body, flow, _ = assign_layouts(graph["layers"], graph["flow"], inits, shapes, force=True, values=_values(graph, blob))
+    body, flow, _ = assign_layouts(graph["layers"], graph["flow"], inits, shapes, force=True, values=blob_inits(graph, blob).get)
     text = _flow_text(body, flow)
     assert "instancenormalization ca@nchw,s,t -> n" in text and "to_q4 ca@nchw -> ca" in text, text
     assert text.count("from_q4 ca -> ca@nchw") == 2, text
@@ -272,5 +242,5 @@ def test_switch_off_gives_the_program_of_a_compiler_without_the_new_kinds(style,
     want = json.load(open(os.path.join(GOLDEN, "stylenet_plan_before.json")))
     assert nf == 0 and nq4 == want["nq4"]
     assert json.loads(json.dumps(body)) == want["body"] and json.loads(json.dumps(flow)) == want["flow"]
-    names = [s[0] for s in _kinds(body, flow)]
+    names = [s[0] for s in steps_of(body, flow)]
     assert names.count("from_q4") >= 15 and "pad_q4" not in names and "instancenormalization_q4" not in names

@@ -6,11 +6,10 @@ import pytest
 
 from planer_amd.irgen import edsr
 from planer_amd.irgen.builder import save_model
-from planer_amd.plan import fuse_flow, fuse_pixel_shuffle, match_pixel_shuffle
+from planer_amd.plan import fuse_pixel_shuffle, match_pixel_shuffle
 from tests.linear_q4_ref import Small, assert_same_bits
-from tests.pixel_shuffle_ref import (AXES, FORM_IDS, FORMS, compile_plan, kinds_of, make_x, mid_shape, out_shape, run_on_oracle, sandwich,
-                                     shuffle_np, steps_of, trio)
-from tests.test_plan_fusion import shapes_of
+from tests.pixel_shuffle_ref import (AXES, FORM_IDS, FORMS, compile_plan, cpu_front, kinds_of, make_x, mid_shape, out_shape, run_on_oracle,
+                                     sandwich, shuffle_np, steps_of, trio)
 
 
 def _original(g, b, x):
@@ -53,8 +52,7 @@ def test_the_stand_in_is_the_trio_and_crd_is_torch_pixel_shuffle():
 
 
 def _unchanged(g, b, x):
-    shapes = shapes_of(g, b, x)
-    body, flow, _ = fuse_flow(g["layers"], g["flow"], [i[0] for i in g["inits"]], shapes)
+    body, flow, _, shapes = cpu_front(g, b, x, stop="fuse_flow")
     body2, flow2, n = fuse_pixel_shuffle(body, flow, shapes)
     assert n == 0
     assert [list(e) for e in body2] == [list(e) for e in body]
@@ -173,16 +171,12 @@ def test_a_shuffle_whose_result_is_read_again_before_the_return_keeps_a_q4_resul
 
 @pytest.mark.parametrize("form", FORMS, ids=FORM_IDS)
 def test_switch_off_gives_the_program_without_the_pass(form, monkeypatch):
-    from planer_amd.plan import assign_layouts, fuse_instnorm_q4, fuse_linear_add
-    from tests.linear_q4_ref import values_of
+    from planer_amd import plan
     g, b = sandwich(*form)
     x = make_x()
-    shapes = shapes_of(g, b, x)
-    inits = [i[0] for i in g["inits"]]
-    body, flow, _ = fuse_flow(g["layers"], g["flow"], inits, shapes)
-    body, flow, _ = assign_layouts(body, flow, inits, shapes, force=True, values=values_of(g, b))
-    body, flow, _ = fuse_instnorm_q4(body, flow, shapes)
-    want = fuse_linear_add(body, flow, shapes)[:2]
+    with monkeypatch.context() as m:             # the compiler with the pass taken out
+        m.setattr(plan, "fuse_pixel_shuffle", lambda body, flow, *_: (body, flow, 0))
+        want = compile_plan(g, b, x)[:2]
     monkeypatch.setenv("PLANER_HIP_PIXEL_SHUFFLE_Q4", "0")
     got = compile_plan(g, b, x)
     assert got[2] == 0 and (got[0], got[1]) == want
