@@ -12,6 +12,10 @@ transposed conv that the phase-decomposed kernel runs heads the same chains
 intermediate tensor has exactly one reader and one writer, so nothing a user
 could observe disappears; the fused step sits where the LAST link of its
 chain was, so a residual operand produced after the conv is still available.
+
+Programs pass from pass to pass as (body, flow).  Inside a pass they are read through `Steps` -- one step per layer, who reads
+and writes each key, the two predicates that make moving a read sound (`only_reader`, `clobbered`) and the one epilogue that
+rebuilds a body (`emit`) -- and what a kind does to its operands is looked up in one table, `KINDS`.
 """
 import os
 
@@ -27,13 +31,103 @@ def _as_list(v):
     return list(v) if isinstance(v, (list, tuple)) else [v]
 
 
-def expand_steps(flow):
-    """Chained steps [x, [l1, l2], y] -> one step per layer (net.py:46-50)."""
-    steps = []
-    for src, names, dst in flow:
-        for pos, name in enumerate(_as_list(names)):
-            steps.append((_as_list(src if pos == 0 else dst), name, dst))
-    return steps
+# ---- what a kind does to its operands: ONE table, every list of kinds below is read off it ---------------------------------------
+# W    rewrites srcs[0] in place and hands it on (layer.py:46, 217-226, 250-258): a read of that tensor may not move across it
+# R    only reads its inputs: a Winograd input transform may be hoisted over it (chain_winograd)
+# F    position-independent: runs unchanged on tensors folded by pixel phase (fold_dilated)
+# Q..  has a channel-quad kernel, kind + "_q4" (planer_amd/q4.py: Q4_LAYERS); QI and QL are those a switch takes out again
+# A kind with none of them is none of these: it writes a tensor of its own, nothing is hoisted over it, it reads unfolded NCHW.
+# Every kind a plan can hold has a row (tests/test_plan_kinds.py), so a new kind states whether it writes in place.
+W, R, F, Q, QI, QL = "in place", "pure reader", "folds", "q4", "q4/PLANER_HIP_INSTNORM_Q4", "q4/PLANER_HIP_LINEAR_Q4"
+KINDS = {
+    # the reference's operators (layer.layer_map)
+    "maxpool": (Q,), "averagepool": (Q,), "gap": (Q,), "upsample": (Q,), "batchnorm": (Q,), "relu": (W, Q), "leakyrelu": (Q,),
+    "sigmoid": (Q,), "add": (Q,), "concat": (Q,), "clip": (W, Q), "instancenormalization": (W, QI), "pad": (QI,), "resize": (QL,),
+    "erf": (W,), "dense": (), "conv": (), "convtranspose": (), "flatten": (), "matmul": (), "identity": (), "return": (),
+    "sub": (), "mul": (), "div": (), "pow": (), "exp": (), "log": (), "tanh": (), "sqrt": (), "reciprocal": (), "hardsigmoid": (),
+    "softmax": (), "logsoftmax": (), "reducesum": (), "reducemean": (), "reducemax": (), "reducemin": (), "transpose": (),
+    "reshape": (), "squeeze": (), "unsqueeze": (), "slice": (), "tile": (), "expand": (), "split": (), "shape": (), "const": (),
+    "constantofshape": (), "range": (), "cast": (), "equal": (), "greater": (), "greaterorequal": (), "where": (), "gather": (),
+    "scatternd": (), "nonzero": (), "topk": (), "lstm": (),
+    # what the passes in front of assign_layouts make
+    "conv_fused": (), "convt_fused": (), "pixelshuffle": (Q,), "groupnorm": (W, Q),
+    # the channel-quad forms
+    "maxpool_q4": (R,), "averagepool_q4": (R,), "gap_q4": (R,), "upsample_q4": (R,), "batchnorm_q4": (R, F), "relu_q4": (W, F),
+    "leakyrelu_q4": (R, F), "sigmoid_q4": (R, F), "add_q4": (R, F), "concat_q4": (R, F), "clip_q4": (W, F),
+    "instancenormalization_q4": (W,), "pad_q4": (R,), "resize_q4": (R,), "pixelshuffle_q4": (R,), "groupnorm_q4": (W,),
+    # plan-internal (q4.register)
+    "to_q4": (), "from_q4": (R,), "refold_q4": (R,), "conv_q4": (R,), "convt_q4": (R,), "conv_q4_pair": (R,), "conv_pool_q4": (),
+    "upconcat_q4": (R,), "upsample_add_q4": (R,), "resize_add_q4": (R,), "conv1x1_wino_in": (R,),
+    "wino4_in": (R,), "wino4_gemm": (R,), "wino4_out": (R,), "wino4_chain": (R,),
+    "wino43_in": (R,), "wino43_gemm": (R,), "wino43_out": (R,), "wino43_chain": (R,),
+}
+
+
+def _kinds_with(*traits):
+    return tuple(k for k, t in KINDS.items() if any(x in t for x in traits))
+
+
+_IN_PLACE, _PURE_READERS, _FOLD_POINTWISE = _kinds_with(W), _kinds_with(R), _kinds_with(F)
+# (instancenormalization_q4 never joins a fold; fold_dilated's list has named it since the norm got its Q4 form, and keeps it)
+_FOLD_IN_PLACE = tuple(k for k in _FOLD_POINTWISE if k in _IN_PLACE) + ("instancenormalization_q4",)
+
+
+class Steps:
+    """The view every pass takes of a (body, flow) program.  `steps`: one [srcs list, name, dst] per layer, chained steps
+    [x, [l1, l2], y] taken apart (net.py:46-50).  `layers`: name -> (kind, para).  `readers`, `writers`: key -> the indices of
+    the steps that read / write it, each once and in order."""
+
+    def __init__(self, body, flow):
+        self.layers = {b[0]: (b[1], b[2]) for b in body}
+        self.steps = [[_as_list(src if pos == 0 else dst), name, dst]
+                      for src, names, dst in flow for pos, name in enumerate(_as_list(names))]
+        self.readers, self.writers = {}, {}
+        for i, (srcs, _, dst) in enumerate(self.steps):
+            for k in set(srcs):
+                self.readers.setdefault(k, []).append(i)
+            for k in _as_list(dst):
+                self.writers.setdefault(k, []).append(i)
+
+    def kind(self, i):
+        return self.layers[self.steps[i][1]][0]
+
+    def step(self, i):
+        """Step i as passes emit it: (srcs, name, kind, para, dst)."""
+        srcs, name, dst = self.steps[i]
+        return (srcs, name) + tuple(self.layers[name]) + (dst,)
+
+    def each(self):
+        return [self.step(i) for i in range(len(self.steps))]
+
+    def only_reader(self, i, dst):
+        """The one step that reads `dst`, a single tensor written once (by step i), where it comes later; else None.  What lets
+        a pass absorb the reader into step i: nothing a user could observe disappears with `dst`."""
+        if not isinstance(dst, str) or len(self.readers.get(dst, ())) != 1 or len(self.writers.get(dst, ())) != 1:
+            return None
+        return self.readers[dst][0] if self.readers[dst][0] > i else None
+
+    def clobbers(self, t, key, in_place=_IN_PLACE, writes=True):
+        """Step t reads `key` and is of a kind in `in_place` (None: any reader counts), or -- with `writes` -- writes `key`."""
+        srcs, _, dst = self.steps[t]
+        return (key in srcs and (in_place is None or self.kind(t) in in_place)) or (writes and key in _as_list(dst))
+
+    def clobbered(self, key, lo, hi, skip=(), **rule):
+        """A step strictly between lo and hi, those in `skip` apart, clobbers `key`: a read of it may not move from lo to hi."""
+        return any(self.clobbers(t, key, **rule) for t in range(lo + 1, hi) if t not in skip)
+
+    def spliced(self, at, dropped=()):
+        """-> [(srcs, name, kind, para, dst)]: the steps with `at[i]` in place of step i and those in `dropped` gone."""
+        return [at[i] if i in at else self.step(i) for i in range(len(self.steps)) if i in at or i not in dropped]
+
+    @staticmethod
+    def emit(out):
+        """[(srcs, name, kind, para, dst)] -> (body, flow): each layer once, in the order of first use; one layer per step."""
+        body, seen = [], set()
+        for srcs, name, kind, para, dst in out:
+            if name not in seen:
+                seen.add(name)
+                body.append([name, kind, para])
+        return body, [[srcs, [name], dst] for srcs, name, kind, para, dst in out]
 
 
 def convt_ok(srcs, para, inits, shapes):
@@ -49,18 +143,11 @@ def fuse_flow(layers, flow, init_names, shapes):
     `shapes` maps tensor keys to shapes (from one eager pass); a residual add
     is folded only when both operands have the same known shape.
     """
-    kinds = {name: (kind, para) for name, kind, para in layers}
-    steps = expand_steps(flow)
-    readers, writers = {}, {}
-    for i, (srcs, _, dst) in enumerate(steps):
-        for k in set(srcs):
-            readers.setdefault(k, []).append(i)
-        for k in _as_list(dst):
-            writers[k] = writers.get(k, 0) + 1
-    inits = set(init_names)
+    view = Steps(layers, flow)
+    steps, inits = view.steps, set(init_names)
     consumed, fused_at, nfused = set(), {}, 0
     for i, (srcs, name, dst) in enumerate(steps):
-        kind, para = kinds[name]
+        kind, para = view.layers[name]
         if i in consumed or not isinstance(dst, str):
             continue
         if kind != "conv" and not (kind == "convtranspose" and convt_ok(srcs, para, inits, shapes)):
@@ -68,18 +155,14 @@ def fuse_flow(layers, flow, init_names, shapes):
         chain, cur, stage = [i], dst, 0
         extra = {"scale": "None", "shift": "None", "res": "None", "act": ACT_NONE, "alpha": 0.0}
         while stage < 4:
-            r = readers.get(cur, [])
-            if len(r) != 1 or writers.get(cur, 0) != 1:
+            j = view.only_reader(chain[-1], cur)
+            if j is None or j in consumed or not isinstance(steps[j][2], str):
                 break
-            j = r[0]
             jsrcs, jname, jdst = steps[j]
-            jkind, jpara = kinds[jname]
-            if j in consumed or j <= chain[-1] or not isinstance(jdst, str):
-                break
+            jkind, jpara = view.layers[jname]
             # an in-place relu on one of the conv's inputs between here and j would
             # change what the delayed conv reads (layer.py:46 mutates its input)
-            if any(kinds[steps[s][1]][0] == "relu" and steps[s][0][0] in srcs
-                   for s in range(chain[-1] + 1, j) if s not in chain):
+            if any(view.clobbered(k, chain[-1], j, chain, in_place=("relu",), writes=False) for k in srcs):
                 break
             if (jkind == "batchnorm" and stage < 1 and len(jsrcs) == 3 and jsrcs[0] == cur
                     and jsrcs[1] in inits and jsrcs[2] in inits):
@@ -102,28 +185,11 @@ def fuse_flow(layers, flow, init_names, shapes):
             cur = jdst
         if len(chain) > 1:
             consumed.update(chain)
-            fused_at[chain[-1]] = (srcs, name, kind, para, extra, cur)
+            args = [srcs[0], srcs[1], srcs[2] if len(srcs) > 2 else "None", extra["scale"], extra["shift"], extra["res"]]
+            fused_at[chain[-1]] = (args, name + "+", "conv_fused" if kind == "conv" else "convt_fused",
+                                   dict(para, act=extra["act"], alpha=extra["alpha"]), cur)
             nfused += len(chain) - 1
-    body, out_flow, seen = [], [], set()
-
-    def add_layer(entry):
-        if entry[0] not in seen:
-            seen.add(entry[0])
-            body.append(entry)
-
-    for i, (srcs, name, dst) in enumerate(steps):
-        if i in fused_at:
-            csrcs, cname, ckind, cpara, extra, out = fused_at[i]
-            para = dict(cpara, act=extra["act"], alpha=extra["alpha"])
-            args = [csrcs[0], csrcs[1], csrcs[2] if len(csrcs) > 2 else "None",
-                    extra["scale"], extra["shift"], extra["res"]]
-            add_layer([cname + "+", "conv_fused" if ckind == "conv" else "convt_fused", para])
-            out_flow.append([args, [cname + "+"], out])
-        elif i not in consumed:
-            kind, para = kinds[name]
-            add_layer([name, kind, para])
-            out_flow.append([srcs, [name], dst])
-    return body, out_flow, nfused
+    return view.emit(view.spliced(fused_at, consumed)) + (nfused,)
 
 
 # ---- activation layout assignment -------------------------------------------------------------
@@ -131,11 +197,10 @@ def fuse_flow(layers, flow, init_names, shapes):
 # these kinds runs in Q4 when one of its activation inputs already is Q4 -- layouts are "sticky"
 # downstream of a conv -- and everything else reads NCHW, with a conversion step inserted where a
 # value is needed in the layout it was not produced in (converted copies are cached per value).
-Q4_POINTWISE = ("maxpool", "averagepool", "gap", "upsample", "batchnorm", "relu", "leakyrelu", "sigmoid",
-                "add", "concat", "clip", "instancenormalization", "pad", "resize", "pixelshuffle", "groupnorm")
+Q4_POINTWISE = _kinds_with(Q, QI, QL)
 # the kinds of instance-normalised generators (fast-neural-style, CycleGAN ...): PLANER_HIP_INSTNORM_Q4=0 takes them out again,
 # which gives the program of a compiler without them
-INSTNORM_Q4_KINDS = ("instancenormalization", "pad")
+INSTNORM_Q4_KINDS = _kinds_with(QI)
 PAD_MODES = ("constant", "wrap", "edge", "reflect", "symmetric")
 TO_Q4, FROM_Q4 = "@to_q4", "@from_q4"
 
@@ -143,7 +208,7 @@ TO_Q4, FROM_Q4 = "@to_q4", "@from_q4"
 # bilinear interpolation between convs (FPN top-down paths, segmentation decoders): PLANER_HIP_LINEAR_Q4=0 takes linear
 # `upsample` and the WHOLE of `resize` out again -- nearest `resize` too, although the switch is named after the linear kernels:
 # no `resize` ran in Q4 before them, and the switch's contract is the program of a compiler without this change
-LINEAR_Q4_KINDS = ("resize",)
+LINEAR_Q4_KINDS = _kinds_with(QL)
 
 
 def linear_q4_enabled():
@@ -158,6 +223,17 @@ def q4_pointwise_kinds():
     if not linear_q4_enabled():
         kinds = tuple(k for k in kinds if k not in LINEAR_Q4_KINDS)
     return kinds
+
+
+def _copy_of(body, flow):
+    """A program as it came, in its own form: what a pass hands back where nothing matched."""
+    return [list(b) for b in body], [[list(s) if isinstance(s, (list, tuple)) else s, n, d] for s, n, d in flow]
+
+
+def _shape(shapes, key):
+    """The shape of a tensor by its key (a converted copy, key@q4, has its tensor's), as a tuple, or None."""
+    s = shapes.get(key.split("@")[0])
+    return None if s is None else tuple(s)
 
 
 def _is4d(shapes, key):
@@ -321,18 +397,15 @@ def assign_layouts(body, flow, init_names, shapes, force=False, values=None):
     Unless `force`, the rewrite is dropped (-> the input program, 0) when the conversions it needs
     would cost more than the convs gain -- e.g. a lone conv whose large output has to be handed
     back as NCHW right away."""
-    kinds = {name: (kind, para) for name, kind, para in body}
-    inits = set(init_names)
-    steps = expand_steps(flow)
+    view = Steps(body, flow)
+    kinds, steps, inits = view.layers, view.steps, set(init_names)
     q4 = set()          # keys whose primary copy is Q4
     copies = {}         # (key, layout) -> key of the cached converted copy
-    out_body, out_flow, seen = [], [], set()
-    nq4 = 0
+    out, nq4 = [], 0    # out: (srcs, name, kind, para, dst)
 
-    def add_layer(entry):
-        if entry[0] not in seen:
-            seen.add(entry[0])
-            out_body.append(list(entry))
+    def convert(key, to_q4, dst):
+        name = TO_Q4 if to_q4 else FROM_Q4
+        out.append(([key], name, name[1:], {}, dst))
 
     est = {"gain": 0.0, "cost": 0.0}
 
@@ -344,9 +417,7 @@ def assign_layouts(body, flow, init_names, shapes, force=False, values=None):
             if shapes.get(key.split("@")[0]) is not None:
                 est["cost"] += _nbytes(shapes[key.split("@")[0]]) * _CONVERT_S_PER_BYTE
             ck = key + ("@q4" if want_q4 else "@nchw")
-            conv_name = TO_Q4 if want_q4 else FROM_Q4
-            add_layer([conv_name, conv_name[1:], {}])
-            out_flow.append([[key], [conv_name], ck])
+            convert(key, want_q4, ck)
             copies[(key, want_q4)] = ck
             if want_q4:
                 q4.add(ck)
@@ -411,25 +482,22 @@ def assign_layouts(body, flow, init_names, shapes, force=False, values=None):
         if not as_q4:
             args = [need(k, False) for k in srcs]
             new_kind = kind
-        if kind in ("relu", "clip", "instancenormalization", "groupnorm"):   # in place (layer.py:46, 217-226, 250-251): cached
-            drop_copies(srcs[0])                                             # copies of the input go stale
+        if kind in _IN_PLACE and kind in Q4_POINTWISE:   # (layer.py:46, 217-226, 250-251): cached copies of the input go stale
+            drop_copies(srcs[0])                         # (not for `erf`, the in-place kind without a Q4 form: DESIGN, asymmetries)
         out_key = dst
         produces_q4 = as_q4 and kind != "gap" and not (kind == "pixelshuffle" and para.get("nchw_out"))
         if produces_q4 and i == last:
             out_key = dst + "@q4"                # the program's result is handed back as NCHW below
-        add_layer([name, new_kind, para])
-        out_flow.append([args, [name], out_key])
+        out.append((args, name, new_kind, para, out_key))
         if kind == "clip" and not as_q4 and srcs[0] in q4 and i != last:
             # clipped in place on its NCHW copy (a partial quad that clip would dirty): later readers of the input must
             # see the clipped values, so the Q4 primary is made again from that copy
-            add_layer([TO_Q4, TO_Q4[1:], {}])
-            out_flow.append([[args[0]], [TO_Q4], srcs[0]])
+            convert(args[0], True, srcs[0])
         if (kind == "instancenormalization" and not as_q4 and srcs[0] in q4
                 and any(srcs[0] in s_ for s_, _, _ in steps[i + 1:])):
             # likewise for an instance norm that stays NCHW (a scale computed by the graph, or the switch off) where the tensor it
             # rewrote has later readers
-            add_layer([TO_Q4, TO_Q4[1:], {}])
-            out_flow.append([[args[0]], [TO_Q4], srcs[0]])
+            convert(args[0], True, srcs[0])
         for k in _as_list(dst):
             q4.discard(k)
             drop_copies(k)
@@ -437,15 +505,14 @@ def assign_layouts(body, flow, init_names, shapes, force=False, values=None):
             q4.add(out_key)
             nq4 += 1
             if i == last:
-                add_layer([FROM_Q4, FROM_Q4[1:], {}])
-                out_flow.append([[out_key], [FROM_Q4], dst])
+                convert(out_key, False, dst)
                 if shapes.get(dst) is not None:
                     est["cost"] += _nbytes(shapes[dst]) * _CONVERT_S_PER_BYTE
         elif as_q4:
             nq4 += 1
     if not force and est["cost"] > est["gain"]:
         return [list(b) for b in body], [[list(srcs), [name], dst] for srcs, name, dst in steps], 0
-    return out_body, out_flow, nq4
+    return view.emit(out) + (nq4,)
 
 
 # ---- instance norm and group norm tails ------------------------------------------------------------------
@@ -461,44 +528,28 @@ def fuse_instnorm_q4(body, flow, shapes):
     then activation -- so a relu that comes first ends the chain and the add behind it stays a step of its own.  As in
     fuse_flow a link is absorbed only when the tensor between has one reader and one writer, and the fused step sits where the
     last link was.  The norm works in place, so it is only moved when nothing else ever reads the tensor it rewrites."""
-    kinds = {b[0]: b for b in body}
-    steps = [[list(src) if isinstance(src, (list, tuple)) else [src], names[0] if isinstance(names, (list, tuple)) else names, dst]
-             for src, names, dst in flow]
-    readers, writers = {}, {}
-    for i, (srcs, name, dst) in enumerate(steps):
-        for k in set(srcs):
-            readers.setdefault(k, []).append(i)
-        for k in _as_list(dst):
-            writers[k] = writers.get(k, 0) + 1
-
-    def shape(key):
-        s = shapes.get(key.split("@")[0])
-        return None if s is None else tuple(s)
-
+    view = Steps(body, flow)
+    steps, readers, writers = view.steps, view.readers, view.writers
     consumed, fused_at, nfused = set(), {}, 0
     for i, (srcs, name, dst) in enumerate(steps):
-        _, kind, para = kinds[name]
+        kind, para = view.layers[name]
         if _NORM_Q4_SRCS.get(kind) != len(srcs) or i in consumed or not isinstance(dst, str):
             continue
-        if readers.get(srcs[0]) != [i] or writers.get(srcs[0], 0) > 1:
+        if readers.get(srcs[0]) != [i] or len(writers.get(srcs[0], ())) > 1:
             continue
         chain, cur, res, act = [i], dst, "None", ACT_NONE
         while act == ACT_NONE:
-            r = readers.get(cur, [])
-            if len(r) != 1 or writers.get(cur, 0) != 1:
+            j = view.only_reader(chain[-1], cur)
+            if j is None or j in consumed or not isinstance(steps[j][2], str):
                 break
-            j = r[0]
             jsrcs, jname, jdst = steps[j]
-            jkind = kinds[jname][1]
-            if j in consumed or j <= chain[-1] or not isinstance(jdst, str):
-                break
+            jkind = view.kind(j)
             if (jkind == "add_q4" and res == "None" and len(jsrcs) == 2 and jsrcs.count(cur) == 1
-                    and shape(jsrcs[0]) is not None and shape(jsrcs[0]) == shape(jsrcs[1])):
+                    and _shape(shapes, jsrcs[0]) is not None and _shape(shapes, jsrcs[0]) == _shape(shapes, jsrcs[1])):
                 res = jsrcs[1 - jsrcs.index(cur)]
             elif jkind == "relu_q4" and jsrcs == [cur]:
                 # the residual is now read at j: nothing may rewrite it between the add and here
-                if res != "None" and any((res in steps[t][0] and kinds[steps[t][1]][1] in _IN_PLACE) or res in _as_list(steps[t][2])
-                                         for t in range(chain[-1] + 1, j)):
+                if res != "None" and view.clobbered(res, chain[-1], j):
                     break
                 act = ACT_RELU
             else:
@@ -507,21 +558,9 @@ def fuse_instnorm_q4(body, flow, shapes):
             cur = jdst
         if len(chain) > 1:
             consumed.update(chain)
-            fused_at[chain[-1]] = (srcs, name, kind, para, res, act, cur)
+            fused_at[chain[-1]] = (srcs + [res], name + "+", kind, dict(para, act=act), cur)
             nfused += len(chain) - 1
-    out = []
-    for i, (srcs, name, dst) in enumerate(steps):
-        if i in fused_at:
-            isrcs, iname, ikind, para, res, act, cur = fused_at[i]
-            out.append((isrcs + [res], iname + "+", ikind, dict(para, act=act), cur))
-        elif i not in consumed:
-            out.append((srcs, name, kinds[name][1], kinds[name][2], dst))
-    out_body, seen = [], set()
-    for srcs, name, kind, para, dst in out:
-        if name not in seen:
-            seen.add(name)
-            out_body.append([name, kind, para])
-    return out_body, [[srcs, [name], dst] for srcs, name, kind, para, dst in out], nfused
+    return view.emit(view.spliced(fused_at, consumed)) + (nfused,)
 
 
 # ---- linear upsample + add ---------------------------------------------------------------------------
@@ -536,37 +575,21 @@ def fuse_linear_add(body, flow, shapes):
     source there: not fused where a step between the two rewrites that source in place (`_IN_PLACE`) or writes it, or writes the
     other operand.  fuse_flow has already put an add behind a conv into that conv's epilogue; this takes what is left -- the
     second and later terms of a sum of upsampled maps."""
-    kinds = {b[0]: b for b in body}
-    steps = [[list(src) if isinstance(src, (list, tuple)) else [src], names[0] if isinstance(names, (list, tuple)) else names, dst]
-             for src, names, dst in flow]
-    readers, writers = {}, {}
+    view = Steps(body, flow)
+    steps, consumed, fused_at = view.steps, set(), {}
     for i, (srcs, name, dst) in enumerate(steps):
-        for k in set(srcs):
-            readers.setdefault(k, []).append(i)
-        for k in _as_list(dst):
-            writers[k] = writers.get(k, 0) + 1
-
-    def shape(key):
-        s = shapes.get(key.split("@")[0])
-        return None if s is None else tuple(s)
-
-    consumed, fused_at = set(), {}
-    for i, (srcs, name, dst) in enumerate(steps):
-        _, kind, para = kinds[name]
-        if kind not in LINEAR_ADD_KINDS or not is_linear(kind, para) or not isinstance(dst, str):
+        kind, para = view.layers[name]
+        if kind not in LINEAR_ADD_KINDS or not is_linear(kind, para):
             continue
-        r = readers.get(dst, [])
-        if len(r) != 1 or writers.get(dst, 0) != 1 or r[0] <= i or r[0] in consumed:
+        j = view.only_reader(i, dst)
+        if j is None or j in consumed:
             continue
-        j = r[0]
         jsrcs, jname, jdst = steps[j]
-        if (kinds[jname][1] != "add_q4" or not isinstance(jdst, str) or len(jsrcs) != 2 or jsrcs.count(dst) != 1
-                or shape(jsrcs[0]) is None or shape(jsrcs[0]) != shape(jsrcs[1])):
+        if (view.kind(j) != "add_q4" or not isinstance(jdst, str) or len(jsrcs) != 2 or jsrcs.count(dst) != 1
+                or _shape(shapes, jsrcs[0]) is None or _shape(shapes, jsrcs[0]) != _shape(shapes, jsrcs[1])):
             continue
         res = jsrcs[1 - jsrcs.index(dst)]
-        between = range(i + 1, j)
-        if any((srcs[0] in steps[t][0] and kinds[steps[t][1]][1] in _IN_PLACE) or srcs[0] in _as_list(steps[t][2])
-               or res in _as_list(steps[t][2]) for t in between):
+        if view.clobbered(srcs[0], i, j) or view.clobbered(res, i, j, in_place=()):
             continue
         if kind == "upsample_q4":
             args = [srcs[0], srcs[1], res]
@@ -574,18 +597,7 @@ def fuse_linear_add(body, flow, shapes):
             args = (srcs + ["None"] * 4)[:4] + [res]
         consumed.update((i, j))
         fused_at[j] = (args, name + "+", LINEAR_ADD_KINDS[kind], para, jdst)
-    out = []
-    for i, (srcs, name, dst) in enumerate(steps):
-        if i in fused_at:
-            out.append(fused_at[i])
-        elif i not in consumed:
-            out.append((srcs, name, kinds[name][1], kinds[name][2], dst))
-    out_body, seen = [], set()
-    for srcs, name, kind, para, dst in out:
-        if name not in seen:
-            seen.add(name)
-            out_body.append([name, kind, para])
-    return out_body, [[srcs, [name], dst] for srcs, name, kind, para, dst in out], len(fused_at)
+    return view.emit(view.spliced(fused_at, consumed)) + (len(fused_at),)
 
 
 # ---- pixel shuffle / unshuffle ---------------------------------------------------------------------------------------------------
@@ -627,22 +639,16 @@ def fuse_pixel_shuffle(body, flow, shapes):
     shape-domain steps is as good as a constant one -- and both intermediates have exactly one writer and one reader.  The step
     sits where the last reshape was and reads the first reshape's input there: not fused where a step between rewrites that input
     in place or writes it.  Steps that only fed the reshapes' shape operands stay where they are."""
-    kinds = {name: (kind, para) for name, kind, para in body}
-    steps = expand_steps(flow)
-    readers, writers = {}, {}
-    for i, (srcs, _, dst) in enumerate(steps):
-        for k in set(srcs):
-            readers.setdefault(k, []).append(i)
-        for k in _as_list(dst):
-            writers[k] = writers.get(k, 0) + 1
+    view = Steps(body, flow)
+    kinds, steps = view.layers, view.steps
 
     def only_reader(i, dst, kind):
-        """The one step that reads `dst` (written once, by step i), where it comes later and is of `kind` with `dst` its first operand."""
-        r = readers.get(dst, [])
-        if not isinstance(dst, str) or len(r) != 1 or writers.get(dst, 0) != 1 or r[0] <= i:
+        """view.only_reader where that step is of `kind` with `dst` its first operand and writes one tensor."""
+        j = view.only_reader(i, dst)
+        if j is None:
             return None
-        jsrcs, jname, jdst = steps[r[0]]
-        return r[0] if kinds[jname][0] == kind and jsrcs[0] == dst and jsrcs.count(dst) == 1 and isinstance(jdst, str) else None
+        jsrcs, _, jdst = steps[j]
+        return j if view.kind(j) == kind and jsrcs[0] == dst and jsrcs.count(dst) == 1 and isinstance(jdst, str) else None
 
     consumed, fused_at, names = set(), {}, {b[0] for b in body}
     for i, (srcs, name, dst) in enumerate(steps):
@@ -658,27 +664,15 @@ def fuse_pixel_shuffle(body, flow, shapes):
         form = match_pixel_shuffle(shapes.get(x), shapes.get(dst), kinds[steps[j][1]][1].get("axis", ()), shapes.get(out))
         if form is None or tuple(shapes.get(steps[j][2]) or ()) != tuple(shapes[dst][a] for a in PIXEL_SHUFFLE_AXES[(form["order"], form["inverse"])]):
             continue
-        if any((x in steps[t][0] and kinds[steps[t][1]][0] in _IN_PLACE) or x in _as_list(steps[t][2])
-               for t in range(i + 1, k) if t != j):
+        if view.clobbered(x, i, k, skip=(j,)):
             continue
         new = steps[j][1] + "+"
         while new in names:                      # a transpose layer that serves several steps: one pixelshuffle layer per trio
             new += "+"
         names.add(new)
         consumed.update((i, j, k))
-        fused_at[k] = ([x], new, form, out)
-    out_body, out_flow, seen = [], [], set()
-    for i, (srcs, name, dst) in enumerate(steps):
-        if i in fused_at:
-            srcs, name, para, dst = fused_at[i]
-            out_body.append([name, "pixelshuffle", para])
-        elif i in consumed:
-            continue
-        elif name not in seen:
-            seen.add(name)
-            out_body.append([name] + list(kinds[name]))
-        out_flow.append([list(srcs), [name], dst])
-    return out_body, out_flow, len(fused_at)
+        fused_at[k] = ([x], new, "pixelshuffle", form, out)
+    return view.emit(view.spliced(fused_at, consumed)) + (len(fused_at),)
 
 
 # ---- group normalisation -----------------------------------------------------------------------------------------------------------
@@ -707,25 +701,17 @@ def fuse_groupnorm(body, flow, shapes, init_names=None):
     have no reader but the first reshape, and nothing may write it between the first step and the last.  A constant is a key no
     step writes (and one of `init_names` where they are given).  The step sits where the last link was; steps that only fed the
     reshapes' shape operands stay where they are."""
-    kinds = {name: (kind, para) for name, kind, para in body}
-    steps = expand_steps(flow)
+    view = Steps(body, flow)
+    kinds, steps, readers, writers = view.layers, view.steps, view.readers, view.writers
     inits = None if init_names is None else set(init_names)
-    readers, writers = {}, {}
-    for i, (srcs, _, dst) in enumerate(steps):
-        for k in set(srcs):
-            readers.setdefault(k, []).append(i)
-        for k in _as_list(dst):
-            writers[k] = writers.get(k, 0) + 1
 
     def const(key):
         return key != "None" and key not in writers and (inits is None or key in inits)
 
     def only_reader(i, dst):
-        """The one step that reads `dst` (written once, by step i), where it comes later and writes one tensor."""
-        r = readers.get(dst, [])
-        if not isinstance(dst, str) or len(r) != 1 or writers.get(dst, 0) != 1 or r[0] <= i or r[0] in consumed:
-            return None
-        return r[0] if isinstance(steps[r[0]][2], str) else None
+        """view.only_reader where that step is not part of an earlier pattern and writes one tensor."""
+        j = view.only_reader(i, dst)
+        return j if j is not None and j not in consumed and isinstance(steps[j][2], str) else None
 
     def channel_operand(j, cur, kind, c):
         """The constant per-channel operand of step j where that is a `kind` of `cur` and such a constant, else None."""
@@ -743,7 +729,7 @@ def fuse_groupnorm(body, flow, shapes, init_names=None):
             continue
         x = srcs[0]
         sx, sm = shapes.get(x), shapes.get(dst)
-        if sx is None or sm is None or len(sx) != 4 or len(sm) < 3 or readers.get(x) != [i] or writers.get(x, 0) > 1:
+        if sx is None or sm is None or len(sx) != 4 or len(sm) < 3 or readers.get(x) != [i] or len(writers.get(x, ())) > 1:
             continue
         n, c = int(sx[0]), int(sx[1])
         g = int(sm[1])
@@ -768,7 +754,7 @@ def fuse_groupnorm(body, flow, shapes, init_names=None):
         got = channel_operand(m, cur, "add", c)
         if got is not None:
             chain, cur, beta = chain + [m], steps[m][2], got
-        if any(x in _as_list(steps[t][2]) for t in range(i + 1, chain[-1] + 1) if t not in chain):
+        if view.clobbered(x, i, chain[-1] + 1, chain, in_place=()):
             continue
         new = nname + "+"
         while new in names:                      # a norm layer that serves several steps: one groupnorm layer per pattern
@@ -776,21 +762,10 @@ def fuse_groupnorm(body, flow, shapes, init_names=None):
         names.add(new)
         consumed.update(chain)
         para = {"groups": g, "epsilon": kinds[nname][1].get("epsilon", 1e-5)}
-        fused_at[chain[-1]] = ([x, nsrcs[1], nsrcs[2], gamma, beta], new, para, cur)
+        fused_at[chain[-1]] = ([x, nsrcs[1], nsrcs[2], gamma, beta], new, "groupnorm", para, cur)
     if not fused_at:
-        return [list(b) for b in body], [[list(s) if isinstance(s, (list, tuple)) else s, n, d] for s, n, d in flow], 0
-    out_body, out_flow, seen = [], [], set()
-    for i, (srcs, name, dst) in enumerate(steps):
-        if i in fused_at:
-            srcs, name, para, dst = fused_at[i]
-            out_body.append([name, "groupnorm", para])
-        elif i in consumed:
-            continue
-        elif name not in seen:
-            seen.add(name)
-            out_body.append([name] + list(kinds[name]))
-        out_flow.append([list(srcs), [name], dst])
-    return out_body, out_flow, len(fused_at)
+        return _copy_of(body, flow) + (0,)
+    return view.emit(view.spliced(fused_at, consumed)) + (len(fused_at),)
 
 
 # ---- Winograd chaining ------------------------------------------------------------------------------
@@ -798,25 +773,17 @@ def fuse_groupnorm(body, flow, shapes, init_names=None):
 # grouped GEMMs (V, U -> M) and output transform + fused tail (M -> y).  When the y of one such conv
 # feeds another, "M -> y -> V'" can be ONE kernel that keeps y on chip (csrc/wino4_chain_kernel.h), and
 # when nothing else reads y it is never written at all.  `chain_winograd` makes the stages explicit plan
-# steps and merges the out / in pairs.  Kinds that only read their inputs (no in-place update): a
-# Winograd input transform may be hoisted over them.
-_PURE_READERS = ("conv_q4", "convt_q4", "wino4_in", "wino4_gemm", "wino4_out", "wino4_chain", "wino43_in", "wino43_gemm", "wino43_out",
-                 "wino43_chain", "conv1x1_wino_in", "conv_q4_pair", "add_q4", "maxpool_q4",
-                 "averagepool_q4", "gap_q4", "upsample_q4", "concat_q4", "upconcat_q4", "batchnorm_q4",
-                 "leakyrelu_q4", "sigmoid_q4", "from_q4", "pad_q4", "refold_q4", "resize_q4", "upsample_add_q4", "resize_add_q4",
-                 "pixelshuffle_q4")
+# steps and merges the out / in pairs.  A Winograd input transform may be hoisted over the kinds that only read their inputs
+# (`_PURE_READERS`: no in-place update).
 
 
 def chain_winograd(body, flow, supported=lambda key: True, chain=True):
     """-> (body', flow', number of chained pairs).  `flow` holds one layer per step (as made by
     assign_layouts / lower); `supported(key)` says whether the LDS transform kernel
     can take the activation `key` (whole planes must fit a workgroup's LDS)."""
-    kinds = {b[0]: b for b in body}
-    steps = []                      # [srcs, name, kind, para, dst]
-    for src, names, dst in flow:
-        name = names[0] if isinstance(names, (list, tuple)) else names
-        srcs = list(src) if isinstance(src, (list, tuple)) else [src]
-        _, kind, para = kinds[name]
+    view = Steps(body, flow)
+    steps = []                      # [srcs, name, kind, para, dst]: the view's steps with the staged convs taken apart
+    for srcs, name, kind, para, dst in view.each():
         if kind == "conv_q4" and para.get("w_layout") in STAGED_LAYOUTS and isinstance(dst, str):
             full = srcs + ["None"] * (6 - len(srcs))
             tail = {k: para[k] for k in ("act", "alpha") if k in para}
@@ -848,12 +815,7 @@ def chain_winograd(body, flow, supported=lambda key: True, chain=True):
                     del steps[j]
                     nchained += 1
             i += 1
-    out_body, seen = [], set()
-    for srcs, name, kind, para, dst in steps:
-        if name not in seen:
-            seen.add(name)
-            out_body.append([name, kind, para])
-    return out_body, [[srcs, [name], dst] for srcs, name, kind, para, dst in steps], nchained
+    return view.emit(steps) + (nchained,)
 
 
 # ---- 1x1 conv -> staged Winograd conv ----------------------------------------------------------------------
@@ -863,26 +825,19 @@ def fuse_conv1x1_wino_in(body, flow, kshape=lambda key: None, small=lambda key: 
     chain_winograd) becomes one `conv1x1_wino_in` step that writes that stage's V (q4.Conv1x1WinoIn): the 1x1 -> 3x3 pairs of a
     Darknet block.  `small(key)` says whether the activation is small enough for the launch saved to matter (the fused kernel
     computes the 1x1 conv on overlapping patches: 1.9x its multiplies)."""
-    kinds = {b[0]: b for b in body}
-    steps = [[list(src) if isinstance(src, (list, tuple)) else [src], names[0] if isinstance(names, (list, tuple)) else names, dst]
-             for src, names, dst in flow]
-    readers, writers = {}, {}
-    for i, (srcs, name, dst) in enumerate(steps):
-        for k in set(srcs):
-            readers.setdefault(k, []).append(i)
-        for k in _as_list(dst):
-            writers.setdefault(k, []).append(i)
+    view = Steps(body, flow)
+    steps, readers, writers = view.steps, view.readers, view.writers
     last_dsts = set(_as_list(steps[-1][2])) if steps else set()
     drop, repl, nfused = set(), {}, 0
     for i, (srcs, name, dst) in enumerate(steps):
-        if kinds[name][1] != "wino4_in" or len(srcs) != 1:
+        if view.kind(i) != "wino4_in" or len(srcs) != 1:
             continue
         y = srcs[0]
         if len(writers.get(y, [])) != 1 or readers.get(y, []) != [i] or y in last_dsts:
             continue
         j = writers[y][0]
         csrcs, cname, cdst = steps[j]
-        _, ckind, cpara = kinds[cname]
+        ckind, cpara = view.layers[cname]
         full = csrcs + ["None"] * (6 - len(csrcs))
         if j >= i or j in drop or ckind != "conv_q4" or cpara.get("w_layout") != DIRECT_Q4 or not isinstance(cdst, str) or full[5] != "None":
             continue
@@ -895,42 +850,25 @@ def fuse_conv1x1_wino_in(body, flow, kshape=lambda key: None, small=lambda key: 
         repl[j] = (full[:5], fname, "conv1x1_wino_in", {"act": int(cpara.get("act", 0)), "alpha": float(cpara.get("alpha", 0.0)), "wino": 4}, dst)
         drop.add(i)
         nfused += 1
-    out = []
-    for i, (srcs, name, dst) in enumerate(steps):
-        if i in drop:
-            continue
-        if i in repl:
-            out.append(repl[i])
-        else:
-            out.append((srcs, name, kinds[name][1], kinds[name][2], dst))
-    out_body, seen = [], set()
-    for srcs, name, kind, para, dst in out:
-        if name not in seen:
-            seen.add(name)
-            out_body.append([name, kind, para])
-    return out_body, [[srcs, [name], dst] for srcs, name, kind, para, dst in out], nfused
+    return view.emit(view.spliced(repl, drop)) + (nfused,)
 
 
 # ---- sibling convolutions --------------------------------------------------------------------------------
 # Where a graph forks into two direct channel-quad convs on the same tensor -- a ResNet block that changes resolution:
 # the stride-2 3x3 conv and the 1x1 stride-2 projection -- both run in ONE launch (q4.ConvQ4Pair,
 # csrc/conv_q4_kernel.h conv_q4_pair_kernel).  The second conv moves up to the first one's place; it only needs the
-# shared input and constants, so that is legal unless something rewrites the input in place in between.
-_IN_PLACE = ("relu", "relu_q4", "clip", "clip_q4", "erf", "instancenormalization", "instancenormalization_q4", "groupnorm",
-             "groupnorm_q4")
+# shared input and constants, so that is legal unless something rewrites the input in place (`_IN_PLACE`) in between.
 
 
 def pair_sibling_convs(body, flow, kshape=lambda key: None):
     """-> (body', flow', number of pairs).  One layer per step, as made by lower.  `kshape(key)` gives
     the OIHW shape of a filter key; only the projection pattern is paired -- equal strides > 1, one of the two a 1x1 --
     because both convs then have the same output map and neither wants a split-K plan of its own."""
-    kinds = {b[0]: b for b in body}
-    steps = [[list(src) if isinstance(src, (list, tuple)) else [src], names[0] if isinstance(names, (list, tuple)) else names, dst]
-             for src, names, dst in flow]
+    view = Steps(body, flow)
+    steps = view.steps
 
     def direct(i):
-        srcs, name, dst = steps[i]
-        _, kind, para = kinds[name]
+        srcs, name, kind, para, dst = view.step(i)
         full = srcs + ["None"] * (6 - len(srcs))
         return (kind == "conv_q4" and para.get("w_layout") == DIRECT_Q4 and isinstance(dst, str) and full[5] == "None"
                 and int(para.get("group", 1)) == 1 and [int(v) for v in para.get("dilations", (1, 1))] == [1, 1]
@@ -945,13 +883,11 @@ def pair_sibling_convs(body, flow, kshape=lambda key: None):
         if direct(i):
             for k in range(i + 1, len(steps)):
                 ks, kname, kdst = steps[k]
-                if srcs[0] in ks and kinds[kname][1] in _IN_PLACE:
+                if view.clobbers(k, srcs[0]):
                     break                                   # the shared input is rewritten: later readers see other values
-                if srcs[0] in _as_list(kdst):
-                    break
                 # the flow's LAST step defines the program's result (net.py:72): hoisting it would make another step last
                 if k not in used and k != len(steps) - 1 and i != len(steps) - 1 and direct(k) and ks[0] == srcs[0]:
-                    p1, p2 = kinds[name][2], kinds[kname][2]
+                    p1, p2 = view.layers[name][1], view.layers[kname][1]
                     k1, k2 = kshape(srcs[1]), kshape(ks[1])
                     st1, st2 = [int(v) for v in p1.get("strides", (1, 1))], [int(v) for v in p2.get("strides", (1, 1))]
                     if (k1 is not None and k2 is not None and st1 == st2 and min(st1) > 1
@@ -959,21 +895,16 @@ def pair_sibling_convs(body, flow, kshape=lambda key: None):
                         j = k
                         break
         if j is None:
-            out.append((srcs, name, kinds[name][1], kinds[name][2], dst))
+            out.append(view.step(i))
             continue
         s2, n2, d2 = steps[j]
         f1, f2 = srcs + ["None"] * (6 - len(srcs)), s2 + ["None"] * (6 - len(s2))
         pname = name + "&" + n2
         out.append(([f1[0]] + f1[1:5] + f2[1:5], pname, "conv_q4_pair",
-                    {"para1": dict(kinds[name][2]), "para2": dict(kinds[n2][2])}, [dst, d2]))
+                    {"para1": dict(view.layers[name][1]), "para2": dict(view.layers[n2][1])}, [dst, d2]))
         used.add(j)
         npairs += 1
-    out_body, seen = [], set()
-    for srcs, name, kind, para, dst in out:
-        if name not in seen:
-            seen.add(name)
-            out_body.append([name, kind, para])
-    return out_body, [[srcs, [name], dst] for srcs, name, kind, para, dst in out], npairs
+    return view.emit(out) + (npairs,)
 
 
 # ---- dilated 3x3 convs on the Winograd kernels: pixel-phase folding ------------------------------------------------------------
@@ -985,8 +916,6 @@ def pair_sibling_convs(body, flow, kshape=lambda key: None):
 # folded conv would read it as padding -- so it folds alone: in, conv, out.
 FOLD_SEP = "~"
 REFOLD = "@refold_q4"
-_FOLD_POINTWISE = ("relu_q4", "leakyrelu_q4", "clip_q4", "sigmoid_q4", "batchnorm_q4", "add_q4", "concat_q4")
-_FOLD_IN_PLACE = ("relu_q4", "clip_q4", "instancenormalization_q4")
 
 
 def folded_key(key, fold, junk=False):
@@ -1026,9 +955,8 @@ def fold_dilated(body, flow, shapes, worth=lambda x_shape, k_shape, para: True):
     when a step rewrites their tensor in place.  Folded tensors get keys of their own (`folded_key`) and `shapes` gains their
     shapes.  `regions`: one {"fold", "dividing", "heads", "steps"} per run of steps that share folded tensors."""
     from .conv_layouts import w1d_q4_eligible
-    kinds = {b[0]: b for b in body}
-    steps = [[list(src) if isinstance(src, (list, tuple)) else [src], names[0] if isinstance(names, (list, tuple)) else names, dst]
-             for src, names, dst in flow]
+    view = Steps(body, flow)
+    steps = view.steps
     forms = {}            # key -> the folds it exists in, the one it was produced in first; absent: unfolded only
     region_of = {}        # key -> index of the region that produced it folded
     copy_region = {}      # (key, fold) -> index of the region a folded copy of an operand was first made for
@@ -1038,13 +966,16 @@ def fold_dilated(body, flow, shapes, worth=lambda x_shape, k_shape, para: True):
         s = shapes.get(key.split("@")[0])
         return tuple(s) if s is not None and len(s) == 4 else None
 
+    def refold(key, src, fold, dst):                     # one layer per (from, to) pair: a layer's parameters are its own
+        out.append(([key], "%s:%dx%d>%dx%d" % ((REFOLD,) + src + fold), "refold_q4", {"to": list(fold), "from": list(src)}, dst))
+
     def need(key, fold):
         if key == "None":
             return key
         have = forms.setdefault(key, [(1, 1)])
         if fold not in have:
             src = have[0]
-            out.append(([folded_key(key, src)], REFOLD, "refold_q4", {"to": list(fold), "from": list(src)}, folded_key(key, fold)))
+            refold(folded_key(key, src), src, fold, folded_key(key, fold))
             have.append(fold)
             if fold != (1, 1) and shape(key) is not None:
                 shapes[folded_key(key, fold).split("@")[0]] = _folded_shape(shape(key), fold)
@@ -1077,7 +1008,7 @@ def fold_dilated(body, flow, shapes, worth=lambda x_shape, k_shape, para: True):
 
     last = len(steps) - 1
     for i, (srcs, name, dst) in enumerate(steps):
-        _, kind, para = kinds[name]
+        kind, para = view.layers[name]
         fold, head = None, False
         if isinstance(dst, str):
             fold = head_fold(kind, para, srcs)
@@ -1129,45 +1060,31 @@ def fold_dilated(body, flow, shapes, worth=lambda x_shape, k_shape, para: True):
         region_of[dst] = reg
         if not dividing or i == last:
             # zero-fill cells hold junk behind the conv: nothing may read this tensor folded.  (And a program ends unfolded.)
-            out.append(([fdst], REFOLD, "refold_q4", {"to": [1, 1], "from": list(fold)}, dst))
+            refold(fdst, fold, (1, 1), dst)
             forms[dst] = [(1, 1)]
             region_of.pop(dst, None)
-    out_body, seen = [], set()
-    named = []
-    nre = 0
-    for srcs, name, kind, para, dst in out:
-        if kind == "refold_q4":                          # one layer per (from, to) pair: a layer's parameters are its own
-            name = "%s:%dx%d>%dx%d" % (REFOLD, para["from"][0], para["from"][1], para["to"][0], para["to"][1])
-            nre += 1
-        if name not in seen:
-            seen.add(name)
-            out_body.append([name, kind, para])
-        named.append([srcs, [name], dst])
     if not regions:
-        return [list(b) for b in body], [[list(s) if isinstance(s, (list, tuple)) else s, n, d] for s, n, d in flow], []
-    return out_body, named, regions
+        return _copy_of(body, flow) + ([],)
+    return view.emit(out) + (regions,)
 
 
 # ---- peepholes behind the filter choice (`body` is {name: entry} there and is rewritten in place) ---------------------------------
 def fuse_upsample_concat(body, flow):
     """upsample_q4 whose only reader is a two-input concat_q4 (axis 1) that takes it FIRST -> one upconcat_q4 step
     (detection-net routes: the upsampled tensor is written once, into its place in the concatenation)."""
-    readers = {}
-    for i, (src, names, dst) in enumerate(flow):
-        for k in (src if isinstance(src, list) else [src]):
-            readers.setdefault(k, []).append(i)
+    view = Steps(body.values(), flow)                    # (one layer per step: step i is flow[i])
     drop, out = set(), {}
     for i, (src, names, dst) in enumerate(flow):
         entry = body[names[0]]
         if (entry[1] == "upsample_q4" and isinstance(dst, str) and isinstance(src, list) and len(src) == 2
-                and entry[2].get("mode", "nearest") == "nearest" and len(readers.get(dst, [])) == 1):
-            j = readers[dst][0]
+                and entry[2].get("mode", "nearest") == "nearest" and len(view.readers.get(dst, [])) == 1):
+            j = view.readers[dst][0]
             csrc, cnames, cdst = flow[j]
             ce = body[cnames[0]]
-            if (ce[1] == "concat_q4" and len(cnames) == 1 and isinstance(csrc, list) and len(csrc) == 2 and csrc[0] == dst
+            if (ce[1] == "concat_q4" and len(cnames) == 1 and isinstance(csrc, list) and len(csrc) == 2 and csrc[0] == dst != csrc[1]
                     and int(ce[2].get("axis", 0)) == 1 and i < j
-                    # the upsample now reads its source at step j: nobody may touch it in between (in-place ReLU)
-                    and not any(src[0] in (f[0] if isinstance(f[0], list) else [f[0]]) for f in flow[i + 1:j])):
+                    # the upsample now reads its source at step j: nobody may read it in between (in-place ReLU)
+                    and not view.clobbered(src[0], i, j, in_place=None, writes=False)):
                 body[cnames[0]] = [ce[0], "upconcat_q4", {"mode": "nearest", "axis": 1}]
                 out[j] = [[src[0], src[1], csrc[1]], cnames, cdst]
                 drop.add(i)
@@ -1179,10 +1096,7 @@ def fuse_stem_pool(body, flow, shapes, kshape, eligible, prepare):
     conv_pool_q4 step: the full-resolution tensor is never written.  `eligible(x shape, filter shape, para)` -> None, or the
     w_layout that takes the conv and its extra parameters (lower's `stem_pool`); STEM_POOL_NCHW reads the NCHW batch itself (no
     row-packed copy) with the filter in its own k order, which `prepare` makes."""
-    readers = {}
-    for i, (src, names, dst) in enumerate(flow):
-        for k in (src if isinstance(src, list) else [src]):
-            readers.setdefault(k, []).append(i)
+    readers = Steps(body.values(), flow).readers
     drop, out = set(), []
     for i, (src, names, dst) in enumerate(flow):
         entry = body[names[0]]
@@ -1270,13 +1184,10 @@ def lower(body, flow, inits, shapes, kshape=None, pick=lambda cands, kind, srcs,
     inits = set(inits)
     kshape = kshape or (lambda key: shapes.get(key.split("@")[0]) if key.split("@")[0] in inits else None)
     prepare = prepare or (lambda lay, key, para: key + suffix(lay, para))
-    kinds = {b[0]: b for b in body}
+    view = Steps(body, flow)
     out_body = {b[0]: list(b) for b in body}
     out_flow = []
-    for src, names, dst in flow:
-        name = names[0] if isinstance(names, list) else names
-        _, kind, para = kinds[name]
-        srcs = list(src) if isinstance(src, list) else [src]
+    for srcs, name, kind, para, dst in view.each():
         ks = kshape(srcs[1]) if len(srcs) >= 2 and srcs[1] in inits else None
         if ks is not None:
             # (an NCHW conv looks its input up by key: one on a converted copy, key@nchw, is not timed)

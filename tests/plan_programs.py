@@ -1,11 +1,13 @@
 """Recorded plan programs (tests/golden/plan_programs.json on the host, plan_programs_gpu.json from Net on the device): the ten
 generator nets at 64 pixels, the canonical form of a program and its digest.  tests/test_plan_programs.py and
-tests/test_gpu_plan_programs.py compare against the recordings; tools/capture_plan_programs.py writes the host one."""
+tests/test_gpu_plan_programs.py compare against the recordings; tools/capture_plan_programs.py writes the host ones, the
+second of which (plan_programs_random.json) holds a digest after every pass for the ten nets and 150 random graphs."""
 import hashlib
 import json
 
 import numpy as np
 
+from planer_amd.conv_layouts import STAGED_LAYOUTS
 from planer_amd.irgen import customnet, drn, edsr, fpn, mobilenetv2, resnet18, resnet_gn, stylenet, unet, yolov3
 
 # name -> (generator, build keywords).  Every input is 64 x 64.
@@ -61,6 +63,44 @@ def net_record(net, xs, pick, mode):
         steps.append(plain([names[0], obj.name, src if isinstance(src, list) else [src], dst]))
         paras.append(obj.para())
     return {"steps": steps, "paras": digest(paras), "counters": {k: int(getattr(net, k)) for k in COUNTERS}}
+
+
+# The second host recording (tests/golden/plan_programs_random.json): the digest after every pass, for the ten nets and for
+# the random graphs of test_plan_fusion's fuzz test.  stages() is the order of a recorded row: the passes of plan.FRONT
+# (compile_front(stop=...)), then plan.lower under each of LOWERINGS.
+RANDOM_SEEDS = range(150)
+# (the first candidate is the direct kernel and the last a fused one: the chain switches get the pick that takes a staged
+# Winograd layout wherever one applies, which is what they act on)
+_STAGED = {"pick": lambda cands, *_: next((c for c in cands if c in STAGED_LAYOUTS), cands[0])}
+LOWERINGS = {"first": {"pick": lambda cands, *_: cands[0]}, "last": {"pick": lambda cands, *_: cands[-1]}, "staged": _STAGED,
+             "stages": dict(_STAGED, wino_chain="stages"), "unchained": dict(_STAGED, wino_chain="0"), "unpaired": {"pair": False},
+             "no_conv1x1": dict(_STAGED, small=None)}
+DIGEST_CHARS = 16       # a row keeps this much of each sha256: 64 bits tell two programs apart, and the file stays small
+
+
+def stages():
+    from planer_amd.plan import FRONT
+    return list(FRONT) + ["lower:" + k for k in LOWERINGS]
+
+
+def stage_digests(g, b, x):
+    """-> [digest after each stage of stages()] for this graph (None for a pass of FRONT that did not run).  The maps of the
+    random graphs are tiny, so layouts are forced; `worth` always agrees, so that drn's dilated convs fold."""
+    from planer_amd.plan import FRONT, lower
+    from tests.plan_audit import cpu_front
+    row = []
+    for stop in FRONT:
+        body, flow, counts, shapes = cpu_front(g, b, x, force=True, worth=lambda *_: True, stop=stop)
+        row.append(digest([body, flow])[:DIGEST_CHARS] if stop in counts else None)
+    for kw in LOWERINGS.values():
+        row.append(digest(list(lower(body, flow, [i[0] for i in g["inits"]], shapes, **kw)[:2]))[:DIGEST_CHARS])
+    return row
+
+
+def random_digests(seed):
+    from tests.random_nets import random_net
+    g, b, xs = random_net(40000 + seed)
+    return stage_digests(g, b, xs[0])
 
 
 def host_programs(name):
