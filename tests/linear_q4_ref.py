@@ -1,6 +1,6 @@
 """Shared pieces of the tests of linear upsample / resize in channel-quad (Q4) plans (tests/test_plan_linear_q4.py on the host,
 tests/test_gpu_linear_q4.py on the GPU): the compiler's front half up to fuse_linear_add, small graphs, the bit-pattern
-comparison, and the per-step check tests/plan_audit.py does not have (it refuses linear upsamples and does not know resize_q4).
+comparison, and a per-step check against the NCHW kernels (tests/plan_audit.py checks the same steps against float64).
 """
 import numpy as np
 

@@ -136,11 +136,38 @@ def assert_exact(x, K, B=None, scale=None, shift=None, res=None, gran=0.25, **co
 
 
 # ---- per-element bound for float data -----------------------------------------------------------------------------------
-def bound(x, K, B=None, scale=None, shift=None, res=None, lam=LAMBDA["direct"], group=1, **conv):
-    """Per-element tolerance of a conv + fused tail whose sums are rounded to fp32 (see the module docstring)."""
+# How far, in output pixels along (H, W), a Winograd output's tile can reach: m - 1 for output segments of m.  The input and
+# output transforms of a tile mix ALL its inputs, so the rounding error of an output is that of its tile's arithmetic, not of its
+# own 3x3 receptive field: an output whose receptive field is all zeros (a ReLU map behind a nearest upsample: blocks of zeros
+# over every channel) beside a large neighbour in the same tile gets that neighbour's error -- sqrt(conv(x^2, K^2)) at the
+# element itself is 0 there, and the float32 emulation `wino_emulate` is outside the element's own bound (err / tol = inf on
+# such maps, tests/test_plan_audit_q4ops.py).  `bound(reach=...)` therefore takes, for the lam term, the largest L2 among the
+# outputs that can share a tile with the element, whatever the tiles' alignment: the window of +-(m - 1).  On maps without such
+# holes it changes little (the calibration of LAMBDA, on dense maps, is untouched); the emulation stays below 0.12 of it on the
+# sparse maps and on calibration_cases alike.
+REACH = {"direct": (0, 0), "f2x2": (1, 1), "f4x4": (3, 3), "w1d4": (0, 3), "wino43": (3, 3)}
+
+
+def _window_max(a, rh, rw, sh=1, sw=1):
+    """max of a (N, C, H, W) over the elements up to rh rows and rw columns away from each element, in steps of (sh, sw)."""
+    if not rh and not rw:
+        return a
+    h, w = a.shape[2:]
+    p = np.pad(a, ((0, 0), (0, 0), (rh * sh, rh * sh), (rw * sw, rw * sw)))
+    out = a
+    for i in range(2 * rh + 1):
+        for j in range(2 * rw + 1):
+            out = np.maximum(out, p[:, :, i * sh:i * sh + h, j * sw:j * sw + w])
+    return out
+
+
+def bound(x, K, B=None, scale=None, shift=None, res=None, lam=LAMBDA["direct"], group=1, reach=(0, 0), **conv):
+    """Per-element tolerance of a conv + fused tail whose sums are rounded to fp32 (see the module docstring).  `reach`: REACH of a
+    Winograd family, where the element's tile neighbours count (above); (0, 0) is the element's own receptive field.  With
+    dilations (d, d) -- a conv that runs by pixel phase on a Winograd kernel -- the neighbours are d pixels apart."""
     x, K = _f64(x), _f64(K)
     kred = K.shape[1] * K.shape[2] * K.shape[3]
-    l2 = np.sqrt(conv64(x * x, K * K, group=group, **conv))
+    l2 = np.sqrt(_window_max(conv64(x * x, K * K, group=group, **conv), *reach, *[int(d) for d in conv.get("dilations", (1, 1))]))
     a = conv64(np.abs(x), np.abs(K), group=group, **conv)
     if B is not None:
         a = a + np.abs(_chan(B))

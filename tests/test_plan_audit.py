@@ -49,6 +49,7 @@ def test_audit_passes_on_the_oracles_own_run(name, pick):
     trace, _, inits = _run(name, pick)
     worst, census = PA.audit(trace, inits)
     assert census and max(worst.values()) <= 1.0
+    PA.assert_every_step_audited(trace, census)
 
 
 def _conv_steps(trace):
