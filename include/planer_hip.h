@@ -296,6 +296,19 @@ int pl_conv2d_prepare_stem_nchw_f32(pl_ctx *ctx, const float *w, int Cout, float
 int pl_conv2d_stem_pool_nchw_q4_f32(pl_ctx *ctx, const float *x, int N, int H, int W, const float *wq, int Cout,
                                     const float *bias, float *yq, const float *scale, const float *shift,
                                     int act, double alpha, int strip_rows);
+/* A second form of that kernel: a polyphase 1-D Winograd F(4,4) along W (conv_stem_wino_kernel.h; nodes 0, 1, -1, 2, -2, 1/2,
+ * inf) -- 7 frequency GEMMs of K = 44 instead of one of K = 148.  Same shapes and arguments; wq = G g in that kernel's k order,
+ * [7][11][Cout][4] floats, made by pl_conv2d_prepare_stem_wino_f32 from OIHW [Cout][3][7][7].  Not bit-exact on integers.
+ * _korder: tab[4 k + a] = index into one output channel's [3][7][7] filter of tap a of k (element e of quad q is k = 4 q + e), or
+ * -1 for a zero; n >= 176. */
+int pl_conv2d_stem_pool_wino_supported(int Cin, int H, int W, int Cout, int kh, int kw, int sh, int sw, int pt,
+                                       int pl, int *ok);
+int pl_conv2d_stem_wino_filter_elems(int Cout, size_t *elems);
+int pl_conv2d_stem_wino_korder(int *tab, int n);
+int pl_conv2d_prepare_stem_wino_f32(pl_ctx *ctx, const float *w, int Cout, float *out);
+int pl_conv2d_stem_pool_wino_q4_f32(pl_ctx *ctx, const float *x, int N, int H, int W, const float *wq, int Cout,
+                                    const float *bias, float *yq, const float *scale, const float *shift,
+                                    int act, double alpha, int strip_rows);
 /* Winograd F(4x4,3x3) on Q4 tensors (same constraints as the F(2x2,3x3) entry points): 6x6 input
  * tiles, 36 grouped GEMMs, 4x fewer multiplies than the direct conv and less transform traffic
  * than F(2x2,3x3); larger transform constants, error a few 1e-6 of max|y| in fp32.

@@ -82,6 +82,12 @@ prepare_winograd43_q4_weights = _packer("winograd43_q4", _cout_cin, _wino_check)
 # OIHW stem filters [Cout][3][7][7] -> [48][Cout][4] in the k order of the stem + max-pool kernel that reads the NCHW input
 prepare_stem_nchw_weights = _packer("stem_nchw", lambda s, **_: (s[0],),
                                     _refuse(lambda co, ci, kh, kw: (ci, kh, kw) == (3, 7, 7), "the NCHW stem kernel takes [Cout][3][7][7] filters"))
+# OIHW stem filters [Cout][3][7][7] -> G g of the polyphase F(4,4) form of that kernel, [7][11][Cout][4] (csrc/conv_stem_wino_kernel.h).
+# The form has no w_layout code of its own: q4.ConvPoolQ4 runs it on w_layout 12 with wino=44 (STEM_WINO), or where the step's
+# filter carries one (q4.attach_stem_wino)
+prepare_stem_wino_weights = _packer("stem_wino", lambda s, **_: (s[0],),
+                                    _refuse(lambda co, ci, kh, kw: (ci, kh, kw) == (3, 7, 7), "the F(4,4) stem kernel takes [Cout][3][7][7] filters"))
+STEM_WINO = 44
 # OIHW depthwise filters [C][1][kh][kw] -> [ceil(C/4)][kh*kw][4] with zero-padded quads
 prepare_dw_q4_weights = _packer("dw_q4", lambda s, **_: (s[0], s[2], s[3]),
                                 _refuse(lambda c, ci, kh, kw: ci == 1, "depthwise filters have one input channel per group"),
@@ -176,6 +182,25 @@ def stem_pool_nchw_eligible(x_shape, k_shape, group=1, strides=(1, 1), dilations
     """Whether the stem + max-pool kernel can read this NCHW input itself (W % 4 == 0 on top of stem_pool_eligible)."""
     return (stem_pool_eligible(x_shape, k_shape, group, strides, dilations, pads)
             and _supported("pl_conv2d_stem_pool_nchw_supported", x_shape, k_shape, strides, pads))
+
+
+def stem_pool_wino_eligible(x_shape, k_shape, group=1, strides=(1, 1), dilations=(1, 1), pads=(0, 0, 0, 0), **_):
+    """Whether the polyphase F(4,4) form of the NCHW stem + max-pool kernel takes this conv (csrc/conv_stem_wino_kernel.h).
+    PLANER_HIP_EXPERIMENT=stem_wino=0 or 1 switches the pick (Net's `stem_pool` callback)."""
+    return (stem_pool_nchw_eligible(x_shape, k_shape, group, strides, dilations, pads)
+            and _supported("pl_conv2d_stem_pool_wino_supported", x_shape, k_shape, strides, pads))
+
+
+def experiment(key, default):
+    """PLANER_HIP_EXPERIMENT="key=value,key=value" as the native code reads it (csrc/common.h pl_experiment)."""
+    for item in os.environ.get("PLANER_HIP_EXPERIMENT", "").split(","):
+        k, _, v = item.partition("=")
+        if k.strip() == key:
+            try:
+                return int(v)
+            except ValueError:
+                return default
+    return default
 
 
 # ---- the table -----------------------------------------------------------------------------------------------------------

@@ -581,6 +581,7 @@ __global__ void __launch_bounds__(256) permute_weights_kernel(const float *w, fl
 #include "conv_smallcin_kernel.h"
 #include "conv_smallcin_valu_kernel.h"
 #include "conv_stem_pool_kernel.h"
+#include "conv_stem_wino_kernel.h"
 #include "conv_dw_kernel.h"
 
 // ---- configurations ---------------------------------------------------------
@@ -1834,6 +1835,84 @@ int pl_conv2d_stem_pool_nchw_q4_f32(pl_ctx *ctx, const float *x, int N, int H, i
     // executed MFMA work: 2 x steps conv rows per strip, 16 nb columns per chunk, K = 148 (sp_nchw_tap)
     ctx->last_gemm[0] = 1; ctx->last_gemm[1] = (long long)a.cout_blocks * 64;
     ctx->last_gemm[2] = (long long)N * a.strips * a.chunks * 2 * a.steps * 16 * nb; ctx->last_gemm[3] = 4 * SP_NCHW_QUADS;
+    return PL_OK;
+}
+
+// The polyphase F(4,4) form of the NCHW stem + max-pool kernel (conv_stem_wino_kernel.h): same shapes, same arguments, the filter
+// as G g in its own k order.
+int pl_conv2d_stem_pool_wino_supported(int Cin, int H, int W, int Cout, int kh, int kw, int sh, int sw, int pt, int pl, int *ok) {
+    PL_REQUIRE(ok, PL_EINVAL, "pl_conv2d_stem_pool_wino_supported: null argument");
+    *ok = (stem_pool_shape_ok(Cin, H, W, Cout, kh, kw, sh, sw, pt, pl) && W % 4 == 0) ? 1 : 0;
+    return PL_OK;
+}
+
+int pl_conv2d_stem_wino_filter_elems(int Cout, size_t *elems) {
+    PL_REQUIRE(elems && Cout > 0, PL_EINVAL, "pl_conv2d_stem_wino_filter_elems: bad argument");
+    *elems = (size_t)SW_F * SW_KQ * Cout * 4;
+    return PL_OK;
+}
+
+// The k order of that filter: tab[4 k + a] = the index (c * 7 + fr) * 7 + kw into one output channel's OIHW filter of tap a of
+// k (k = 0 .. 43; element e of quad q is k = 4 q + e), -1 where the slot is a zero.  A host query (tests).
+int pl_conv2d_stem_wino_korder(int *tab, int n) {
+    PL_REQUIRE(tab && n >= 16 * SW_KQ, PL_EINVAL, "pl_conv2d_stem_wino_korder: need %d entries", 16 * SW_KQ);
+    for (int i = 0; i < 16 * SW_KQ; ++i) tab[i] = sw_k_tap(i >> 2, i & 3);
+    return PL_OK;
+}
+
+int pl_conv2d_prepare_stem_wino_f32(pl_ctx *ctx, const float *w, int Cout, float *out) {
+    PL_REQUIRE(ctx && w && out, PL_EINVAL, "pl_conv2d_prepare_stem_wino_f32: null pointer");
+    PL_REQUIRE(Cout > 0, PL_EINVAL, "pl_conv2d_prepare_stem_wino_f32: bad shape");
+    PL_REQUIRE((reinterpret_cast<uintptr_t>(out) & 15u) == 0, PL_EINVAL, "pl_conv2d_prepare_stem_wino_f32: unaligned output");
+    const size_t total = (size_t)SW_F * SW_KQ * Cout;
+    PL_REQUIRE(total * 16 < (1ull << 29), PL_EUNSUPPORTED, "filter too large");
+    CtxGuard g(ctx);
+    pack_filter_stem_wino_kernel<<<(unsigned)((total + 255) / 256), 256, 0, ctx->stream>>>(w, reinterpret_cast<float4 *>(out), (unsigned)total, Cout);
+    PL_LAUNCH_CHECK();
+    return PL_OK;
+}
+
+int pl_conv2d_stem_pool_wino_q4_f32(pl_ctx *ctx, const float *x, int N, int H, int W, const float *wq, int Cout, const float *bias,
+                                    float *yq, const float *scale, const float *shift, int act, double alpha, int strip_rows) {
+    const int Cin = 3, kh = SP_KH, kw = 7, sh = 2, sw = 2, pt = 3, pl = 3;
+    int rc = rowpack_check(ctx, x, N, Cin, H, W, wq, Cout, kh, kw, yq, sh, sw, pt, pl, nullptr);
+    if (rc != PL_OK) return rc;
+    PL_REQUIRE(stem_pool_shape_ok(Cin, H, W, Cout, kh, kw, sh, sw, pt, pl) && W % 4 == 0, PL_EUNSUPPORTED,
+               "conv + maxpool (F(4,4) stem): 3 channels, 7x7 / stride 2 / pad 3, W %% 4 == 0, Cout %% 4 == 0");
+    PL_REQUIRE(act >= 0 && act <= 2, PL_EINVAL, "pl_conv2d_stem_pool_wino_q4_f32: bad activation code");
+    PL_REQUIRE(strip_rows == 0 || strip_rows == 7 || strip_rows == 14, PL_EINVAL, "pl_conv2d_stem_pool_wino_q4_f32: strip_rows is 0 (= 7), 7 or 14");
+    PL_REQUIRE(((reinterpret_cast<uintptr_t>(bias) | reinterpret_cast<uintptr_t>(scale) | reinterpret_cast<uintptr_t>(shift) |
+                 reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(wq)) & 15u) == 0,
+               PL_EINVAL, "pl_conv2d_stem_pool_wino_q4_f32: x / wq / bias / scale / shift are read as 16-byte quads");
+    if (N == 0) return PL_OK;
+    CtxGuard guard(ctx);
+    StemPoolArgs a;
+    memset(&a, 0, sizeof a);
+    a.xp = x; a.wq = wq; a.y = yq;
+    a.N = N; a.H = H; a.W = W;
+    a.Ho = (H + 2 * pt - kh + sh) / sh; a.Wo = (W + 2 * pl - kw + sw) / sw;
+    a.Hq = (a.Ho + 1) / 2; a.Wq = (a.Wo + 1) / 2;
+    a.Cout = Cout; a.Coq = Cout / 4;
+    a.prows = strip_rows == 14 ? 14 : SP_PROWS;
+    a.steps = a.prows + 1;
+    a.strips = (a.Hq + a.prows - 1) / a.prows;
+    a.cout_blocks = (Cout + 63) / 64;
+    const size_t xb = (size_t)N * Cin * H * W * 4, yb = (size_t)N * a.Coq * a.Hq * a.Wq * 16;
+    int nb = 0;
+    stem_pool_chunks(a.Wo, a.chunks, a.pq, nb);
+    PL_REQUIRE(a.chunks > 0 && xb < (1ull << 31) && yb < (1ull << 31), PL_EUNSUPPORTED, "conv + maxpool (F(4,4) stem): tensor too large");
+    a.x_bytes = (unsigned)xb; a.w_bytes = (unsigned)((size_t)SW_F * SW_KQ * Cout * 16); a.y_bytes = (unsigned)yb;
+    a.ep = make_epilogue(bias, scale, shift, nullptr, act, alpha);
+    const long long blocks = (long long)N * a.strips * a.chunks * a.cout_blocks;
+    PL_REQUIRE(blocks < (1ll << 31), PL_EUNSUPPORTED, "conv + maxpool (F(4,4) stem): grid too large");
+    hipLaunchKernelGGL(conv_stem_wino_kernel, dim3((unsigned)blocks), dim3(512), 0, ctx->stream, a);
+    PL_LAUNCH_CHECK();
+    char buf[112];
+    snprintf(buf, sizeof buf, "stem+maxpool(nchw) F(4,4) 64co x 2 rows x 32 tiles, strips=%d of %d rows, chunks=%d blocks=%lld", a.strips, a.prows, a.chunks, blocks);
+    ctx->last_plan = buf;
+    // executed MFMA work: 7 frequency GEMMs, 2 x steps conv rows per strip, 32 tile slots per row and chunk, K = 44
+    ctx->last_gemm[0] = SW_F; ctx->last_gemm[1] = (long long)a.cout_blocks * 64;
+    ctx->last_gemm[2] = (long long)N * a.strips * a.chunks * 2 * a.steps * SW_TS; ctx->last_gemm[3] = 4 * SW_KQ;
     return PL_OK;
 }
 

@@ -27,9 +27,11 @@ from . import _lib
 from . import hip
 from .hip import DeviceArray
 from . import q4 as _q4
-from .conv_layouts import DIRECT_Q4, IGEMM_NCHW, LAYOUTS, STEM_POOL, STEM_POOL_NCHW, WINO4_Q4, WINO43_Q4, suffix
+from .conv_layouts import DIRECT_Q4, IGEMM_NCHW, LAYOUTS, STEM_POOL, STEM_POOL_NCHW, WINO4_Q4, WINO43_Q4, experiment, suffix
 from .layer import layer_map, wrap
 from .plan import compile_front, fuse_upsample_concat, lower
+
+STEM_WINO_DEFAULT = 1      # whether the stem + max-pool step takes the F(4,4) form where it applies
 
 _q4.register(layer_map)
 
@@ -542,10 +544,16 @@ class Net:
             K = wmap.get(key, self._extra.get(key))
             return K.shape if K is not None and K.dtype == numpy.float32 else None
 
+        stem_form = {"wino": False}     # what `stem_pool` chose for the stem whose filter `prepare` is asked for next
+
         def prepare(lay, init, para):
             key = init + suffix(lay, para)
             if key not in self._extra:
                 self._extra[key] = LAYOUTS[lay].prepare(wmap[init], **para)
+            if lay == STEM_POOL_NCHW:
+                # the F(4,4) form of the stem kernel is neither a layout nor a step parameter (recorded programs stay as they
+                # are): its filter rides on the direct form's, and the step runs it where it finds one (q4.ConvPoolQ4)
+                _q4.attach_stem_wino(self._extra[key], wmap[init] if stem_form["wino"] else None)
             return key
 
         def stem_pool(xs, ks, para):
@@ -562,6 +570,8 @@ class Net:
                 hq = ((xs[2] + 6 - 7) // 2 + 1 + 1) // 2
                 if xs[0] * (-(-hq // 14)) * (-(-ks[0] // 64)) * 2 >= self.ctx.cu_count:
                     extra["strip_rows"] = 14
+            # the polyphase F(4,4) form of the kernel (csrc/conv_stem_wino_kernel.h); PLANER_HIP_EXPERIMENT=stem_wino=0 / 1
+            stem_form["wino"] = bool(experiment("stem_wino", STEM_WINO_DEFAULT)) and _q4.stem_pool_wino_eligible(xs, ks, **para)
             return STEM_POOL_NCHW, extra
 
         def fits(key):

@@ -12,16 +12,17 @@ one 16-byte load per (pixel, 4 channels) instead of four 4-byte loads keeps the
 fp32 MFMA pipe 13-17 % busier, and every HBM-bound layer moves float4s.
 """
 import ctypes
+import weakref
 
 import numpy
 
 from . import _lib
-from .conv_layouts import CONVT_Q4, DIRECT_Q4, DW_Q4, LAYOUTS, ROWPACK_Q4, STEM_POOL, STEM_POOL_NCHW, WF4_Q4, WINO43_Q4
+from .conv_layouts import CONVT_Q4, DIRECT_Q4, DW_Q4, LAYOUTS, ROWPACK_Q4, STEM_POOL, STEM_POOL_NCHW, STEM_WINO, WF4_Q4, WINO43_Q4
 # the packers and predicates of the Q4 layouts, importable from here
 from .conv_layouts import (dw_q4_eligible, prepare_dw_q4_weights, prepare_q4_weights, prepare_rowpack_weights,  # noqa: F401
-                           prepare_stem_nchw_weights, prepare_w1d4_q4_weights, prepare_wf4_q4_weights, prepare_winograd4_q4_weights,
+                           prepare_stem_nchw_weights, prepare_stem_wino_weights, prepare_w1d4_q4_weights, prepare_wf4_q4_weights, prepare_winograd4_q4_weights,
                            prepare_winograd43_q4_weights, prepare_winograd_q4_weights, q4_conv_eligible, rowpack_eligible,
-                           stem_pool_eligible, stem_pool_nchw_eligible, w1d_q4_eligible, winograd43_eligible, winograd_q4_eligible)
+                           stem_pool_eligible, stem_pool_nchw_eligible, stem_pool_wino_eligible, w1d_q4_eligible, winograd43_eligible, winograd_q4_eligible)
 from .conv_layouts import convt_phase_eligible as convt_q4_eligible, prepare_convt_weights as prepare_convt_q4_weights
 from .hip import DeviceArray, _f32, asarray, empty
 from .layer import (ACT_NONE, PIXEL_SHUFFLE_AXES, _PAD_MODES, _contig_strides, _full, _host_values, _linear_positions, _linear_weights,
@@ -217,14 +218,20 @@ def ConvQ4(xq, Kq, B=None, scale=None, shift=None, resq=None, group=1, strides=(
 
 
 def ConvPoolQ4(x, Kq, B=None, scale=None, shift=None, group=1, strides=(1, 1), dilations=(1, 1), pads=(0, 0, 0, 0),
-               act=ACT_NONE, alpha=0.0, w_layout=STEM_POOL, out=None, src_ptr=None, ctx=None, strip_rows=0, **_):
+               act=ACT_NONE, alpha=0.0, w_layout=STEM_POOL, out=None, src_ptr=None, ctx=None, strip_rows=0, wino=0, **_):
     """Row-packed stem conv (ConvQ4 w_layout 6: NCHW input, filter from prepare_rowpack_weights) with its fused tail, followed
     by layer.Maxpool(w=(3, 3), strides=(2, 2), pads=(1, 1, 1, 1)) (layer.py:71-72), in ONE kernel: only the pooled Q4 tensor is
     written.  Emitted by the plan compiler (plan.fuse_stem_pool) where the max-pool is the conv's only reader.
     w_layout 12: the kernel reads the NCHW tensor itself (filter from prepare_stem_nchw_weights; W % 4 == 0) -- no row-packed
     copy.  A plan's static input then carries `x.prefed = (feed, pooled)`: whoever feeds the plan runs this kernel from the
-    caller's batch straight into `pooled` (`out` / `src_ptr` / `ctx` below), and the captured pass starts behind it."""
+    caller's batch straight into `pooled` (`out` / `src_ptr` / `ctx` below), and the captured pass starts behind it.
+    wino=44 (w_layout 12 only): the polyphase F(4,4) form of that kernel, filter from prepare_stem_wino_weights; a direct-form
+    filter that carries one (attach_stem_wino) runs that form too."""
     _f32(x, Kq, B, scale, shift)
+    if wino and (w_layout != STEM_POOL_NCHW or int(wino) != STEM_WINO):
+        raise ValueError("conv + maxpool: wino=%d is the F(4,4) form of w_layout %d only" % (STEM_WINO, STEM_POOL_NCHW))
+    if w_layout == STEM_POOL_NCHW and not wino and Kq in _STEM_WINO:
+        Kq, wino = _STEM_WINO[Kq], STEM_WINO      # a plan's stem filter with the F(4,4) form attached (Net picks it)
     if w_layout == STEM_POOL_NCHW and out is None and getattr(x, "prefed", None) is not None:
         return x.prefed[1]                         # a plan's static input: the feed has already run this step
     if is_q4(x) or not stem_pool_eligible(x.shape, Kq.shape, group, strides, dilations, pads):
@@ -241,7 +248,7 @@ def ConvPoolQ4(x, Kq, B=None, scale=None, shift=None, group=1, strides=(1, 1), d
         if w % 4 or xptr % 16:
             raise NotImplementedError("the NCHW stem + max-pool kernel needs W % 4 == 0 and a 16-byte aligned input")
         y = out if out is not None else _new_q4(n, cout, (ho + 1) // 2, (wo + 1) // 2, cx)
-        _lib.call("pl_conv2d_stem_pool_nchw_q4_f32", cx.handle, xptr, n, h, w, Kq.ptr, cout, _ptr(B), y.ptr, _ptr(scale),
+        _lib.call(_stem_entry(wino), cx.handle, xptr, n, h, w, Kq.ptr, cout, _ptr(B), y.ptr, _ptr(scale),
                   _ptr(shift), int(act), float(alpha), int(strip_rows))
         return y
     geom = (kw, strides[1], pads[0], pads[1])
@@ -258,14 +265,33 @@ def ConvPoolQ4(x, Kq, B=None, scale=None, shift=None, group=1, strides=(1, 1), d
     return y
 
 
-def stem_pool_feeder(x_shape, Kq, B, scale, shift, act, alpha, pooled, strip_rows=0):
+_STEM_WINO = weakref.WeakKeyDictionary()      # direct-form stem filter (w_layout 12) -> its F(4,4) filter
+
+
+def attach_stem_wino(Kq, K):
+    """Give the prepared stem filter `Kq` (prepare_stem_nchw_weights) the F(4,4) form of the OIHW filter `K` to run instead
+    (ConvPoolQ4, stem_pool_feeder), or take it away (K = None).  How a plan carries the form: the step, its w_layout and its
+    filter key stay what they are."""
+    if K is None:
+        _STEM_WINO.pop(Kq, None)
+    elif Kq not in _STEM_WINO:
+        _STEM_WINO[Kq] = prepare_stem_wino_weights(K)
+
+
+def _stem_entry(wino):
+    return "pl_conv2d_stem_pool_wino_q4_f32" if wino else "pl_conv2d_stem_pool_nchw_q4_f32"
+
+
+def stem_pool_feeder(x_shape, Kq, B, scale, shift, act, alpha, pooled, strip_rows=0, wino=0):
     """feed(src_ptr, ctx): the NCHW stem + max-pool kernel from the batch at `src_ptr` into the persistent tensor `pooled`, on
     `ctx`'s stream -- what `DeviceArray.prefed` holds for a plan's static input (Net._pack_static_inputs)."""
     n, _, h, w = (int(v) for v in x_shape)
     cout = int(Kq.shape[0])
+    if not wino and Kq in _STEM_WINO:
+        Kq, wino = _STEM_WINO[Kq], STEM_WINO
 
     def feed(src_ptr, ctx):
-        _lib.call("pl_conv2d_stem_pool_nchw_q4_f32", ctx.handle, src_ptr, n, h, w, Kq.ptr, cout, _ptr(B), pooled.ptr, _ptr(scale),
+        _lib.call(_stem_entry(wino), ctx.handle, src_ptr, n, h, w, Kq.ptr, cout, _ptr(B), pooled.ptr, _ptr(scale),
                   _ptr(shift), int(act), float(alpha), int(strip_rows))
     return feed
 

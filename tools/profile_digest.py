@@ -105,6 +105,8 @@ def expected_kernels(a):
     plan = re.sub(r"^wino\d+\[(.*)\]$", r"\1", plan) if algo == "direct" else plan
     if plan.startswith("as128"):
         return ["wino4_gemm_as_kernel"]      # filter-stationary GEMM stage of a 128-channel F(4x4,3x3) conv
+    if plan.startswith("stem+maxpool(nchw) F(4,4)"):
+        return ["conv_stem_wino_kernel"]     # the polyphase F(4,4) form of the same step
     if plan.startswith("stem+maxpool(nchw)"):
         return ["conv_stem_pool_kernel"]     # reads the NCHW batch itself; runs when the plan is fed, in front of the graph
     if plan.startswith("stem+maxpool"):
