@@ -633,6 +633,27 @@ int pl_resize_hwc_f32(pl_ctx *ctx, const float *x, float *y, int H, int W, int C
 int pl_tile_accumulate_f32(pl_ctx *ctx, const float *rst, float *buf, float *count, int h, int w,
                            int C, int r0, int c0, int OH, int OW, int margin);
 int pl_tile_normalise_f32(pl_ctx *ctx, float *buf, const float *count, int OH, int OW, int C);
+/* ---- uint8 image batches as net input ----
+ * y[n][c][oh][ow] = fl(fl(r * k[c]) + b[c]), y the float32 (N, Co, OH, OW) tensor a net reads; call it in front of pl_plan_run.
+ * x is a uint8 batch, (N, H, W, C) if nhwc else (N, C, H, W), and may start at any byte; C and Co in 1..4 (else
+ * PL_EUNSUPPORTED).  Output channel c reads source channel order[c] (host array of Co ints, each in [0, C); NULL: identity, and
+ * then Co == C).  k and b are host arrays of Co floats.  k, b and order travel as kernel arguments: nothing is allocated or
+ * uploaded, the call is asynchronous on ctx's stream.
+ * ra/rs (OH entries), ca/cs (OW entries): device tables as pl_resize_hwc_f32 takes them, all four or none.  None: OH == H,
+ * OW == W and r is the byte as a float.  Given: r is util.resize's sample (util.py:253-269) of the bytes, columns first,
+ * t = fl(fl(p[ca] * (1 - cs)) + fl(p[ca + 1] * cs)), then rows on t the same way; 1 - cs, 1 - rs in float32, no fused
+ * multiply-add anywhere.  Tables need nhwc != 0 (else PL_EUNSUPPORTED) and H, W >= 2 (else PL_EINVAL: the reference's index
+ * rule wraps there); entries are clamped to [0, H - 2] / [0, W - 2].
+ * Limit: fewer than 2^31 source bytes and fewer than 2^31 output floats, else PL_EUNSUPPORTED.  Every refusal comes before any
+ * launch and leaves y untouched.  Nothing outside x's N H W C bytes is read, nothing outside y's N Co OH OW floats written.
+ * Without tables a workgroup takes PL_IMAGE_U8_TILE_PIXELS consecutive pixels of a plane (planes are flat: H W pixels), a lane
+ * PL_IMAGE_U8_LANE_PIXELS of them, stored as one 16-byte word per channel plane where y is 16-byte aligned and H W % 4 == 0;
+ * with tables a lane takes PL_IMAGE_U8_LANE_PIXELS consecutive columns of one output row (16-byte stores where OW % 4 == 0). */
+#define PL_IMAGE_U8_TILE_PIXELS 1024
+#define PL_IMAGE_U8_LANE_PIXELS 4
+int pl_image_u8_nchw_f32(pl_ctx *ctx, const unsigned char *x, float *y, int N, int H, int W, int C, int nhwc,
+                         int Co, const int *order, int OH, int OW, const int *ra, const float *rs, const int *ca,
+                         const float *cs, const float *k, const float *b);
 /* split-K combine + epilogue (internal to conv, exported for tests) */
 int pl_splitk_reduce_f32(pl_ctx *ctx, const float *ws, int splits, float *y,
                          int N, int C, int inner, const float *bias,

@@ -16,6 +16,8 @@ PL_OK, PL_EINVAL, PL_EUNSUPPORTED, PL_ENOMEM, PL_EHIP, PL_ERCCL = range(6)
 NONZERO_BLOCK = 2048          # include/planer_hip.h PL_NONZERO_BLOCK
 INSTNORM_Q4_ONE_WG_PIXELS = 4096    # include/planer_hip.h PL_INSTNORM_Q4_ONE_WG_PIXELS
 INSTNORM_Q4_CHUNK_PIXELS = 2048     # include/planer_hip.h PL_INSTNORM_Q4_CHUNK_PIXELS
+IMAGE_U8_TILE_PIXELS = 1024         # include/planer_hip.h PL_IMAGE_U8_TILE_PIXELS
+IMAGE_U8_LANE_PIXELS = 4            # include/planer_hip.h PL_IMAGE_U8_LANE_PIXELS
 ACT_NONE, ACT_RELU, ACT_LEAKY = 0, 1, 2
 ACT_RES_AFTER = 16
 UNIQUE_ID_BYTES = 128
@@ -186,6 +188,7 @@ SIGNATURES = {
     "pl_topk_f32": [_P, _P, _I, _I, _I, _I, _I, _P, _P],
     "pl_lstm_cell_f32": [_P, _P, _P, _P, _P, _P, _P, _I, _I],
     "pl_resize_hwc_f32": [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P],
+    "pl_image_u8_nchw_f32": [_P, _P, _P, _I, _I, _I, _I, _I, _I, POINTER(c_int), _I, _I, _P, _P, _P, _P, POINTER(c_float), POINTER(c_float)],
     "pl_tile_accumulate_f32": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I],
     "pl_tile_normalise_f32": [_P, _P, _P, _I, _I, _I],
     "pl_splitk_reduce_f32": [_P, _P, _I, _P, _I, _I, _I, _P, _P, _P, _P, _I, c_double],

@@ -8,6 +8,7 @@
 #include "instnorm_q4_kernel.h"
 #include "groupnorm_q4_kernel.h"
 #include "pixel_shuffle_q4_kernel.h"
+#include "image_input_kernel.h"
 
 namespace {
 
@@ -879,6 +880,50 @@ int pl_resize_hwc_f32(pl_ctx *ctx, const float *x, float *y, int H, int W, int C
     CtxGuard g(ctx);
     resize_hwc_kernel<<<stream_grid(ctx, total), TPB, 0, ctx->stream>>>(x, y, (unsigned)total, W, C, OW, ra, rs, ca, cs,
                                                                      FastDiv(C), FastDiv(OW));
+    PL_LAUNCH_CHECK();
+    return PL_OK;
+}
+
+// uint8 image batch -> float32 NCHW (image_input_kernel.h).  Every refusal comes before any launch.
+int pl_image_u8_nchw_f32(pl_ctx *ctx, const unsigned char *x, float *y, int N, int H, int W, int C, int nhwc, int Co,
+                         const int *order, int OH, int OW, const int *ra, const float *rs, const int *ca, const float *cs,
+                         const float *k, const float *b) {
+    namespace ii = image_input;
+    PL_REQUIRE(ctx && k && b, PL_EINVAL, "pl_image_u8_nchw_f32: null argument");
+    PL_REQUIRE(N >= 0 && H > 0 && W > 0 && OH > 0 && OW > 0, PL_EINVAL, "pl_image_u8_nchw_f32: bad shape");
+    PL_REQUIRE(C >= 1 && C <= ii::MAX_C && Co >= 1 && Co <= ii::MAX_C, PL_EUNSUPPORTED,
+               "pl_image_u8_nchw_f32: 1 to 4 channels, got C = %d, Co = %d", C, Co);
+    PL_REQUIRE(order || Co == C, PL_EINVAL, "pl_image_u8_nchw_f32: no channel order given and Co != C");
+    ii::Affine af;
+    for (int c = 0; c < ii::MAX_C; ++c) {
+        af.k[c] = c < Co ? k[c] : 0.f;
+        af.b[c] = c < Co ? b[c] : 0.f;
+        af.order[c] = c < Co ? (order ? order[c] : c) : 0;
+        PL_REQUIRE(af.order[c] >= 0 && af.order[c] < C, PL_EINVAL, "pl_image_u8_nchw_f32: order[%d] = %d is no source channel", c,
+                   af.order[c]);
+    }
+    const bool tables = ra || rs || ca || cs;
+    PL_REQUIRE(!tables || (ra && rs && ca && cs), PL_EINVAL, "pl_image_u8_nchw_f32: all four sampling tables or none");
+    PL_REQUIRE(tables || (OH == H && OW == W), PL_EINVAL, "pl_image_u8_nchw_f32: OH x OW != H x W needs sampling tables");
+    PL_REQUIRE(!tables || nhwc, PL_EUNSUPPORTED, "pl_image_u8_nchw_f32: resize takes the (N, H, W, C) layout only");
+    PL_REQUIRE(!tables || (H >= 2 && W >= 2), PL_EINVAL, "pl_image_u8_nchw_f32: resize needs H, W >= 2");
+    const size_t HWo = (size_t)OH * OW;
+    PL_REQUIRE((size_t)N * H * W * C < (1ull << 31) && (size_t)N * Co * HWo < (1ull << 31), PL_EUNSUPPORTED,
+               "pl_image_u8_nchw_f32: 2^31 or more source bytes or output floats");
+    if (N == 0) return PL_OK;
+    PL_REQUIRE(x && y, PL_EINVAL, "pl_image_u8_nchw_f32: null argument");
+    CtxGuard g(ctx);
+    if (tables) {
+        const int groups = (OW + ii::LANE_PX - 1) / ii::LANE_PX;
+        const size_t total = (size_t)N * OH * groups;
+        ii::image_u8_resize_kernel<<<stream_grid(ctx, total), TPB, 0, ctx->stream>>>(x, y, total, H, W, C, Co, OH, OW, groups, ra,
+                                                                                 rs, ca, cs, af, aligned16(y) && OW % 4 == 0);
+    } else {
+        const unsigned tiles = cdiv(HWo, ii::TILE_PX);
+        const bool vec = aligned16(y) && HWo % 4 == 0;
+        if (nhwc) ii::image_u8_flat_kernel<true><<<(unsigned)N * tiles, TPB, 0, ctx->stream>>>(x, y, HWo, C, Co, tiles, af, vec);
+        else ii::image_u8_flat_kernel<false><<<(unsigned)N * Co * tiles, TPB, 0, ctx->stream>>>(x, y, HWo, C, Co, tiles, af, vec);
+    }
     PL_LAUNCH_CHECK();
     return PL_OK;
 }

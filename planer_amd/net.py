@@ -30,6 +30,7 @@ from . import q4 as _q4
 from .conv_layouts import DIRECT_Q4, IGEMM_NCHW, LAYOUTS, STEM_POOL, STEM_POOL_NCHW, WINO4_Q4, WINO43_Q4, experiment, suffix
 from .layer import layer_map, wrap
 from .plan import compile_front, fuse_upsample_concat, lower
+from .util import ImageFeed, ImageSpec
 
 STEM_WINO_DEFAULT = 1      # whether the stem + max-pool step takes the F(4,4) form where it applies
 
@@ -86,7 +87,11 @@ def _feed_static(ctx, dst, a, always=False):
     only reader of that input is the row-packed stem conv (Net._capture, `dst.packed`), the batch is re-laid straight
     into the packed image the graph reads -- that pass replaces the copy -- and the NCHW tensor is left alone.  Where that
     reader is the stem + max-pool kernel that takes NCHW itself (`dst.prefed`), the kernel runs HERE, from the caller's batch
-    into the pooled tensor the captured pass starts from: no copy and no re-layout at all."""
+    into the pooled tensor the captured pass starts from: no copy and no re-layout at all.
+    A uint8 image batch (`ImageFeed`, Net.image_input) is decoded straight into `dst`; the feed-time part then runs from there."""
+    if isinstance(a, ImageFeed):
+        a.decode_into(dst.ptr, ctx)
+        a, always = dst, False
     if dst.prefed is not None:
         if a.ptr % 16:                                   # (a view that starts off a 16-byte boundary: through the static tensor)
             _lib.call("pl_d2d", ctx.handle, dst.ptr, a.ptr, dst.nbytes)
@@ -360,6 +365,7 @@ class Net:
         self._streams_pick = {}      # compile key -> stream plan ("pipe3", "2x2", ...) chosen by measurement
         self.algo_misses = 0         # conv algorithm picks that had to be measured (no cached choice)
         self.stream_misses = 0       # stream-plan picks that had to be measured
+        self._image_in = {}          # input key (None: the first input) -> util.ImageSpec: uint8 batches that input also takes
 
     # ---- loading ----------------------------------------------------------------
     def load_json(self, inputs, inits, body, flow, debug=False):
@@ -408,6 +414,43 @@ class Net:
         """Re-read the host mirror after the device blob was written by a broadcast."""
         self._host[:] = self._blob.get()
         self._plans, self._extra = {}, {}
+
+    def image_input(self, k, b, layout="nhwc", size=None, order=None, key=None):
+        """Input `key` (default: the first) also takes uint8 image batches, host ndarray or DeviceArray, (N, H, W, C) for
+        layout "nhwc" or (N, C, H, W) for "nchw": the net then reads fl(fl(x * k[c]) + b[c]) as float32 NCHW (k, b per channel
+        from util.image_affine), channel c taken from source channel order[c], resized to `size` by util.resize's rule where
+        the batch's H x W differs.  The decode is one kernel (pl_image_u8_nchw_f32) in front of the pass; a uint8 batch runs the
+        plan of the float32 tensor it decodes to.  float32 inputs are taken as before.  Calling it again replaces the
+        declaration."""
+        self._image_in[key] = ImageSpec(k, b, layout, size, order)
+        u8 = lambda sig: any(dt == "uint8" for _, dt in sig)        # noqa: E731
+        self._plans = {s: p for s, p in self._plans.items() if not u8(s[1:])}
+        self._eager_prog = {s: p for s, p in self._eager_prog.items() if not u8(s)}
+        return self
+
+    def _image_spec(self, pos):
+        name = self.input[pos] if pos < len(self.input) else None
+        return self._image_in.get(name, self._image_in.get(None) if pos == 0 else None)
+
+    def _image_feeds(self, xs):
+        """uint8 batches of inputs declared with `image_input` (host arrays are uploaded as they are) -> ImageFeeds."""
+        xs = list(xs)
+        for i, a in enumerate(xs if self._image_in else ()):
+            spec = self._image_spec(i)
+            if spec is not None and isinstance(a, (DeviceArray, numpy.ndarray)) and a.dtype == numpy.uint8:
+                xs[i] = spec.bind(hip.asarray(a, ctx=self.ctx))
+        return xs
+
+    def _signature(self, xs):
+        """(shape, dtype) per input as a plan is keyed: a declared uint8 batch counts as the float32 tensor it decodes to."""
+        sig = []
+        for i, a in enumerate(xs):
+            spec = self._image_spec(i) if self._image_in else None
+            if spec is not None and not isinstance(a, ImageFeed) and a.dtype == numpy.uint8:
+                sig.append((spec.geometry(a.shape)[1], "float32"))
+            else:
+                sig.append((tuple(a.shape), str(a.dtype)))
+        return tuple(sig)
 
     def half(self):
         raise NotImplementedError("planer_amd computes the hot path in float32 only (BASELINE metric)")
@@ -809,7 +852,7 @@ class Net:
     def compile(self, *xs, mode="latency"):
         """(see _compile: the plan's program is fused under this mode's conv algorithm tables)"""
         with self.picking(mode):
-            return self._compile(*xs, mode=mode)
+            return self._compile(*self._image_feeds(xs), mode=mode)
 
     def _compile(self, *xs, mode="latency"):
         """Build (or fetch) the captured plan for these device inputs.  `mode` only affects how
@@ -820,6 +863,7 @@ class Net:
         if plan is not None:
             self._ensure_streams(plan)
             return plan
+        xs = [a.materialise() if isinstance(a, ImageFeed) else a for a in xs]      # (a uint8 batch: compiled on its decoded form)
         ctx = self.ctx
         shapes = {k: a.shape for k, a in zip(self.input, xs)}
         shapes.update({k: w.shape for k, w in zip(self.inits, self.weights)})
@@ -1153,7 +1197,9 @@ class Net:
         """Inputs of a one-graph or sub-batch plan, copied on the net's OWN stream (where the caller produced them);
         `launch()` forks the side streams behind that point."""
         for s, a in zip(plan.inputs, xs):
-            if isinstance(plan, _MultiPlan) or not isinstance(a, DeviceArray):
+            if isinstance(a, ImageFeed):                 # decoded into the static tensor, then the feed pass from there
+                _feed_static(self.ctx, s, a)
+            elif isinstance(plan, _MultiPlan) or not isinstance(a, DeviceArray):
                 if a is not s:
                     s.copy_from(a)
                 if s.prefed is not None or s.packed is not None:        # (a host array: through the static tensor, then the feed pass)
@@ -1181,10 +1227,11 @@ class Net:
             # batch while the other replicas compute; a copy enqueued on a stream would hold that stream's hardware queue, and
             # the replica that shares it, for as long).  The buffer is free once the replica's previous feed has read it.
             hx = [numpy.require(i, requirements="C") if b else i for i, b in zip(x, host)]
-            plan = self._plans.get(("throughput",) + tuple((a.shape, str(a.dtype)) for a in hx))
+            plan = self._plans.get(("throughput",) + self._signature(hx))
             if isinstance(plan, _PipelinePlan) and route == "staged":       # pinned ring + DMA on the replica's stream (pl_h2d_staged)
                 self._ensure_streams(plan)
-                xs = [hip.asarray(i, ctx=self.ctx, consumer=plan.replicas[plan.turn].ctx) if b else i for i, b in zip(hx, host)]
+                xs = self._image_feeds(hip.asarray(i, ctx=self.ctx, consumer=plan.replicas[plan.turn].ctx) if b else i
+                                       for i, b in zip(hx, host))
             elif isinstance(plan, _PipelinePlan):
                 self._ensure_streams(plan)
                 rp, direct = plan.replicas[plan.turn], True
@@ -1203,10 +1250,11 @@ class Net:
                             _lib.call("pl_h2d_direct", rp.ctx.handle, d.ptr, a.ctypes.data, a.nbytes)
                         a = d
                     xs.append(a)
+                xs = self._image_feeds(xs)            # (a uint8 batch is decoded out of the replica's upload buffer)
             else:
                 plan = None
         if plan is None:
-            xs = [hip.asarray(i, ctx=self.ctx) if b else i for i, b in zip(x, host)]
+            xs = self._image_feeds(hip.asarray(i, ctx=self.ctx) if b else i for i, b in zip(x, host))
             if self.use_graph and not self.profile:
                 try:
                     plan = self.compile(*xs, mode="throughput")
@@ -1265,8 +1313,9 @@ class Net:
         need = any(host)
         if need:
             x = [hip.asarray(i, ctx=self.ctx) if b else i for i, b in zip(x, host)]
+        x = self._image_feeds(x)
         graphable = (self.use_graph and not key.get("debug") and not self.profile
-                     and all(isinstance(i, DeviceArray) for i in x))
+                     and all(isinstance(i, (DeviceArray, ImageFeed)) for i in x))
         if graphable:
             try:
                 rst = self._replay(list(x), private=not need)          # host in -> host out: .get() reads the plan's buffers
@@ -1276,6 +1325,7 @@ class Net:
                 # step by step from here on
                 self.use_graph = graphable = False
         if not graphable:
+            x = [i.materialise() if isinstance(i, ImageFeed) else i for i in x]      # eager routes: a fresh decoded array
             if self._eager_prog and not key.get("debug") and not self.profile and all(isinstance(i, DeviceArray) for i in x):
                 rst = self._interpret(self._eager_program(list(x)), list(x))
             else:

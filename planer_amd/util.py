@@ -61,6 +61,114 @@ def resize(img, size):
     return y
 
 
+# ---- uint8 image batches as net input ----------------------------------------------------------------------
+def image_affine(mean, std, scale=255.0):
+    """(k, b) with x / scale, - mean, / std folded into one multiply and one add per element: k = 1 / (scale * std),
+    b = -mean / std, evaluated in float64 and rounded once to float32.  mean and std: one value per output channel."""
+    mean = numpy.atleast_1d(numpy.asarray(mean, numpy.float64))
+    std = numpy.atleast_1d(numpy.asarray(std, numpy.float64))
+    mean, std = numpy.broadcast_arrays(mean, std)
+    return (1.0 / (float(scale) * std)).astype(numpy.float32), (-mean / std).astype(numpy.float32)
+
+
+class ImageSpec:
+    """How a uint8 image batch becomes a net's float32 NCHW input: y[:, c] = fl(fl(r * k[c]) + b[c]) with r the byte of source
+    channel order[c], or util.resize's sample of those bytes where `size` differs from the batch's H x W.  Host values only."""
+
+    def __init__(self, k, b, layout="nhwc", size=None, order=None):
+        k, b = numpy.atleast_1d(numpy.asarray(k)), numpy.atleast_1d(numpy.asarray(b))
+        if layout not in ("nhwc", "nchw"):
+            raise ValueError("image input: layout is 'nhwc' or 'nchw', got %r" % (layout,))
+        if k.ndim != 1 or k.shape != b.shape or not 1 <= k.size <= 4:
+            raise ValueError("image input: k and b hold one value per output channel (1 to 4), got shapes %s and %s" % (k.shape, b.shape))
+        if order is not None:
+            order = tuple(int(c) for c in order)
+            if len(order) != k.size or min(order) < 0 or max(order) > 3:
+                raise ValueError("image input: order names one source channel (0..3) per output channel, got %r" % (order,))
+        if size is not None:
+            if len(tuple(size)) != 2 or min(size) < 1:
+                raise ValueError("image input: size is (height, width), got %r" % (size,))
+            size = (int(size[0]), int(size[1]))
+            if layout == "nchw":
+                raise NotImplementedError("image input: resizing takes the 'nhwc' layout only")
+        self.k, self.b = k.astype(numpy.float32), b.astype(numpy.float32)
+        self.layout, self.size, self.order, self.channels = layout, size, order, int(k.size)
+        self._k = (_lib.c_float * self.channels)(*self.k.tolist())
+        self._b = (_lib.c_float * self.channels)(*self.b.tolist())
+        self._order = (_lib.c_int * self.channels)(*order) if order is not None else None
+
+    def geometry(self, shape):
+        """(N, H, W, C) of a uint8 batch of `shape` in this layout and the (N, Co, OH, OW) it decodes to."""
+        if len(shape) != 4:
+            raise ValueError("image input: a uint8 batch is 4-d (%s), got shape %s" % (self.layout, tuple(shape)))
+        n, h, w, c = shape if self.layout == "nhwc" else (shape[0], shape[2], shape[3], shape[1])
+        if not 1 <= c <= 4:
+            raise NotImplementedError("image input: 1 to 4 source channels, got %d in shape %s (%s)" % (c, tuple(shape), self.layout))
+        if self.order is None and self.channels != c:
+            raise ValueError("image input: %d values in k for %d source channels and no order" % (self.channels, c))
+        if self.order is not None and max(self.order) >= c:
+            raise ValueError("image input: order %r names a channel the %d-channel batch does not have" % (self.order, c))
+        oh, ow = self.size if self.size is not None else (h, w)
+        if (oh, ow) != (h, w) and (h < 2 or w < 2):
+            raise ValueError("image input: resizing needs H, W >= 2, got %d x %d" % (h, w))
+        return (n, h, w, c), (n, self.channels, oh, ow)
+
+    def tables(self, ctx, src, out):
+        """util.resize's sampling tables for (H, W) -> (OH, OW) as device arrays, or None where the sizes agree.  Kept on the
+        Context object for its lifetime (every stream of the device may read them: the upload is over on return)."""
+        key = (src[1], src[2], out[2], out[3])
+        if key[:2] == key[2:]:
+            return None
+        cache = ctx.__dict__.setdefault("_image_tables", {})
+        if key not in cache:
+            ra, rs = _axis_samples(key[0], key[2])
+            ca, cs = _axis_samples(key[1], key[3])
+            cache[key] = tuple(hip.asarray(a, ctx=ctx) for a in (ra, rs, ca, cs))
+            ctx.synchronize()
+        return cache[key]
+
+    def bind(self, x):
+        return ImageFeed(self, x)
+
+
+class ImageFeed:
+    """A uint8 device batch standing for the float32 tensor it decodes to: `shape` / `dtype` are the decoded tensor's (a plan
+    is looked up by them), `decode_into` writes that tensor wherever the caller wants it, on the stream the caller names."""
+
+    def __init__(self, spec, x):
+        if not isinstance(x, DeviceArray) or x.dtype != numpy.uint8:
+            raise TypeError("image input: expected a uint8 DeviceArray, got %r" % (x,))
+        self.spec, self.u8, self.ctx = spec, x, x.ctx
+        self.src, self.shape = spec.geometry(x.shape)
+        self.dtype, self.ndim = numpy.dtype(numpy.float32), 4
+        self.tabs = spec.tables(x.ctx, self.src, self.shape)
+
+    @property
+    def nbytes(self):
+        return 4 * self.shape[0] * self.shape[1] * self.shape[2] * self.shape[3]
+
+    def decode_into(self, ptr, ctx=None):
+        n, h, w, c = self.src
+        sp, t = self.spec, self.tabs
+        _lib.call("pl_image_u8_nchw_f32", (ctx or self.ctx).handle, self.u8.ptr, ptr, n, h, w, c, int(sp.layout == "nhwc"),
+                  sp.channels, sp._order, self.shape[2], self.shape[3], *([a.ptr for a in t] if t else [None] * 4), sp._k, sp._b)
+
+    def materialise(self):
+        y = hip.empty(self.shape, ctx=self.ctx)
+        self.decode_into(y.ptr)
+        return y
+
+    def rows(self, lo, hi):
+        return ImageFeed(self.spec, self.u8.rows(lo, hi))
+
+
+def decode_images(x, k, b, layout="nhwc", size=None, order=None):
+    """A uint8 DeviceArray batch, (N, H, W, C) or (N, C, H, W), as the float32 (N, Co, OH, OW) DeviceArray
+    fl(fl(r * k[c]) + b[c]) (pl_image_u8_nchw_f32): r is the byte of source channel order[c] (default: c), bilinearly resampled
+    to `size` as util.resize does where that differs from H x W.  (k, b) from `image_affine`.  Asynchronous on x's stream."""
+    return ImageFeed(ImageSpec(k, b, layout, size, order), x).materialise()
+
+
 def _window(img, rc):
     """img[rows, cols] as a contiguous device array."""
     r, c = rc
