@@ -8,34 +8,45 @@
 // transform.  Per 16 output channels and conv-row pair that is 4 tile blocks x 7 frequencies x 11 = 308 MFMAs
 // (v_mfma_f32_16x16x4_f32) where the direct form issues 2 x 7 x 37 = 518.
 //
+// V, the transformed input, is a RING OF K-QUADS: V[f][ring quad][tile slot][4].  With a the input row counted from the strip's
+// first (2 c0 - 3 in the image) and rho = 3 a + c a staged (input row, channel) row, k = 2 rho + phase = 6 a + 2 c + phase is
+// absolute over the strip, and quad Q = k / 4 sits at ring position Q mod 20.  Step t (conv rows 2 t, 2 t + 1 of the strip, one
+// pooled row) reads input rows a = 4 t .. 4 t + 8 = quads 6 t .. 6 t + 13; its conv row r multiplies k = 24 t + 12 r .. + 43, which
+// starts on a quad, so filter quad j (0 .. 10) meets ring position (6 t + 3 r + j) mod 20 and the filter in registers is the same
+// in every step: nothing rotates.  A step adds 4 input rows = 12 staged rows = 6 quads (6 t + 13, upper half, .. 6 t + 19, lower
+// half); 14 + 6 = 20, so the quads step t + 1 adds are not among those step t reads.
+//
 // A step of the persistent workgroup (8 waves; wave (mb, r) = 16 output channels x conv row r of the pair):
-//   1. the 27 (input row, channel) rows under the pair have landed in X by LDS-DMA;
-//   2. TRANSFORM, LDS -> LDS: item (rho, tile) reads floats 8 tile .. + 15 of row rho (4 x ds_read_b128), applies B^T to the even
-//      and to the odd phase and writes the 7 x 2 values to V[f][k-quad][tile slot][4] at k = 2 rho + phase (7 x ds_write_b64);
-//      the conv row r of the pair multiplies k = 12 r .. 12 r + 43 of it: rows 2 r .. 2 r + 6, 3 channels, 2 phases in the order
-//      pl_conv2d_prepare_stem_wino_f32 packs the filter.  Every one of the 9 rows is transformed again in the next step (5 of
-//      them are shared): 756 items of ~60 flops on 512 threads against 1232 MFMAs;
-//   3. the rows of the next step are requested, and the MFMAs run in two halves of one tile block (16 tiles) x 7 frequencies =
-//      28 accumulator registers each.  A B fragment is one ds_read_b128: lane (tile li, quarter kk) reads quad 4 u + kk of its
-//      tile, 4 MFMAs; with 128 tile slots' worth of bytes between quads the two lane quarters of a b128 group cover the 16 slots
-//      of a bank row (conflict-free).  The last 3 quads are one MFMA each (ds_read_b32, element kk).  The FILTER never enters
-//      LDS: a lane's 77 A values (7 f x 11 quads, one channel) are loaded once per workgroup and stay in registers.
-//      Frequencies run 4 (then 3) abreast, so two MFMAs on one accumulator are 3-4 issues apart;
+//   1. top barrier: V of step t is whole and the 12 staged rows that step t + 1 adds have landed in X by LDS-DMA;
+//   2. the MFMAs run in two halves of one tile block (16 tiles) x 7 frequencies = 28 accumulator registers each.  A B fragment
+//      is one ds_read_b128: lane (tile li, quarter kk) reads quad 4 u + kk of its tile, 4 MFMAs; with 128 tile slots' worth of
+//      bytes between quads the two lane quarters of a b128 group cover the 16 slots of a bank row (conflict-free, wherever the
+//      quad sits in the ring).  The last 3 quads are one MFMA each (ds_read_b32, element kk).  k = 42, 43 of a conv row lie under
+//      zero filter values, but in the ring they are another row's values -- stale, or being written -- so every wave multiplies
+//      zeros there (`cut`), or an inf of a row the conv row never reads would come out as inf x 0.  The FILTER never enters LDS: a
+//      lane's 77 A values (7 f x 11 quads, one channel) are loaded once per workgroup and stay in registers.  Frequencies run
+//      4 (then 3) abreast, so two MFMAs on one accumulator are 3-4 issues apart;
+//   3. TRANSFORM of step t + 1, LDS -> LDS, riding in half 0's MFMAs: item (staged row, tile) = thread tid < 12 x 28 = 336 reads
+//      floats 8 tile .. + 15 of its row (4 x ds_read_b128, behind MFMA group 3), applies B^T to the even and to the odd phase and
+//      writes the 7 x 2 values at k = 2 rho + phase (7 x ds_write_b64, behind group 4).  The 5 input rows a step shares with the
+//      one before are not transformed again.  Behind the mid-step barrier X is empty and the rows of step t + 2 are requested.
+//      Step 0 alone transforms its 9 input rows (27 staged rows, 756 items) in a phase of its own, staged in the pooled-row ring,
+//      which is idle until then;
 //   4. the output transform A^T is lane-local (7 accumulators -> 4 conv pixels x 4 channels), then the fused tail, the
 //      horizontal 3-max -- pooled column 2 t takes pixel 4 t - 1 from the neighbouring lane (DPP), 2 t + 1 is lane-local -- and
-//      two 16-byte cells per lane into the ring.  It rides in the other half's MFMAs: half 0 carries the tail of the previous
-//      step's half 1, the hand-over barrier and the pooled row, half 1 the tail of this step's half 0.
-// LDS (of 160 KB): V 7 f x 14 quads x 32 slots x 16 B = 49.0 KB, X 26.0 KB (one buffer: the transform has emptied it when the
-// next rows are requested), the ring 4 x 16 x 56 x 16 B = 56.0 KB: 131 KB.  With the filter in LDS (77 KB per 64 channels) V
-// could not stay whole; 32-channel workgroups would repeat the transform and the input traffic.  Registers: 77 filter + 2 x 28
-// accumulators + 2 x 16 fragments.
+//      two 16-byte cells per lane into the ring of pooled rows.  It rides in the other half's MFMAs: half 0 carries the tail of
+//      the previous step's half 1, the hand-over barrier and the pooled row, half 1 the tail of this step's half 0.
+// LDS (of 160 KB): V 7 f x 20 quads x 32 slots x 16 B = 70.0 KB, X 12.0 KB, the ring of pooled rows 4 x 16 x 56 x 16 B = 56.0 KB:
+// 138 KB.  With the filter in LDS (77 KB per 64 channels) V could not stay whole; 32-channel workgroups would repeat the transform
+// and the input traffic.  Registers: 77 filter + 2 x 28 accumulators + 2 x 16 fragments + 16 of the transform item.
 // Width: one chunk of up to 112 conv columns = 28 tiles in 32 slots (slots 28 .. 31 hold zeros); wider maps are cut into chunks as
 // in the direct form.  Non-finite inputs spread over their tile (and, within it, over the conv rows that read the input row).
 constexpr int SW_F = 7, SW_KQ = 11, SW_K = 42;      // frequencies, filter k-quads, real k values
-constexpr int SW_VQ = 14, SW_TS = 32;               // k-quads of V (9 rows x 3 channels x 2 phases = 54 -> 56), tile slots
-constexpr int SW_TILES = 28, SW_XROWS = 27;         // tiles per chunk, staged (input row, channel) rows
+constexpr int SW_VQ = 20, SW_TS = 32;               // ring quads of V (a step reads 14: 9 rows x 3 channels x 2 phases = 54 -> 56, the next adds 6), tile slots
+constexpr int SW_TILES = 28;                        // tiles per chunk
+constexpr int SW_XROWS0 = 27, SW_XROWS = 12;        // staged (input row, channel) rows: the 9 input rows of step 0, the 4 new ones of a step
 constexpr int SW_XROW = 244;                        // floats per staged row: 4 left + 2 per conv column + the last tile's reach, 61 cells
-constexpr int SW_X_FLOATS = (SW_XROWS * (SW_XROW / 4) + 63) / 64 * 256;
+constexpr int sw_x_floats(int rows) { return (rows * (SW_XROW / 4) + 63) / 64 * 256; }
 constexpr int SW_FQ = SW_VQ * SW_TS * 4;            // floats of V per frequency
 constexpr int SW_PC = 56, SW_HP_CELLS = 16 * SW_PC;
 // G of F(4,4) on the nodes 0, 1, -1, 2, -2, 1/2, inf (row f, tap a)
@@ -68,8 +79,10 @@ __device__ __forceinline__ void sw_bt(const float d0, const float d1, const floa
 
 __global__ void __launch_bounds__(512) conv_stem_wino_kernel(const StemPoolArgs p) {
     __shared__ __attribute__((aligned(16))) float V[SW_F * SW_FQ];
-    __shared__ __attribute__((aligned(16))) float X[SW_X_FLOATS];
+    __shared__ __attribute__((aligned(16))) float X[sw_x_floats(SW_XROWS)];
     __shared__ __attribute__((aligned(16))) float4 HP[4 * SW_HP_CELLS];
+    static_assert(sw_x_floats(SW_XROWS0) <= 16 * SW_HP_CELLS, "the rows of step 0 are staged in the pooled-row ring");
+    float *X0 = reinterpret_cast<float *>(HP);              // step 0 only: nothing enters the ring before its transform is done
     typedef __attribute__((address_space(3))) float lds_float;
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -114,38 +127,45 @@ __global__ void __launch_bounds__(512) conv_stem_wino_kernel(const StemPoolArgs 
             }
         }
     }
-    // V starts as zeros: the tile slots 28 .. 31 and the k values 54, 55 are never written
+    // V starts as zeros: the tile slots 28 .. 31 are never written
     for (int i = tid; i < SW_F * SW_FQ / 4; i += 512) reinterpret_cast<float4 *>(V)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
 
-    // ---- input rows of step t: 27 rows (input row r, channel c) of 61 cells; cell j = input columns 2 x0 - 4 + 4 j .. + 3 of row hr0 - 3 + r
-    auto load_rows = [&](int t) {
-        const int hr0 = 2 * (c0 + 2 * t);
-        constexpr int CPR = SW_XROW / 4, CELLS = SW_XROWS * CPR;
+    // ---- staged rows: ROWS (input row, channel) rows of 61 cells from absolute row rho0 = 3 a + c on (a: input row of the strip,
+    // 2 c0 - 3 + a in the image; step t reads a = 4 t .. 4 t + 8); cell j = input columns 2 x0 - 4 + 4 j .. + 3
+    auto load_rows = [&](auto rows, float *buf, int rho0) {
+        constexpr int CPR = SW_XROW / 4, CELLS = decltype(rows)::value * CPR;
         for (int pc = wave; pc * 64 < CELLS; pc += 8) {
             const int idx = pc * 64 + lane;
             const int rr = idx / CPR, j = idx - rr * CPR;
-            const int r = rr / 3, c = rr - 3 * r;
-            const int h = hr0 - 3 + r, xin = 2 * x0 - 4 + 4 * j;
+            const int a = (rho0 + rr) / 3, c = rho0 + rr - 3 * a;
+            const int h = 2 * c0 - 3 + a, xin = 2 * x0 - 4 + 4 * j;
             const bool ok = idx < CELLS && (unsigned)h < (unsigned)p.H && xin >= 0 && xin + 3 < p.W;
             const int off = ok ? (int)(((((unsigned)n * 3u + (unsigned)c) * (unsigned)p.H + (unsigned)h) * (unsigned)p.W + (unsigned)xin) << 2) : OOB;
-            if (idx < CELLS) __builtin_amdgcn_raw_ptr_buffer_load_lds(xrsrc, (lds_float *)(X + pc * 256), 16, off, 0, 0, 0);
+            if (idx < CELLS) __builtin_amdgcn_raw_ptr_buffer_load_lds(xrsrc, (lds_float *)(buf + pc * 256), 16, off, 0, 0, 0);
         }
     };
-    load_rows(0);
+    // the rows step t adds to the 5 it shares with step t - 1: a = 4 t + 5 .. 4 t + 8
+    auto load_step = [&](int t) { load_rows(std::integral_constant<int, SW_XROWS>{}, X, 12 * t + 15); };
+    load_rows(std::integral_constant<int, SW_XROWS0>{}, X0, 0);
 
-    // ---- X -> V: conv column 4 t + jj, tap v sits at float 8 t + 2 jj + v + 1 of its row: the even phase is the odd floats ----
-    auto transform = [&]() {
-        for (int it = tid; it < SW_XROWS * SW_TILES; it += 512) {
-            const int rho = it / SW_TILES, tt = it - rho * SW_TILES;
-            const float4 *src = reinterpret_cast<const float4 *>(X + rho * SW_XROW + 8 * tt);
-            const float4 a = src[0], b = src[1], c = src[2], d = src[3];
-            float ev[SW_F], od[SW_F];
-            sw_bt(a.y, a.w, b.y, b.w, c.y, c.w, d.y, ev);
-            sw_bt(a.z, b.x, b.z, c.x, c.z, d.x, d.z, od);
-            float *dst = V + ((rho >> 1) * SW_TS + tt) * 4 + 2 * (rho & 1);
+    // ---- staged rows -> V: conv column 4 t + jj, tap v sits at float 8 t + 2 jj + v + 1 of its row: the even phase is the odd
+    // floats.  Row rho is k = 2 rho, 2 rho + 1: half of quad rho / 2, at ring position (rho / 2) mod SW_VQ.  An item is staged row
+    // rr of the buffer (absolute row rho0 + rr) x tile tt, in two parts: 4 x ds_read_b128, then B^T and 7 x ds_write_b64 ----
+    auto item_load = [&](const float *buf, int it, float4 (&s)[4]) {
+        const int rr = it / SW_TILES, tt = it - rr * SW_TILES;
+        const float4 *src = reinterpret_cast<const float4 *>(buf + rr * SW_XROW + 8 * tt);
+        s[0] = src[0]; s[1] = src[1]; s[2] = src[2]; s[3] = src[3];
+    };
+    auto item_store = [&](int rho0, int it, const float4 (&s)[4]) {
+        const int rr = it / SW_TILES, tt = it - rr * SW_TILES, rho = rho0 + rr;
+        const float4 a = s[0], b = s[1], c = s[2], d = s[3];
+        float ev[SW_F], od[SW_F];
+        sw_bt(a.y, a.w, b.y, b.w, c.y, c.w, d.y, ev);
+        sw_bt(a.z, b.x, b.z, c.x, c.z, d.x, d.z, od);
+        const int q = (rho0 >> 1) % SW_VQ + (((rho0 & 1) + rr) >> 1);                // (rho / 2) mod SW_VQ: the first term is wave-uniform
+        float *dst = V + ((q >= SW_VQ ? q - SW_VQ : q) * SW_TS + tt) * 4 + 2 * (rho & 1);
 #pragma unroll
-            for (int f = 0; f < SW_F; ++f) *reinterpret_cast<float2 *>(dst + f * SW_FQ) = make_float2(ev[f], od[f]);
-        }
+        for (int f = 0; f < SW_F; ++f) *reinterpret_cast<float2 *>(dst + f * SW_FQ) = make_float2(ev[f], od[f]);
     };
 
     // tail parameters of this lane's channel quad (a lane of the 16x16 C layout holds rows 4 (lane / 16) .. + 3 of its column)
@@ -237,12 +257,17 @@ __global__ void __launch_bounds__(512) conv_stem_wino_kernel(const StemPoolArgs 
     // the MFMAs of one tile block: 6 groups G = 3 b + g -- frequencies 4 b .. (4 abreast, then 3), g = 0, 1: quads 4 g + kk
     // (4 MFMAs per frequency), g = 2: quads 8 .. 10 (3).  Fragments one group ahead in two register sets; ride(G) is what
     // rides along behind group G.
-    auto mma_half = [&](auto tbc, sp_f32x4 (&acc)[SW_F], auto &&ride) {
+    auto mma_half = [&](auto tbc, int t, sp_f32x4 (&acc)[SW_F], auto &&ride) {
         constexpr int tb = decltype(tbc)::value;
-        const float *vb = V + ((3 * rsel + kk) * SW_TS + 16 * tb + li) * 4;           // + f SW_FQ + 512 g
-        const float *vt = V + ((3 * rsel + 8) * SW_TS + 16 * tb + li) * 4 + kk;      // + f SW_FQ + 128 j
-        // conv row 0 of the pair: k = 42, 43 of the last quad are real values of V under zero filter values -- multiply zeros
-        const bool cut = rsel == 0 && kk >= 2;
+        // filter quad j of the wave's conv row is absolute quad 6 t + 3 rsel + j: ring position (qb + j) mod SW_VQ
+        const int qb = (6 * t + 3 * rsel) % SW_VQ;
+        auto at = [&](int j) { return V + ((qb + j >= SW_VQ ? qb + j - SW_VQ : qb + j) * SW_TS + 16 * tb + li) * 4; };
+        const float *vb[2] = {at(kk), at(4 + kk)};                                   // + f SW_FQ
+        // k = 42, 43 of the last quad lie under zero filter values, but in the ring they are another row's values -- the other
+        // conv row's, stale ones, or those the riding transform is writing: multiply zeros, and do not even read them (the lanes
+        // kk >= 2 load k = 40, 41 again, which nothing writes during the step, and drop them)
+        const bool cut = kk >= 2;
+        const float *vt[3] = {at(8) + kk, at(9) + kk, at(10) + (kk & 1)};            // + f SW_FQ
 #pragma unroll
         for (int f = 0; f < SW_F; ++f) acc[f] = (sp_f32x4){0.f, 0.f, 0.f, 0.f};
         float4 fb[2][4];
@@ -253,11 +278,11 @@ __global__ void __launch_bounds__(512) conv_stem_wino_kernel(const StemPoolArgs 
                 const int f = 4 * b + fi;
                 if (f >= SW_F) continue;
                 if (g < 2) {
-                    fb[set][fi] = *reinterpret_cast<const float4 *>(vb + f * SW_FQ + 512 * g);
+                    fb[set][fi] = *reinterpret_cast<const float4 *>(vb[g] + f * SW_FQ);
                 } else {
-                    fb[set][fi].x = vt[f * SW_FQ];
-                    fb[set][fi].y = vt[f * SW_FQ + 128];
-                    const float last = vt[f * SW_FQ + 256];
+                    fb[set][fi].x = vt[0][f * SW_FQ];
+                    fb[set][fi].y = vt[1][f * SW_FQ];
+                    const float last = vt[2][f * SW_FQ];
                     fb[set][fi].z = cut ? 0.f : last;
                 }
             }
@@ -284,21 +309,34 @@ __global__ void __launch_bounds__(512) conv_stem_wino_kernel(const StemPoolArgs 
         }
     };
 
+    // step 0: all 9 input rows, a phase of its own
+    if (p.steps > 1) load_step(1);
+    __syncthreads();                                     // the rows of steps 0 and 1 have landed (vmcnt)
+    {
+        float4 s[4];
+        for (int it = tid; it < SW_XROWS0 * SW_TILES; it += 512) {
+            item_load(X0, it, s);
+            item_store(0, it, s);
+        }
+    }
+    float4 xs[4];                                        // thread tid < 336 transforms item tid of step t + 1 while step t multiplies
     for (int t = 0; t < p.steps; ++t) {
-        __syncthreads();                                 // the rows of step t have landed (vmcnt); V is free
-        transform();
-        __syncthreads();                                 // V is whole; X is free
-        if (t + 1 < p.steps) load_rows(t + 1);
-        // half 0 carries the tail of the previous step's half 1, the barrier that completes ring rows 2 t - 2, 2 t - 1, the pooled row
-        mma_half(std::integral_constant<int, 0>{}, accA, [&](int G) {
+        __syncthreads();                                 // V of step t is whole; the rows of step t + 1 have landed (vmcnt)
+        const bool more = t + 1 < p.steps && tid < SW_XROWS * SW_TILES;
+        // half 0 carries the tail of the previous step's half 1, the barrier that completes ring rows 2 t - 2, 2 t - 1, the pooled
+        // row, and the transform of step t + 1: its 6 ring quads are not among the 14 this step reads
+        mma_half(std::integral_constant<int, 0>{}, t, accA, [&](int G) {
             if (t >= 1) {
                 if (G == 0) tail_block(accB, 1, 2 * (t - 1) + rsel);
                 if (G == 1) lds_barrier();
                 if (t >= 2 && (G == 2 || G == 3)) pool_half(t - 2, G - 2);
             }
+            if (G == 3 && more) item_load(X, tid, xs);
+            if (G == 4 && more) item_store(12 * t + 27, tid, xs);
         });
-        lds_barrier();                                   // the pooled row has been read: its ring rows take rows 2 t, 2 t + 1
-        mma_half(std::integral_constant<int, 1>{}, accB, [&](int G) {
+        lds_barrier();                                   // the pooled row has been read: its ring rows take rows 2 t, 2 t + 1; X is free
+        if (t + 2 < p.steps) load_step(t + 2);
+        mma_half(std::integral_constant<int, 1>{}, t, accB, [&](int G) {
             if (G == 0) tail_block(accA, 0, 2 * t + rsel);
         });
     }
