@@ -654,6 +654,33 @@ int pl_tile_normalise_f32(pl_ctx *ctx, float *buf, const float *count, int OH, i
 int pl_image_u8_nchw_f32(pl_ctx *ctx, const unsigned char *x, float *y, int N, int H, int W, int C, int nhwc,
                          int Co, const int *order, int OH, int OW, const int *ra, const float *rs, const int *ca,
                          const float *cs, const float *k, const float *b);
+/* ---- uint8 images and label maps as net output ----
+ * Both read x, the float32 (N, C, H, W) tensor a net wrote (any 4-byte boundary), and write uint8 y, which may start at any
+ * byte; call them behind pl_plan_run, on the plan's context.  Asynchronous on ctx's stream; nothing is allocated or uploaded.
+ *
+ * pl_image_f32_u8: y is (N, H, W, Co) if nhwc else (N, Co, H, W), Co in 1..4 (else PL_EUNSUPPORTED), C >= 1.  Output channel c
+ * reads source plane order[c] (host array of Co ints, each in [0, C); NULL: identity, and then Co == C).  k and b are host
+ * arrays of Co floats and travel, with order, as kernel arguments.  Per sample, every operation rounded on its own:
+ * t = fl(fl(v * k[c]) + b[c]); a NaN t becomes 0; t is clamped to [0, 255]; then rounded to nearest, ties to even (trunc == 0) or
+ * truncated toward zero (trunc != 0); the byte is stored.  In numpy: np.where(np.isnan(t), 0, np.clip(t, 0, 255)), then
+ * np.rint(..).astype(uint8) or .astype(uint8), bit for bit.
+ *
+ * pl_labels_f32_u8: y is (N, H, W).  2 <= C <= 256: y = np.argmax(x, axis=1) exactly (the first index among equal maxima, so
+ * -0.0 and +0.0 tie; a NaN counts as the maximum, the first NaN wins; all -inf gives 0); threshold is ignored.  C == 1:
+ * y = x > (float)threshold, a NaN gives 0.  C > 256: PL_EUNSUPPORTED.
+ *
+ * Limit: fewer than 2^31 source floats and fewer than 2^31 output bytes, else PL_EUNSUPPORTED.  N H W == 0: PL_OK, no launch.
+ * Every refusal comes before any launch and leaves y untouched.  Nothing outside x's N C H W floats is read, nothing outside
+ * y's bytes written; no atomics.
+ * A workgroup takes PL_IMAGE_OUT_TILE_PIXELS consecutive pixels of one image's flat H W plane, a lane PL_IMAGE_OUT_LANE_PIXELS
+ * of them: one 16-byte load per source plane where x is 16-byte aligned and H W % 4 == 0 (single floats otherwise); planar and
+ * label bytes as one 32-bit store where their address is 4-byte aligned (single bytes otherwise); an interleaved tile as one run
+ * of aligned 16-byte stores between single bytes in front of the first and behind the last 16-byte boundary. */
+#define PL_IMAGE_OUT_TILE_PIXELS 1024
+#define PL_IMAGE_OUT_LANE_PIXELS 4
+int pl_image_f32_u8(pl_ctx *ctx, const float *x, unsigned char *y, int N, int C, int H, int W, int Co, const int *order,
+                    int nhwc, const float *k, const float *b, int trunc);
+int pl_labels_f32_u8(pl_ctx *ctx, const float *x, unsigned char *y, int N, int C, int H, int W, double threshold);
 /* split-K combine + epilogue (internal to conv, exported for tests) */
 int pl_splitk_reduce_f32(pl_ctx *ctx, const float *ws, int splits, float *y,
                          int N, int C, int inner, const float *bias,

@@ -9,6 +9,7 @@
 #include "groupnorm_q4_kernel.h"
 #include "pixel_shuffle_q4_kernel.h"
 #include "image_input_kernel.h"
+#include "image_output_kernel.h"
 
 namespace {
 
@@ -924,6 +925,56 @@ int pl_image_u8_nchw_f32(pl_ctx *ctx, const unsigned char *x, float *y, int N, i
         if (nhwc) ii::image_u8_flat_kernel<true><<<(unsigned)N * tiles, TPB, 0, ctx->stream>>>(x, y, HWo, C, Co, tiles, af, vec);
         else ii::image_u8_flat_kernel<false><<<(unsigned)N * Co * tiles, TPB, 0, ctx->stream>>>(x, y, HWo, C, Co, tiles, af, vec);
     }
+    PL_LAUNCH_CHECK();
+    return PL_OK;
+}
+
+// float32 NCHW -> uint8 images and label maps (image_output_kernel.h).  Every refusal comes before any launch.
+namespace {
+// whether n * c * hw (each below 2^31, so no product of two wraps) stays below 2^31
+inline bool below_2_31(size_t n, size_t c, size_t hw) { return n * c < (1ull << 31) && n * c * hw < (1ull << 31); }
+}  // namespace
+
+int pl_image_f32_u8(pl_ctx *ctx, const float *x, unsigned char *y, int N, int C, int H, int W, int Co, const int *order, int nhwc,
+                    const float *k, const float *b, int trunc) {
+    namespace io = image_output;
+    PL_REQUIRE(ctx && x && y && k && b, PL_EINVAL, "pl_image_f32_u8: null argument");
+    PL_REQUIRE(N >= 0 && C >= 1 && H >= 0 && W >= 0, PL_EINVAL, "pl_image_f32_u8: bad shape (%d, %d, %d, %d)", N, C, H, W);
+    PL_REQUIRE(Co >= 1 && Co <= io::MAX_CO, PL_EUNSUPPORTED, "pl_image_f32_u8: 1 to 4 output channels, got Co = %d", Co);
+    PL_REQUIRE(order || Co == C, PL_EINVAL, "pl_image_f32_u8: no channel order given and Co = %d != C = %d", Co, C);
+    io::Affine af;
+    for (int c = 0; c < io::MAX_CO; ++c) {
+        af.k[c] = c < Co ? k[c] : 0.f;
+        af.b[c] = c < Co ? b[c] : 0.f;
+        af.order[c] = c < Co ? (order ? order[c] : c) : 0;
+        PL_REQUIRE(af.order[c] >= 0 && af.order[c] < C, PL_EINVAL, "pl_image_f32_u8: order[%d] = %d is no source plane", c,
+                   af.order[c]);
+    }
+    const size_t HW = (size_t)H * W;
+    PL_REQUIRE(HW < (1ull << 31) && below_2_31(N, C, HW) && below_2_31(N, Co, HW), PL_EUNSUPPORTED,
+               "pl_image_f32_u8: 2^31 or more source floats or output bytes");
+    if (N == 0 || HW == 0) return PL_OK;
+    CtxGuard g(ctx);
+    const unsigned tiles = cdiv(HW, io::TILE_PX);
+    const bool vec = aligned16(x) && HW % 4 == 0;
+    if (nhwc) io::image_f32_u8_kernel<true><<<(unsigned)N * tiles, TPB, 0, ctx->stream>>>(x, y, HW, C, Co, tiles, af, vec, trunc != 0);
+    else io::image_f32_u8_kernel<false><<<(unsigned)N * tiles, TPB, 0, ctx->stream>>>(x, y, HW, C, Co, tiles, af, vec, trunc != 0);
+    PL_LAUNCH_CHECK();
+    return PL_OK;
+}
+
+int pl_labels_f32_u8(pl_ctx *ctx, const float *x, unsigned char *y, int N, int C, int H, int W, double threshold) {
+    namespace io = image_output;
+    PL_REQUIRE(ctx && x && y, PL_EINVAL, "pl_labels_f32_u8: null argument");
+    PL_REQUIRE(N >= 0 && C >= 1 && H >= 0 && W >= 0, PL_EINVAL, "pl_labels_f32_u8: bad shape (%d, %d, %d, %d)", N, C, H, W);
+    PL_REQUIRE(C <= io::MAX_LABELS, PL_EUNSUPPORTED, "pl_labels_f32_u8: at most 256 planes fit a byte, got C = %d", C);
+    const size_t HW = (size_t)H * W;
+    PL_REQUIRE(HW < (1ull << 31) && below_2_31(N, C, HW), PL_EUNSUPPORTED, "pl_labels_f32_u8: 2^31 or more source floats");
+    if (N == 0 || HW == 0) return PL_OK;
+    CtxGuard g(ctx);
+    const unsigned tiles = cdiv(HW, io::TILE_PX);
+    io::labels_f32_u8_kernel<<<(unsigned)N * tiles, TPB, 0, ctx->stream>>>(x, y, HW, C, tiles, (float)threshold,
+                                                                          aligned16(x) && HW % 4 == 0);
     PL_LAUNCH_CHECK();
     return PL_OK;
 }

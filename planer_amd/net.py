@@ -30,7 +30,7 @@ from . import q4 as _q4
 from .conv_layouts import DIRECT_Q4, IGEMM_NCHW, LAYOUTS, STEM_POOL, STEM_POOL_NCHW, WINO4_Q4, WINO43_Q4, experiment, suffix
 from .layer import layer_map, wrap
 from .plan import compile_front, fuse_upsample_concat, lower
-from .util import ImageFeed, ImageSpec
+from .util import ImageFeed, ImageOutSpec, ImageSpec, LabelSpec
 
 STEM_WINO_DEFAULT = 1      # whether the stem + max-pool step takes the F(4,4) form where it applies
 
@@ -366,6 +366,7 @@ class Net:
         self.algo_misses = 0         # conv algorithm picks that had to be measured (no cached choice)
         self.stream_misses = 0       # stream-plan picks that had to be measured
         self._image_in = {}          # input key (None: the first input) -> util.ImageSpec: uint8 batches that input also takes
+        self._image_out = {}         # output position -> util.ImageOutSpec / util.LabelSpec: that output comes back as uint8
 
     # ---- loading ----------------------------------------------------------------
     def load_json(self, inputs, inits, body, flow, debug=False):
@@ -427,6 +428,53 @@ class Net:
         self._plans = {s: p for s, p in self._plans.items() if not u8(s[1:])}
         self._eager_prog = {s: p for s, p in self._eager_prog.items() if not u8(s)}
         return self
+
+    def image_output(self, k, b, layout="nhwc", order=None, rounding="nearest", index=0):
+        """Output number `index` (its position in what the net returns), a float32 (N, C, H, W) tensor, comes back as uint8
+        images, (N, H, W, Co) for layout "nhwc" or (N, Co, H, W) for "nchw": the byte of fl(fl(v * k[c]) + b[c]) (k, b per channel
+        from util.image_affine_inverse), v taken from plane order[c]; NaN -> 0, clamped to [0, 255], rounded to nearest even or
+        truncated ("truncate": what astype(uint8) does).  One kernel (pl_image_f32_u8) behind the pass, in place of the private
+        copy of that output: plans are not touched.  A later declaration for the same index replaces this one."""
+        self._image_out[self._out_index(index)] = ImageOutSpec(k, b, layout, order, rounding)
+        return self
+
+    def label_output(self, threshold=0.0, index=0):
+        """Output number `index`, float32 (N, C, H, W) scores, comes back as the uint8 label map (N, H, W): numpy's argmax over
+        the C planes (2 to 256), for C == 1 the comparison x > threshold (pl_labels_f32_u8).  See `image_output`."""
+        self._image_out[self._out_index(index)] = LabelSpec(threshold)
+        return self
+
+    def float_output(self, index=0):
+        """Output number `index` comes back as the float32 tensor again."""
+        self._image_out.pop(self._out_index(index), None)
+        return self
+
+    @staticmethod
+    def _out_index(index):
+        if not isinstance(index, (int, numpy.integer)) or index < 0:
+            raise ValueError("output index is a position in what the net returns (0, 1, ...), got %r" % (index,))
+        return int(index)
+
+    def _check_outputs(self, out):
+        """ValueError unless every declared output is a 4-d float32 device tensor its encoder takes."""
+        seq = out if isinstance(out, tuple) else (out,)
+        for i, spec in self._image_out.items():
+            if i >= len(seq):
+                raise ValueError("output %d is declared uint8, the net returns %d output(s)" % (i, len(seq)))
+            if not isinstance(seq[i], DeviceArray):
+                raise ValueError("output %d is declared uint8 and is no device tensor: %s" % (i, type(seq[i]).__name__))
+            spec.check(seq[i])
+
+    def _hand_back(self, out, private):
+        """What a pass hands to the caller: a declared output encoded into a fresh uint8 array on the stream that owns it, the
+        others as private copies (`private`: the plan's buffers are rewritten by the next pass) or as they are."""
+        if not self._image_out and not private:
+            return out
+        self._check_outputs(out)
+        seq = out if isinstance(out, tuple) else (out,)
+        rst = tuple(self._image_out[i].encode(o) if i in self._image_out else
+                    o.copy() if private and isinstance(o, DeviceArray) else o for i, o in enumerate(seq))
+        return rst if isinstance(out, tuple) else rst[0]
 
     def _image_spec(self, pos):
         name = self.input[pos] if pos < len(self.input) else None
@@ -1177,6 +1225,8 @@ class Net:
 
     def _replay(self, xs, private=True):
         plan = self.compile(*xs)
+        if self._image_out:
+            self._check_outputs(plan.outputs)          # (before anything is launched)
         if isinstance(plan, _PipelinePlan):
             # the replica whose turn it is gets the inputs (plan.inputs are those of the replica launched LAST);
             # its stream first waits for the main stream, where the caller produced xs
@@ -1185,13 +1235,9 @@ class Net:
         else:
             self._feed_on_main(plan, xs)
         plan.launch()
-        out = plan.outputs
-        if not private:                            # the caller copies to the host right away
-            return out
-        # hand back private copies: the plan's buffers are rewritten by the next replay
-        if isinstance(out, tuple):
-            return tuple(o.copy() if isinstance(o, DeviceArray) else o for o in out)
-        return out.copy() if isinstance(out, DeviceArray) else out
+        # private copies (the plan's buffers are rewritten by the next replay) unless the caller copies to the host right away;
+        # a declared uint8 output is encoded into a fresh array either way
+        return self._hand_back(plan.outputs, private)
 
     def _feed_on_main(self, plan, xs):
         """Inputs of a one-graph or sub-batch plan, copied on the net's OWN stream (where the caller produced them);
@@ -1262,6 +1308,8 @@ class Net:
                     self.use_graph = False
         if plan is None:                              # flows that need the host between kernels: run now, hand back a finished handle
             return Pending(self, self(*x), None, any(host), final=True)
+        if self._image_out:
+            self._check_outputs(plan.outputs)         # (before anything is launched)
         if isinstance(plan, _PipelinePlan):
             rp = plan.replicas[plan.turn]
             if not (direct and all(host)):
@@ -1279,8 +1327,8 @@ class Net:
             self._feed_on_main(plan, xs)
             plan.launch()
             cx, out = self.ctx, plan.outputs
-        # private copies on the replica's stream, then the marker result() waits for
-        outs = tuple(o.copy() if isinstance(o, DeviceArray) else o for o in out) if isinstance(out, tuple) else out.copy()
+        # private copies (declared uint8 outputs: encoded) on the replica's stream, then the marker result() waits for
+        outs = self._hand_back(out, True)
         ev = self._events.pop() if self._events else hip.Event(cx)      # a marker can be recorded on any stream of its device
         _lib.call("pl_event_record", cx.handle, ev.handle)
         tickets = None
@@ -1330,6 +1378,8 @@ class Net:
                 rst = self._interpret(self._eager_program(list(x)), list(x))
             else:
                 rst = self.forward(*x, **key)
+            if self._image_out:
+                rst = self._hand_back(rst, False)
         if need:
             rst = tuple(i.get() for i in rst) if isinstance(rst, tuple) else rst.get()
         return rst[0] if len(rst) == 1 else rst

@@ -169,6 +169,125 @@ def decode_images(x, k, b, layout="nhwc", size=None, order=None):
     return ImageFeed(ImageSpec(k, b, layout, size, order), x).materialise()
 
 
+# ---- uint8 images and label maps as net output -------------------------------------------------------------
+def image_affine_inverse(mean, std, scale=255.0):
+    """(k, b) that undo `image_affine`: (x * std + mean) * scale as one multiply and one add per element, k = scale * std,
+    b = scale * mean, evaluated in float64 and rounded once to float32."""
+    mean = numpy.atleast_1d(numpy.asarray(mean, numpy.float64))
+    std = numpy.atleast_1d(numpy.asarray(std, numpy.float64))
+    mean, std = numpy.broadcast_arrays(mean, std)
+    return (float(scale) * std).astype(numpy.float32), (float(scale) * mean).astype(numpy.float32)
+
+
+def _f32_nchw(what, x):
+    """(N, C, H, W) of a 4-d float32 DeviceArray, or an error that names what `x` is."""
+    if not isinstance(x, DeviceArray):
+        raise TypeError("%s: expected a float32 DeviceArray (N, C, H, W), got %s" % (what, type(x).__name__))
+    if x.dtype != numpy.float32 or x.ndim != 4:
+        raise ValueError("%s: expected a float32 tensor (N, C, H, W), got %s of shape %s" % (what, x.dtype, tuple(x.shape)))
+    return x.shape
+
+
+class ImageOutSpec:
+    """How a float32 NCHW result becomes a uint8 image batch: channel c is the byte of fl(fl(v * k[c]) + b[c]), v the sample of
+    source plane order[c]; NaN -> 0, clamped to [0, 255], then rounded to nearest even ("nearest") or truncated ("truncate", what
+    `astype(uint8)` does).  One value in k and b serves every output channel.  Host values only."""
+
+    def __init__(self, k, b, layout="nhwc", order=None, rounding="nearest"):
+        k, b = numpy.atleast_1d(numpy.asarray(k)), numpy.atleast_1d(numpy.asarray(b))
+        if layout not in ("nhwc", "nchw"):
+            raise ValueError("image output: layout is 'nhwc' or 'nchw', got %r" % (layout,))
+        if rounding not in ("nearest", "truncate"):
+            raise ValueError("image output: rounding is 'nearest' or 'truncate', got %r" % (rounding,))
+        if k.ndim != 1 or k.shape != b.shape or not 1 <= k.size <= 4:
+            raise ValueError("image output: k and b hold one value per output channel (1 to 4), got shapes %s and %s" % (k.shape, b.shape))
+        if order is not None:
+            order = tuple(int(c) for c in order)
+            if not 1 <= len(order) <= 4 or min(order) < 0 or k.size not in (1, len(order)):
+                raise ValueError("image output: order names one source plane (>= 0) per output channel (1 to 4, as many as k "
+                                 "holds unless that is one), got %r" % (order,))
+        self.k, self.b = k.astype(numpy.float32), b.astype(numpy.float32)
+        self.layout, self.order, self.rounding = layout, order, rounding
+        # output channels: the order's, else k's; one value in k and no order: as many as the tensor has, known at encode time
+        self.channels = len(order) if order is not None else (int(k.size) if k.size > 1 else None)
+        self._order = (_lib.c_int * len(order))(*order) if order is not None else None
+        self._kb = {}                # output channels -> (k, b) as ctypes arrays, kept alive here
+
+    def _affine(self, co):
+        if co not in self._kb:
+            k, b = numpy.broadcast_to(self.k, (co,)), numpy.broadcast_to(self.b, (co,))
+            self._kb[co] = (_lib.c_float * co)(*k.tolist()), (_lib.c_float * co)(*b.tolist())
+        return self._kb[co]
+
+    def geometry(self, shape):
+        """(N, C, H, W, Co) for a float32 result of `shape`, or a ValueError that names what does not fit."""
+        n, c, h, w = shape
+        co = self.channels or c
+        if not 1 <= co <= 4:
+            raise ValueError("image output: 1 to 4 output channels, got %d from shape %s" % (co, tuple(shape)))
+        if self.order is None and co != c:
+            raise ValueError("image output: %d values in k for %d channels and no order" % (co, c))
+        if self.order is not None and max(self.order) >= c:
+            raise ValueError("image output: order %r names a plane the %d-channel tensor does not have" % (self.order, c))
+        return n, c, h, w, co
+
+    def check(self, x):
+        self.geometry(_f32_nchw("image output", x))
+
+    def encode(self, x, ctx=None):
+        """The uint8 DeviceArray of float32 (N, C, H, W) `x`, (N, H, W, Co) or (N, Co, H, W) (pl_image_f32_u8), a fresh array;
+        asynchronous on `ctx`'s stream (default: x's)."""
+        n, c, h, w, co = self.geometry(_f32_nchw("image output", x))
+        ctx = ctx or x.ctx
+        y = hip.empty((n, h, w, co) if self.layout == "nhwc" else (n, co, h, w), numpy.uint8, ctx=ctx)
+        k, b = self._affine(co)
+        _lib.call("pl_image_f32_u8", ctx.handle, x.ptr, y.ptr, n, c, h, w, co, self._order, int(self.layout == "nhwc"), k, b,
+                  int(self.rounding == "truncate"))
+        return y
+
+
+class LabelSpec:
+    """A float32 (N, C, H, W) result as the uint8 label map (N, H, W): numpy's argmax over the C planes (2 to 256), for C == 1
+    the comparison x > threshold.  Host values only."""
+
+    def __init__(self, threshold=0.0):
+        t = float(numpy.float32(threshold))
+        if t != t:
+            raise ValueError("label output: threshold is a number, got %r" % (threshold,))
+        self.threshold = t
+
+    def geometry(self, shape):
+        n, c, h, w = shape
+        if not 1 <= c <= 256:
+            raise ValueError("label output: 1 to 256 planes fit a byte, got %d in shape %s" % (c, tuple(shape)))
+        return n, c, h, w
+
+    def check(self, x):
+        self.geometry(_f32_nchw("label output", x))
+
+    def encode(self, x, ctx=None):
+        """The uint8 (N, H, W) DeviceArray of float32 (N, C, H, W) `x` (pl_labels_f32_u8), a fresh array; asynchronous on `ctx`'s
+        stream (default: x's)."""
+        n, c, h, w = self.geometry(_f32_nchw("label output", x))
+        ctx = ctx or x.ctx
+        y = hip.empty((n, h, w), numpy.uint8, ctx=ctx)
+        _lib.call("pl_labels_f32_u8", ctx.handle, x.ptr, y.ptr, n, c, h, w, self.threshold)
+        return y
+
+
+def encode_images(x, k, b, layout="nhwc", order=None, rounding="nearest"):
+    """A float32 (N, C, H, W) DeviceArray as the uint8 image batch, (N, H, W, Co) or (N, Co, H, W): the byte of
+    fl(fl(v * k[c]) + b[c]), NaN -> 0, clamped to [0, 255], rounded to nearest even or truncated (pl_image_f32_u8); v is the sample
+    of source plane order[c] (default: c).  (k, b) from `image_affine_inverse`.  Asynchronous on x's stream."""
+    return ImageOutSpec(k, b, layout, order, rounding).encode(x)
+
+
+def label_map(x, threshold=0.0):
+    """A float32 (N, C, H, W) DeviceArray as the uint8 label map (N, H, W): numpy's argmax over axis 1, or x > threshold where
+    C == 1 (pl_labels_f32_u8).  Asynchronous on x's stream."""
+    return LabelSpec(threshold).encode(x)
+
+
 def _window(img, rc):
     """img[rows, cols] as a contiguous device array."""
     r, c = rc
