@@ -681,6 +681,43 @@ int pl_image_u8_nchw_f32(pl_ctx *ctx, const unsigned char *x, float *y, int N, i
 int pl_image_f32_u8(pl_ctx *ctx, const float *x, unsigned char *y, int N, int C, int H, int W, int Co, const int *order,
                     int nhwc, const float *k, const float *b, int trunc);
 int pl_labels_f32_u8(pl_ctx *ctx, const float *x, unsigned char *y, int N, int C, int H, int W, double threshold);
+/* ---- detections as net output ----
+ * YOLO-style heads -> rows [x1, y1, x2, y2, score, class]: pl_yolo_decode_f32 once per head, pl_topk_f32 over the scores,
+ * pl_nms_f32.  Call them behind pl_plan_run, on the plan's context.  Asynchronous on ctx's stream; nothing is allocated or
+ * uploaded, nothing synchronises, no atomics.
+ *
+ * pl_yolo_decode_f32: x is one head, float32 (N, A (5 + C), Gh, Gw); anchors is a host array of 2 A floats (aw, ah per anchor, in
+ * input pixels) and travels as kernel arguments, A <= PL_YOLO_MAX_ANCHORS.  An image's anchors of all heads form a row of `row`
+ * entries; this head's start at `offset`, anchor a of cell (gy, gx) has index i = offset + (a Gh + gy) Gw + gx and is stored
+ * at position row - 1 - i of the image's row, back to front: pl_topk_f32 (largest = 1) orders equal values by descending
+ * position, so its result is by (score descending, anchor index ascending).  With
+ * t[j] = x[n, a (5 + C) + j, gy, gx] and s(v) = 1 / (1 + exp(-v)) (pl_sigmoid_f32's):
+ *   class = argmax of t[5 : 5 + C] with pl_labels_f32_u8's rule (the first of equal maxima, the first NaN before any number),
+ *   score = fl(s(t4) * s(t[5 + class])); the anchor is a candidate iff score > (float)conf (a NaN score is none),
+ *   cx = fl(fl(s(t0) + gx) * (float)sx), cy likewise with gy and sy, w = fl(exp(t2) * aw), h = fl(exp(t3) * ah),
+ *   box = (cx - w/2, cy - h/2, cx + w/2, cy + h/2), not clipped; every operation rounded on its own.
+ * A candidate writes scores (N, row), classes (N, row) int32 and boxes (N, row, 4); any other anchor writes score -1 and leaves
+ * its class and box untouched.  One lane per cell of one anchor; the class planes are read only where s(t4) > conf.
+ *
+ * pl_nms_f32: greedy non-maximum suppression of each image's K entries (sorted_scores (N, K) descending and order (N, K) int64,
+ * rows of boxes (N, R, 4) / classes (N, R) int32, as pl_topk_f32 returns them; classes NULL: one class).  Entry j is a candidate
+ * iff its score > (float)floor and 0 <= order < R.  In order, a candidate is dropped when a candidate kept earlier (class_aware:
+ * of the same class) overlaps it: in float32, every operation rounded on its own, fmin / fmax as np.fmin / np.fmax,
+ *   iw = fmax(0, fmin(x2i, x2j) - fmax(x1i, x1j)), ih likewise, inter = iw ih, area = (x2 - x1) (y2 - y1),
+ *   union = (area_i + area_j) - inter, dropped iff inter > (float)iou * union
+ * (no division: a zero union or a NaN drops nothing); it stops after max_det kept.  det (N, max_det, 6) gets the kept rows
+ * [x1, y1, x2, y2, score, class] and +0.0 in the rows behind them, num (N) int32 their count: both are written completely.
+ * One workgroup per image, 24 K + 16 ceil(K / 64) bytes of dynamic LDS, one barrier per kept box.
+ *
+ * PL_EINVAL: a null pointer (classes of pl_nms_f32 excepted), a negative dimension, C < 1, offset < 0 or offset + A Gh Gw > row,
+ * K > R.  PL_EUNSUPPORTED: A > PL_YOLO_MAX_ANCHORS, K > PL_NMS_MAX_CANDIDATES, max_det > K, 2^31 or more floats in a tensor.
+ * N == 0 (decode: or A Gh Gw == 0): PL_OK, no launch.  Every refusal comes before any launch and leaves the outputs untouched. */
+#define PL_YOLO_MAX_ANCHORS 8
+#define PL_NMS_MAX_CANDIDATES 4096
+int pl_yolo_decode_f32(pl_ctx *ctx, const float *x, int N, int A, int C, int Gh, int Gw, const float *anchors, double sx,
+                       double sy, double conf, int row, int offset, float *scores, int *classes, float *boxes);
+int pl_nms_f32(pl_ctx *ctx, const float *boxes, const int *classes, const float *sorted_scores, const long long *order, int N,
+               int R, int K, double floor, double iou, int class_aware, int max_det, float *det, int *num);
 /* split-K combine + epilogue (internal to conv, exported for tests) */
 int pl_splitk_reduce_f32(pl_ctx *ctx, const float *ws, int splits, float *y,
                          int N, int C, int inner, const float *bias,

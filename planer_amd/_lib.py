@@ -20,6 +20,8 @@ IMAGE_U8_TILE_PIXELS = 1024         # include/planer_hip.h PL_IMAGE_U8_TILE_PIXE
 IMAGE_U8_LANE_PIXELS = 4            # include/planer_hip.h PL_IMAGE_U8_LANE_PIXELS
 IMAGE_OUT_TILE_PIXELS = 1024        # include/planer_hip.h PL_IMAGE_OUT_TILE_PIXELS
 IMAGE_OUT_LANE_PIXELS = 4           # include/planer_hip.h PL_IMAGE_OUT_LANE_PIXELS
+YOLO_MAX_ANCHORS = 8                # include/planer_hip.h PL_YOLO_MAX_ANCHORS
+NMS_MAX_CANDIDATES = 4096           # include/planer_hip.h PL_NMS_MAX_CANDIDATES
 ACT_NONE, ACT_RELU, ACT_LEAKY = 0, 1, 2
 ACT_RES_AFTER = 16
 UNIQUE_ID_BYTES = 128
@@ -193,6 +195,8 @@ SIGNATURES = {
     "pl_image_u8_nchw_f32": [_P, _P, _P, _I, _I, _I, _I, _I, _I, POINTER(c_int), _I, _I, _P, _P, _P, _P, POINTER(c_float), POINTER(c_float)],
     "pl_image_f32_u8": [_P, _P, _P, _I, _I, _I, _I, _I, POINTER(c_int), _I, POINTER(c_float), POINTER(c_float), _I],
     "pl_labels_f32_u8": [_P, _P, _P, _I, _I, _I, _I, c_double],
+    "pl_yolo_decode_f32": [_P, _P, _I, _I, _I, _I, _I, POINTER(c_float), c_double, c_double, c_double, _I, _I, _P, _P, _P],
+    "pl_nms_f32": [_P, _P, _P, _P, _P, _I, _I, _I, c_double, c_double, _I, _I, _P, _P],
     "pl_tile_accumulate_f32": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I],
     "pl_tile_normalise_f32": [_P, _P, _P, _I, _I, _I],
     "pl_splitk_reduce_f32": [_P, _P, _I, _P, _I, _I, _I, _P, _P, _P, _P, _I, c_double],

@@ -10,6 +10,7 @@
 #include "pixel_shuffle_q4_kernel.h"
 #include "image_input_kernel.h"
 #include "image_output_kernel.h"
+#include "detect_kernel.h"
 
 namespace {
 
@@ -975,6 +976,56 @@ int pl_labels_f32_u8(pl_ctx *ctx, const float *x, unsigned char *y, int N, int C
     const unsigned tiles = cdiv(HW, io::TILE_PX);
     io::labels_f32_u8_kernel<<<(unsigned)N * tiles, TPB, 0, ctx->stream>>>(x, y, HW, C, tiles, (float)threshold,
                                                                           aligned16(x) && HW % 4 == 0);
+    PL_LAUNCH_CHECK();
+    return PL_OK;
+}
+
+// YOLO heads -> detections (detect_kernel.h).  Every refusal comes before any launch.
+int pl_yolo_decode_f32(pl_ctx *ctx, const float *x, int N, int A, int C, int Gh, int Gw, const float *anchors, double sx, double sy,
+                       double conf, int row, int offset, float *scores, int *classes, float *boxes) {
+    namespace dt = detect;
+    PL_REQUIRE(ctx && x && anchors && scores && classes && boxes, PL_EINVAL, "pl_yolo_decode_f32: null argument");
+    PL_REQUIRE(N >= 0 && A >= 0 && Gh >= 0 && Gw >= 0 && row >= 0, PL_EINVAL, "pl_yolo_decode_f32: bad shape (%d, %d x (5 + %d), %d, %d), row %d",
+               N, A, C, Gh, Gw, row);
+    PL_REQUIRE(C >= 1, PL_EINVAL, "pl_yolo_decode_f32: at least one class, got C = %d", C);
+    const size_t HW = (size_t)Gh * Gw;
+    PL_REQUIRE(offset >= 0 && HW < (1ull << 31) && (size_t)A * HW <= (size_t)row && (size_t)offset <= (size_t)row - (size_t)A * HW,
+               PL_EINVAL, "pl_yolo_decode_f32: %d x %d x %d anchors at offset %d do not fit a row of %d", A, Gh, Gw, offset, row);
+    PL_REQUIRE(A <= dt::MAX_ANCHORS, PL_EUNSUPPORTED, "pl_yolo_decode_f32: at most %d anchors per head, got A = %d", dt::MAX_ANCHORS, A);
+    const size_t planes = (size_t)A * (5 + (size_t)C);      // (A <= 8: below 2^35)
+    PL_REQUIRE(planes < (1ull << 31) && below_2_31(N, planes, HW) && below_2_31(N, 4, row), PL_EUNSUPPORTED,
+               "pl_yolo_decode_f32: 2^31 or more floats in a tensor");
+    if (N == 0 || A == 0 || HW == 0) return PL_OK;
+    dt::Anchors an;
+    for (int a = 0; a < dt::MAX_ANCHORS; ++a) {
+        an.w[a] = a < A ? anchors[2 * a] : 0.f;
+        an.h[a] = a < A ? anchors[2 * a + 1] : 0.f;
+    }
+    CtxGuard g(ctx);
+    const unsigned tiles = cdiv(HW, dt::TPB);
+    dt::decode_kernel<<<(unsigned)N * (unsigned)A * tiles, dt::TPB, 0, ctx->stream>>>(x, scores, classes, boxes, A, C, Gw, HW, tiles, an, (float)sx,
+                                                                                      (float)sy, (float)conf, (size_t)row, (size_t)offset);
+    PL_LAUNCH_CHECK();
+    return PL_OK;
+}
+
+int pl_nms_f32(pl_ctx *ctx, const float *boxes, const int *classes, const float *sorted_scores, const long long *order, int N, int R,
+               int K, double floor, double iou, int class_aware, int max_det, float *det, int *num) {
+    namespace dt = detect;
+    PL_REQUIRE(ctx && boxes && sorted_scores && order && det && num, PL_EINVAL, "pl_nms_f32: null argument");
+    PL_REQUIRE(N >= 0 && R >= 0 && K >= 0 && max_det >= 0, PL_EINVAL, "pl_nms_f32: bad shape N = %d, R = %d, K = %d, max_det = %d", N, R, K,
+               max_det);
+    PL_REQUIRE(K <= R, PL_EINVAL, "pl_nms_f32: K = %d entries of %d rows", K, R);
+    PL_REQUIRE(K <= dt::NMS_MAX_K, PL_EUNSUPPORTED, "pl_nms_f32: at most %d entries per image, got K = %d", dt::NMS_MAX_K, K);
+    PL_REQUIRE(max_det <= K, PL_EUNSUPPORTED, "pl_nms_f32: max_det = %d exceeds K = %d", max_det, K);
+    PL_REQUIRE(below_2_31(N, 4, R) && below_2_31(N, 6, max_det), PL_EUNSUPPORTED, "pl_nms_f32: 2^31 or more floats in a tensor");
+    if (N == 0) return PL_OK;
+    CtxGuard g(ctx);
+    const size_t lds = dt::nms_lds_bytes(K);
+    if (lds > 48 * 1024)
+        PL_HIP(hipFuncSetAttribute((const void *)dt::nms_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    dt::nms_kernel<<<(unsigned)N, dt::TPB, lds, ctx->stream>>>(boxes, classes, sorted_scores, order, R, K, (float)floor, (float)iou,
+                                                               class_aware != 0, max_det, det, num);
     PL_LAUNCH_CHECK();
     return PL_OK;
 }

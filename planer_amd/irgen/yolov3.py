@@ -12,7 +12,8 @@ from .builder import GraphBuilder
 
 
 class _Gen:
-    def __init__(self, seed):
+    def __init__(self, seed, head_gain=1.0):
+        self.head_gain = head_gain
         self.rng = np.random.default_rng(seed)
         self.g = GraphBuilder(["x"])
         self.n = 0
@@ -40,8 +41,8 @@ class _Gen:
     def head(self, src, cin, tag, classes_ch=255):
         rng, g = self.rng, self.g
         w = rng.standard_normal((classes_ch, cin, 1, 1)) * np.sqrt(1.0 / cin)
-        g.init(tag + "_w", w.astype(np.float32))
-        g.init(tag + "_bias", (rng.standard_normal(classes_ch) * 0.1).astype(np.float32))
+        g.init(tag + "_w", (w * self.head_gain).astype(np.float32))
+        g.init(tag + "_bias", (rng.standard_normal(classes_ch) * 0.1 * self.head_gain).astype(np.float32))
         return g.op("conv", [src, tag + "_w", tag + "_bias"], tag, name=tag + "_conv",
                     group=1, strides=[1, 1], dilations=[1, 1], pads=[0, 0, 0, 0])
 
@@ -52,8 +53,10 @@ class _Gen:
         return self.g.op("add", [src, y], t, name=t + "_add")
 
 
-def build(seed=0):
-    m = _Gen(seed)
+def build(seed=0, head_gain=1.0):
+    """head_gain scales the three heads' filters and biases: the random weights give logits in the hundreds, where every
+    sigmoid is 0 or 1; a gain around 1/400 gives the spread of scores a detection post-processing needs to be measured on."""
+    m = _Gen(seed, head_gain)
     g = m.g
     g.init("scales", np.array([1, 1, 2, 2], np.float32))
     y = m.cbl("x", 3, 32, 3)

@@ -30,7 +30,7 @@ from . import q4 as _q4
 from .conv_layouts import DIRECT_Q4, IGEMM_NCHW, LAYOUTS, STEM_POOL, STEM_POOL_NCHW, WINO4_Q4, WINO43_Q4, experiment, suffix
 from .layer import layer_map, wrap
 from .plan import compile_front, fuse_upsample_concat, lower
-from .util import ImageFeed, ImageOutSpec, ImageSpec, LabelSpec
+from .util import DetectionSpec, ImageFeed, ImageOutSpec, ImageSpec, LabelSpec
 
 STEM_WINO_DEFAULT = 1      # whether the stem + max-pool step takes the F(4,4) form where it applies
 
@@ -367,6 +367,7 @@ class Net:
         self.stream_misses = 0       # stream-plan picks that had to be measured
         self._image_in = {}          # input key (None: the first input) -> util.ImageSpec: uint8 batches that input also takes
         self._image_out = {}         # output position -> util.ImageOutSpec / util.LabelSpec: that output comes back as uint8
+        self._detect = None          # (util.DetectionSpec, positions of its heads or None: every output): they come back as det, num
 
     # ---- loading ----------------------------------------------------------------
     def load_json(self, inputs, inits, body, flow, debug=False):
@@ -435,19 +436,51 @@ class Net:
         from util.image_affine_inverse), v taken from plane order[c]; NaN -> 0, clamped to [0, 255], rounded to nearest even or
         truncated ("truncate": what astype(uint8) does).  One kernel (pl_image_f32_u8) behind the pass, in place of the private
         copy of that output: plans are not touched.  A later declaration for the same index replaces this one."""
-        self._image_out[self._out_index(index)] = ImageOutSpec(k, b, layout, order, rounding)
+        spec = ImageOutSpec(k, b, layout, order, rounding)
+        self._image_out[self._unclaimed(index)] = spec
         return self
 
     def label_output(self, threshold=0.0, index=0):
         """Output number `index`, float32 (N, C, H, W) scores, comes back as the uint8 label map (N, H, W): numpy's argmax over
         the C planes (2 to 256), for C == 1 the comparison x > threshold (pl_labels_f32_u8).  See `image_output`."""
-        self._image_out[self._out_index(index)] = LabelSpec(threshold)
+        spec = LabelSpec(threshold)
+        self._image_out[self._unclaimed(index)] = spec
         return self
 
     def float_output(self, index=0):
-        """Output number `index` comes back as the float32 tensor again."""
-        self._image_out.pop(self._out_index(index), None)
+        """Output number `index` comes back as the float32 tensor again; if it is a head of a detection declaration, so do all
+        of that declaration's heads."""
+        index = self._out_index(index)
+        self._image_out.pop(index, None)
+        if self._detect is not None and (self._detect[1] is None or index in self._detect[1]):
+            self._detect = None
         return self
+
+    def detection_output(self, heads, classes, conf=0.25, iou=0.45, max_det=100, max_candidates=1024, class_aware=True, size=None,
+                         indices=None):
+        """The outputs at positions `indices` (in head order; default: every output, in order) are YOLO-style heads, float32
+        (N, A (5 + classes), Gh, Gw), head h with anchors and stride heads[h] = (anchors, stride or None).  In their place the
+        net returns det, float32 (N, max_det, 6) rows [x1, y1, x2, y2, score, class] in input pixels by descending score (+0.0
+        in unused rows), and num, int32 (N,), inserted where the lowest of those positions was; the other outputs keep their
+        order.  Decode, top-k and NMS run behind the pass on the stream that owns the outputs (util.DetectionSpec): plans are
+        not touched.  Declaring again replaces the declaration; `float_output` on one of the positions removes it."""
+        spec = DetectionSpec(heads, classes, conf, iou, max_det, max_candidates, class_aware, size)
+        if indices is not None:
+            indices = tuple(self._out_index(i) for i in indices)
+            if len(indices) != len(spec.heads) or len(set(indices)) != len(indices):
+                raise ValueError("detection output: indices names one distinct output position per head (%d), got %r"
+                                 % (len(spec.heads), indices))
+        taken = sorted(self._image_out if indices is None else set(indices) & set(self._image_out))
+        if taken:
+            raise ValueError("detection output: output %d is already declared an image or label output" % taken[0])
+        self._detect = (spec, indices)
+        return self
+
+    def _unclaimed(self, index):
+        index = self._out_index(index)
+        if self._detect is not None and (self._detect[1] is None or index in self._detect[1]):
+            raise ValueError("output %d is a head of the declared detection output" % index)
+        return index
 
     @staticmethod
     def _out_index(index):
@@ -456,7 +489,8 @@ class Net:
         return int(index)
 
     def _check_outputs(self, out):
-        """ValueError unless every declared output is a 4-d float32 device tensor its encoder takes."""
+        """ValueError unless every declared output is a 4-d float32 device tensor its encoder takes.  Returns the positions of
+        the detection heads (None: none declared)."""
         seq = out if isinstance(out, tuple) else (out,)
         for i, spec in self._image_out.items():
             if i >= len(seq):
@@ -464,17 +498,36 @@ class Net:
             if not isinstance(seq[i], DeviceArray):
                 raise ValueError("output %d is declared uint8 and is no device tensor: %s" % (i, type(seq[i]).__name__))
             spec.check(seq[i])
+        if self._detect is None:
+            return None
+        spec, idx = self._detect
+        if idx is None:
+            idx = tuple(range(len(seq)))
+            if len(idx) != len(spec.heads):
+                raise ValueError("detection output: %d heads declared, the net returns %d output(s)" % (len(spec.heads), len(seq)))
+        for i in idx:
+            if i >= len(seq):
+                raise ValueError("output %d is declared a detection head, the net returns %d output(s)" % (i, len(seq)))
+            if not isinstance(seq[i], DeviceArray):
+                raise ValueError("output %d is declared a detection head and is no device tensor: %s" % (i, type(seq[i]).__name__))
+        spec.check([seq[i] for i in idx])
+        return idx
 
     def _hand_back(self, out, private):
         """What a pass hands to the caller: a declared output encoded into a fresh uint8 array on the stream that owns it, the
         others as private copies (`private`: the plan's buffers are rewritten by the next pass) or as they are."""
-        if not self._image_out and not private:
+        if not self._image_out and self._detect is None and not private:
             return out
-        self._check_outputs(out)
+        heads = self._check_outputs(out)
         seq = out if isinstance(out, tuple) else (out,)
-        rst = tuple(self._image_out[i].encode(o) if i in self._image_out else
-                    o.copy() if private and isinstance(o, DeviceArray) else o for i, o in enumerate(seq))
-        return rst if isinstance(out, tuple) else rst[0]
+        rst = [self._image_out[i].encode(o) if i in self._image_out else
+               o.copy() if private and isinstance(o, DeviceArray) and not (heads and i in heads) else o for i, o in enumerate(seq)]
+        if heads is None:
+            return tuple(rst) if isinstance(out, tuple) else rst[0]
+        # det, num where the lowest head was; the heads themselves are not handed back (nor copied)
+        first = min(heads)
+        det_num = self._detect[0].encode([seq[i] for i in heads])
+        return tuple(r for i, o in enumerate(rst) for r in (det_num if i == first else () if i in heads else (o,)))
 
     def _image_spec(self, pos):
         name = self.input[pos] if pos < len(self.input) else None
@@ -1225,7 +1278,7 @@ class Net:
 
     def _replay(self, xs, private=True):
         plan = self.compile(*xs)
-        if self._image_out:
+        if self._image_out or self._detect is not None:
             self._check_outputs(plan.outputs)          # (before anything is launched)
         if isinstance(plan, _PipelinePlan):
             # the replica whose turn it is gets the inputs (plan.inputs are those of the replica launched LAST);
@@ -1308,7 +1361,7 @@ class Net:
                     self.use_graph = False
         if plan is None:                              # flows that need the host between kernels: run now, hand back a finished handle
             return Pending(self, self(*x), None, any(host), final=True)
-        if self._image_out:
+        if self._image_out or self._detect is not None:
             self._check_outputs(plan.outputs)         # (before anything is launched)
         if isinstance(plan, _PipelinePlan):
             rp = plan.replicas[plan.turn]
@@ -1378,7 +1431,7 @@ class Net:
                 rst = self._interpret(self._eager_program(list(x)), list(x))
             else:
                 rst = self.forward(*x, **key)
-            if self._image_out:
+            if self._image_out or self._detect is not None:
                 rst = self._hand_back(rst, False)
         if need:
             rst = tuple(i.get() for i in rst) if isinstance(rst, tuple) else rst.get()

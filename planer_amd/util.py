@@ -288,6 +288,132 @@ def label_map(x, threshold=0.0):
     return LabelSpec(threshold).encode(x)
 
 
+# ---- detections as net output ---------------------------------------------------------------------------------
+def _f32v(v):
+    """`v` rounded to float32, as the Python float the kernels get (their doubles are cast back without loss)."""
+    return float(numpy.float32(v))
+
+
+def _nms_sorted(boxes, classes, scores, n, r, k, floor, iou, class_aware, max_det, ctx):
+    """top-k of scores (N, R) and pl_nms_f32 on the k first of each image: (det (N, max_det, 6), num (N,)), fresh arrays."""
+    vals, idx = hip.empty((n, k), ctx=ctx), hip.empty((n, k), numpy.int64, ctx=ctx)
+    if n and k:
+        _lib.call("pl_topk_f32", ctx.handle, scores.ptr, n, r, 1, k, 1, vals.ptr, idx.ptr)
+    det, num = hip.empty((n, max_det, 6), ctx=ctx), hip.empty((n,), numpy.int32, ctx=ctx)
+    _lib.call("pl_nms_f32", ctx.handle, boxes.ptr, classes.ptr if classes is not None else None, vals.ptr, idx.ptr, n, r, k,
+              floor, iou, int(bool(class_aware)), max_det, det.ptr, num.ptr)
+    return det, num
+
+
+class DetectionSpec:
+    """How YOLO-style head tensors become detections.  heads[h] = (anchors, stride): anchors a sequence of 1 to 8 (aw, ah) pairs
+    in input pixels, stride a number, an (sx, sy) pair or None (then size[1] / Gw, size[0] / Gh from size = (H, W)).  Head h is
+    float32 (N, A_h (5 + classes), Gh, Gw).  An anchor's class is the argmax of its class logits (the first of equal maxima),
+    its score sigmoid(t4) * sigmoid(t[5 + class]); it is a candidate iff score > conf.  The max_candidates (at most 4096) first
+    candidates by (score descending, anchor index ascending) go through greedy NMS (dropped iff inter > iou * union with a kept
+    box, class_aware: of the same class), which stops after max_det.  conf, iou, anchors and strides are rounded to float32, the
+    numbers the kernels compute with.  Host values only."""
+
+    def __init__(self, heads, classes, conf=0.25, iou=0.45, max_det=100, max_candidates=1024, class_aware=True, size=None):
+        self.heads = []
+        for h, head in enumerate(heads):
+            try:
+                anchors, stride = head
+                anchors = numpy.asarray(anchors, numpy.float64).reshape(-1, 2)
+            except (TypeError, ValueError):
+                raise ValueError("detection output: head %d is (anchors, stride or None), anchors (aw, ah) pairs, got %r" % (h, head))
+            if not 1 <= len(anchors) <= _lib.YOLO_MAX_ANCHORS:
+                raise ValueError("detection output: head %d has %d anchors, 1 to %d fit" % (h, len(anchors), _lib.YOLO_MAX_ANCHORS))
+            if stride is not None:
+                stride = tuple(_f32v(s) for s in numpy.broadcast_to(numpy.asarray(stride, numpy.float64), (2,)))
+            self.heads.append((anchors.astype(numpy.float32), stride))
+        if not self.heads:
+            raise ValueError("detection output: no heads given")
+        if not isinstance(classes, (int, numpy.integer)) or classes < 1:
+            raise ValueError("detection output: classes is a count >= 1, got %r" % (classes,))
+        if not isinstance(max_candidates, (int, numpy.integer)) or not 1 <= max_candidates <= _lib.NMS_MAX_CANDIDATES:
+            raise ValueError("detection output: max_candidates is 1 to %d, got %r" % (_lib.NMS_MAX_CANDIDATES, max_candidates))
+        if not isinstance(max_det, (int, numpy.integer)) or max_det < 1:
+            raise ValueError("detection output: max_det is a count >= 1, got %r" % (max_det,))
+        if size is not None:
+            size = tuple(int(s) for s in size)
+            if len(size) != 2 or min(size) < 1:
+                raise ValueError("detection output: size is the input's (H, W), got %r" % (size,))
+        self.classes, self.max_det, self.max_candidates = int(classes), int(max_det), int(max_candidates)
+        self.conf, self.iou, self.class_aware, self.size = _f32v(conf), _f32v(iou), bool(class_aware), size
+        self._anchors = [(_lib.c_float * a.size)(*a.ravel().tolist()) for a, _ in self.heads]       # kept alive here
+
+    def geometry(self, shapes):
+        """(N, [(A, C, Gh, Gw, sx, sy, offset) per head], A_total, k, max_det) for head tensors of `shapes`, k the entries NMS
+        sees and max_det the rows of det (min(self.max_det, k)), or a ValueError that names what does not fit."""
+        shapes = [tuple(s) for s in shapes]
+        if len(shapes) != len(self.heads):
+            raise ValueError("detection output: %d heads declared, %d tensors given" % (len(self.heads), len(shapes)))
+        rows, off = [], 0
+        for h, (shape, (anchors, stride)) in enumerate(zip(shapes, self.heads)):
+            if len(shape) != 4:
+                raise ValueError("detection output: head %d is (N, A (5 + C), Gh, Gw), got shape %s" % (h, shape))
+            n, ch, gh, gw = shape
+            a = len(anchors)
+            if ch != a * (5 + self.classes):
+                raise ValueError("detection output: head %d has %d channels, %d anchors x (5 + %d classes) is %d"
+                                 % (h, ch, a, self.classes, a * (5 + self.classes)))
+            if n != shapes[0][0]:
+                raise ValueError("detection output: head %d has batch size %d, head 0 has %d" % (h, n, shapes[0][0]))
+            if stride is None:
+                if self.size is None or not gh or not gw:
+                    raise ValueError("detection output: head %d has no stride and there is no input size to derive it from" % h)
+                stride = _f32v(self.size[1] / gw), _f32v(self.size[0] / gh)
+            rows.append((a, self.classes, gh, gw, stride[0], stride[1], off))
+            off += a * gh * gw
+        k = min(self.max_candidates, off)
+        return shapes[0][0], rows, off, k, min(self.max_det, k)
+
+    def check(self, xs):
+        self.geometry([_f32_nchw("detection output", x) for x in xs])
+
+    def encode(self, xs, ctx=None):
+        """(det, num) of the head tensors `xs`: det float32 (N, max_det, 6), rows [x1, y1, x2, y2, score, class] by descending
+        score and +0.0 behind them, num int32 (N,); fresh arrays (max_det is at most the number of anchors).  One
+        pl_yolo_decode_f32 per head, pl_topk_f32, pl_nms_f32, asynchronous on `ctx`'s stream (default: the first head's);
+        scores, classes, boxes and the top-k results are scratch from that context's pool."""
+        n, rows, total, k, max_det = self.geometry([_f32_nchw("detection output", x) for x in xs])
+        ctx = ctx or xs[0].ctx
+        scores, boxes = hip.empty((n, total), ctx=ctx), hip.empty((n, total, 4), ctx=ctx)
+        classes = hip.empty((n, total), numpy.int32, ctx=ctx)
+        for x, anchors, (a, c, gh, gw, sx, sy, off) in zip(xs, self._anchors, rows):
+            _lib.call("pl_yolo_decode_f32", ctx.handle, x.ptr, n, a, c, gh, gw, anchors, sx, sy, self.conf, total, off,
+                      scores.ptr, classes.ptr, boxes.ptr)
+        return _nms_sorted(boxes, classes, scores, n, total, k, self.conf, self.iou, self.class_aware, max_det, ctx)
+
+
+def decode_detections(xs, heads, classes, conf=0.25, iou=0.45, max_det=100, max_candidates=1024, class_aware=True, size=None):
+    """(det, num) of YOLO-style head tensors `xs` (float32 DeviceArrays): `DetectionSpec(heads, classes, ...).encode(xs)`."""
+    return DetectionSpec(heads, classes, conf, iou, max_det, max_candidates, class_aware, size).encode(list(xs))
+
+
+def nms(boxes, scores, classes=None, iou=0.45, max_det=100, floor=-math.inf):
+    """Greedy NMS of boxes (N, K0, 4) float32 (x1, y1, x2, y2) with scores (N, K0) float32 and, if given, classes (N, K0) int32
+    (only boxes of one class suppress each other): the min(K0, 4096) first of each image by (score descending, index ascending)
+    with score > floor go through pl_nms_f32.  Returns det (N, min(max_det, K0, 4096), 6) and num (N,) like `DetectionSpec.encode`.
+    Asynchronous on boxes' stream."""
+    for what, a, dt, nd in (("boxes", boxes, numpy.float32, 3), ("scores", scores, numpy.float32, 2), ("classes", classes, numpy.int32, 2)):
+        if a is None and what == "classes":
+            continue
+        if not isinstance(a, DeviceArray):
+            raise TypeError("nms: %s is a %s DeviceArray, got %s" % (what, numpy.dtype(dt).name, type(a).__name__))
+        if a.dtype != dt or a.ndim != nd:
+            raise ValueError("nms: %s is %d-d %s, got %s of shape %s" % (what, nd, numpy.dtype(dt).name, a.dtype, tuple(a.shape)))
+    n, r = scores.shape
+    if boxes.shape != (n, r, 4) or (classes is not None and classes.shape != (n, r)):
+        raise ValueError("nms: boxes (N, K0, 4), scores (N, K0) and classes (N, K0) do not agree: %s, %s, %s"
+                         % (tuple(boxes.shape), tuple(scores.shape), None if classes is None else tuple(classes.shape)))
+    if not isinstance(max_det, (int, numpy.integer)) or max_det < 1:
+        raise ValueError("nms: max_det is a count >= 1, got %r" % (max_det,))
+    k = min(r, _lib.NMS_MAX_CANDIDATES)
+    return _nms_sorted(boxes, classes, scores, n, r, k, float(floor), _f32v(iou), classes is not None, min(int(max_det), k), boxes.ctx)
+
+
 def _window(img, rc):
     """img[rows, cols] as a contiguous device array."""
     r, c = rc
