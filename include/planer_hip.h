@@ -681,6 +681,46 @@ int pl_image_u8_nchw_f32(pl_ctx *ctx, const unsigned char *x, float *y, int N, i
 int pl_image_f32_u8(pl_ctx *ctx, const float *x, unsigned char *y, int N, int C, int H, int W, int Co, const int *order,
                     int nhwc, const float *k, const float *b, int trunc);
 int pl_labels_f32_u8(pl_ctx *ctx, const float *x, unsigned char *y, int N, int C, int H, int W, double threshold);
+/* ---- tiled inference around a plan: windows cut and blended in one launch each ----
+ * pl_tile_windows_*_nchw_f32: y, the float32 (S, Co, h, w) NCHW batch a plan reads, from ONE image x of (H, W, C), uint8 or
+ * float32, at any byte / float boundary.  r0 / c0: device arrays of n >= 1 window origins in the working image of WH x WW pixels;
+ * slot s shows window min(s, n - 1), so a short last chunk fills the plan's whole batch with defined data.  Window pixel (r, c)
+ * is working pixel (r0 + r, c0 + c), clamped into the working image.  ra/rs (WH entries), ca/cs (WW entries): the tables of
+ * pl_resize_hwc_f32 for (H, W) -> (WH, WW), all four or none.  None: WH == H, WW == W and the working image is x.  Given: a
+ * working pixel is util.resize's sample of x with the roundings of pl_image_u8_nchw_f32 (columns first, every product and sum
+ * rounded on its own), entries clamped to [0, H - 2] / [0, W - 2]; needs H, W >= 2.  The resampled image is never materialised.
+ *   uint8:   y = fl(fl(r * k[c]) + b[c]) of source channel order[c]; C, Co in 1..4 (else PL_EUNSUPPORTED); order, k, b host arrays
+ *            as pl_image_u8_nchw_f32 takes them (kernel arguments).
+ *   float32: a copy of channel c; any C == Co >= 1.
+ * A lane owns 4 consecutive pixels of one plane's flat h w pixels: one 16-byte store per channel where y is 16-byte aligned and
+ * h w % 4 == 0, single floats otherwise.  Nothing outside x's H W C elements is read whatever the origins hold, nothing outside
+ * y's S Co h w floats written.  Limit: fewer than 2^31 source elements and output floats, else PL_EUNSUPPORTED.  S == 0: PL_OK.
+ *
+ * pl_tile_blend_*: x holds all n = gr gc window results, float32 (n, C, oh, ow) as a plan wrote them, window i = gi gc + gj of
+ * the row-major grid at output origin (R0[i], C0[i]) (device arrays).  Per output pixel and plane the covering windows are
+ * visited in grid order: acc = fl(v w) for window 0, acc = fl(acc + fl(v w)) from +0.0 for the others, count = the integer sum
+ * of w, result fl(acc / (float)count), w = min(distance to the window's nearest edge, ramp) + 1: the reference's float32 loop
+ * (util.py:327-344: window 0 assigned, the others added to zeros) bit for bit, a -0.0 under window 0 alone included.  Any number of windows may cover a pixel; a pixel none covers gets 0 / 0.
+ * count must stay below 2^24 (the host keeps it within the reference's uint16).  One launch, no atomics, no zero-fill, no
+ * weight plane; every output element is written once.
+ *   pl_tile_blend_f32:       y float32 (OH, OW, C).
+ *   pl_tile_blend_u8:        y uint8 (OH, OW, Co) if nhwc else (Co, OH, OW), the blended value of plane order[c] through
+ *                            pl_image_f32_u8's rule (Co, order, k, b, trunc as there).
+ *   pl_tile_blend_labels_u8: y uint8 (OH, OW), pl_labels_f32_u8's rule on the blended values (C > 256: PL_EUNSUPPORTED).
+ * Limit: fewer than 2^31 window floats and output elements.  Every refusal comes before any launch. */
+int pl_tile_windows_u8_nchw_f32(pl_ctx *ctx, const unsigned char *x, float *y, int H, int W, int C, int Co, const int *order,
+                                const int *r0, const int *c0, int n, int S, int h, int w, int WH, int WW, const int *ra,
+                                const float *rs, const int *ca, const float *cs, const float *k, const float *b);
+int pl_tile_windows_f32_nchw_f32(pl_ctx *ctx, const float *x, float *y, int H, int W, int C, const int *r0, const int *c0, int n,
+                                 int S, int h, int w, int WH, int WW, const int *ra, const float *rs, const int *ca,
+                                 const float *cs);
+int pl_tile_blend_f32(pl_ctx *ctx, const float *x, float *y, int n, int C, int oh, int ow, const int *R0, const int *C0, int gr,
+                      int gc, int OH, int OW, int ramp);
+int pl_tile_blend_u8(pl_ctx *ctx, const float *x, unsigned char *y, int n, int C, int oh, int ow, const int *R0, const int *C0,
+                     int gr, int gc, int OH, int OW, int ramp, int Co, const int *order, int nhwc, const float *k,
+                     const float *b, int trunc);
+int pl_tile_blend_labels_u8(pl_ctx *ctx, const float *x, unsigned char *y, int n, int C, int oh, int ow, const int *R0,
+                            const int *C0, int gr, int gc, int OH, int OW, int ramp, double threshold);
 /* ---- detections as net output ----
  * YOLO-style heads -> rows [x1, y1, x2, y2, score, class]: pl_yolo_decode_f32 once per head, pl_topk_f32 over the scores,
  * pl_nms_f32.  Call them behind pl_plan_run, on the plan's context.  Asynchronous on ctx's stream; nothing is allocated or

@@ -199,6 +199,13 @@ SIGNATURES = {
     "pl_nms_f32": [_P, _P, _P, _P, _P, _I, _I, _I, c_double, c_double, _I, _I, _P, _P],
     "pl_tile_accumulate_f32": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I],
     "pl_tile_normalise_f32": [_P, _P, _P, _I, _I, _I],
+    "pl_tile_windows_u8_nchw_f32": [_P, _P, _P, _I, _I, _I, _I, POINTER(c_int), _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P,
+                                    POINTER(c_float), POINTER(c_float)],
+    "pl_tile_windows_f32_nchw_f32": [_P, _P, _P, _I, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P],
+    "pl_tile_blend_f32": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _I],
+    "pl_tile_blend_u8": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, POINTER(c_int), _I, POINTER(c_float),
+                         POINTER(c_float), _I],
+    "pl_tile_blend_labels_u8": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _I, c_double],
     "pl_splitk_reduce_f32": [_P, _P, _I, _P, _I, _I, _I, _P, _P, _P, _P, _I, c_double],
     "pl_stream_loop32_ok": [_Z, _I, POINTER(c_int)],
     "pl_comm_unique_id": [_P],

@@ -11,6 +11,7 @@
 #include "image_input_kernel.h"
 #include "image_output_kernel.h"
 #include "detect_kernel.h"
+#include "tile_kernel.h"
 
 namespace {
 
@@ -1050,6 +1051,136 @@ int pl_tile_normalise_f32(pl_ctx *ctx, float *buf, const float *count, int OH, i
     PL_REQUIRE(loop32_ok(ctx, total), PL_EUNSUPPORTED, "tile: image too large");
     CtxGuard g(ctx);
     tile_normalise_kernel<<<stream_grid(ctx, total), TPB, 0, ctx->stream>>>(buf, count, (unsigned)total, FastDiv(C));
+    PL_LAUNCH_CHECK();
+    return PL_OK;
+}
+
+// Net.tiled's window gather and blend (tile_kernel.h).  Every refusal comes before any launch.
+extern "C++" {        // (a template among the C entry points)
+namespace {
+template <typename T>
+int launch_tile_windows(pl_ctx *ctx, const char *who, const T *x, float *y, int H, int W, int C, int Co, const int *r0, const int *c0,
+                        int n, int S, int h, int w, int WH, int WW, const int *ra, const float *rs, const int *ca, const float *cs,
+                        const image_input::Affine &af) {
+    PL_REQUIRE(ctx && r0 && c0, PL_EINVAL, "%s: null argument", who);
+    PL_REQUIRE(H > 0 && W > 0 && h > 0 && w > 0 && WH > 0 && WW > 0 && S >= 0 && n >= 1, PL_EINVAL,
+               "%s: bad shape (image %d x %d, working %d x %d, window %d x %d, %d windows, %d slots)", who, H, W, WH, WW, h, w, n, S);
+    PL_REQUIRE(h <= WH && w <= WW, PL_EINVAL, "%s: a %d x %d window does not fit the %d x %d working image", who, h, w, WH, WW);
+    const bool tables = ra || rs || ca || cs;
+    PL_REQUIRE(!tables || (ra && rs && ca && cs), PL_EINVAL, "%s: all four sampling tables or none", who);
+    PL_REQUIRE(tables || (WH == H && WW == W), PL_EINVAL, "%s: a working size other than H x W needs sampling tables", who);
+    PL_REQUIRE(!tables || (H >= 2 && W >= 2), PL_EINVAL, "%s: resampling needs H, W >= 2", who);
+    const size_t hw = (size_t)h * w;
+    PL_REQUIRE((size_t)H * W < (1ull << 31) && below_2_31(H, W, C) && hw < (1ull << 31) && below_2_31(S, Co, hw), PL_EUNSUPPORTED,
+               "%s: 2^31 or more source elements or output floats", who);
+    if (S == 0) return PL_OK;
+    PL_REQUIRE(x && y, PL_EINVAL, "%s: null argument", who);
+    CtxGuard g(ctx);
+    const unsigned groups = cdiv(hw, tile::LANE_PX);
+    const size_t total = (size_t)S * groups;
+    const bool vec = aligned16(y) && hw % 4 == 0;
+    const tile::Tables tb = {ra, rs, ca, cs};
+    if (tables)
+        tile::tile_windows_kernel<T, true><<<stream_grid(ctx, total), TPB, 0, ctx->stream>>>(x, y, total, H, W, C, Co, h, w, WH, WW, r0, c0, n,
+                                                                                         groups, tb, af, vec);
+    else
+        tile::tile_windows_kernel<T, false><<<stream_grid(ctx, total), TPB, 0, ctx->stream>>>(x, y, total, H, W, C, Co, h, w, WH, WW, r0, c0, n,
+                                                                                          groups, tb, af, vec);
+    PL_LAUNCH_CHECK();
+    return PL_OK;
+}
+
+// the checks the three blend entry points share; fills `g` (Co, threshold and trunc are the caller's)
+int blend_geometry(pl_ctx *ctx, const char *who, const void *x, const void *y, int n, int C, int oh, int ow, const int *R0, const int *C0,
+                   int gr, int gc, int OH, int OW, int ramp, tile::Blend &g) {
+    PL_REQUIRE(ctx && x && y && R0 && C0, PL_EINVAL, "%s: null argument", who);
+    PL_REQUIRE(n >= 1 && C >= 1 && oh > 0 && ow > 0 && gr >= 1 && gc >= 1 && OH >= 0 && OW >= 0 && ramp >= 0, PL_EINVAL,
+               "%s: bad shape (%d windows (%d, %d, %d), grid %d x %d, output %d x %d, ramp %d)", who, n, C, oh, ow, gr, gc, OH, OW, ramp);
+    PL_REQUIRE((size_t)gr * gc == (size_t)n, PL_EINVAL, "%s: a %d x %d grid is not %d windows", who, gr, gc, n);
+    PL_REQUIRE(oh <= OH && ow <= OW, PL_EINVAL, "%s: a %d x %d window result does not fit the %d x %d output", who, oh, ow, OH, OW);
+    PL_REQUIRE((size_t)oh * ow < (1ull << 31) && below_2_31(n, C, (size_t)oh * ow) && (size_t)OH * OW < (1ull << 31), PL_EUNSUPPORTED,
+               "%s: 2^31 or more window floats or output pixels", who);
+    g.n = n, g.C = C, g.oh = oh, g.ow = ow, g.gr = gr, g.gc = gc, g.OH = OH, g.OW = OW, g.ramp = ramp;
+    g.Co = C, g.groups = cdiv((size_t)OW, tile::LANE_PX), g.threshold = 0.f, g.trunc = false;
+    return PL_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int pl_tile_windows_u8_nchw_f32(pl_ctx *ctx, const unsigned char *x, float *y, int H, int W, int C, int Co, const int *order,
+                                const int *r0, const int *c0, int n, int S, int h, int w, int WH, int WW, const int *ra, const float *rs,
+                                const int *ca, const float *cs, const float *k, const float *b) {
+    namespace ii = image_input;
+    PL_REQUIRE(ctx && k && b, PL_EINVAL, "pl_tile_windows_u8_nchw_f32: null argument");
+    PL_REQUIRE(C >= 1 && C <= ii::MAX_C && Co >= 1 && Co <= ii::MAX_C, PL_EUNSUPPORTED,
+               "pl_tile_windows_u8_nchw_f32: 1 to 4 channels, got C = %d, Co = %d", C, Co);
+    PL_REQUIRE(order || Co == C, PL_EINVAL, "pl_tile_windows_u8_nchw_f32: no channel order given and Co != C");
+    ii::Affine af;
+    for (int c = 0; c < ii::MAX_C; ++c) {
+        af.k[c] = c < Co ? k[c] : 0.f;
+        af.b[c] = c < Co ? b[c] : 0.f;
+        af.order[c] = c < Co ? (order ? order[c] : c) : 0;
+        PL_REQUIRE(af.order[c] >= 0 && af.order[c] < C, PL_EINVAL, "pl_tile_windows_u8_nchw_f32: order[%d] = %d is no source channel", c,
+                   af.order[c]);
+    }
+    return launch_tile_windows(ctx, "pl_tile_windows_u8_nchw_f32", x, y, H, W, C, Co, r0, c0, n, S, h, w, WH, WW, ra, rs, ca, cs, af);
+}
+
+int pl_tile_windows_f32_nchw_f32(pl_ctx *ctx, const float *x, float *y, int H, int W, int C, const int *r0, const int *c0, int n, int S,
+                                 int h, int w, int WH, int WW, const int *ra, const float *rs, const int *ca, const float *cs) {
+    PL_REQUIRE(C >= 1, PL_EINVAL, "pl_tile_windows_f32_nchw_f32: at least one channel, got C = %d", C);
+    image_input::Affine af = {};
+    return launch_tile_windows(ctx, "pl_tile_windows_f32_nchw_f32", x, y, H, W, C, C, r0, c0, n, S, h, w, WH, WW, ra, rs, ca, cs, af);
+}
+
+int pl_tile_blend_f32(pl_ctx *ctx, const float *x, float *y, int n, int C, int oh, int ow, const int *R0, const int *C0, int gr, int gc,
+                      int OH, int OW, int ramp) {
+    tile::Blend g;
+    if (int rc = blend_geometry(ctx, "pl_tile_blend_f32", x, y, n, C, oh, ow, R0, C0, gr, gc, OH, OW, ramp, g)) return rc;
+    PL_REQUIRE(below_2_31(OH, OW, C), PL_EUNSUPPORTED, "pl_tile_blend_f32: 2^31 or more output floats");
+    const size_t total = (size_t)OH * g.groups;
+    if (!total) return PL_OK;
+    CtxGuard guard(ctx);
+    tile::tile_blend_kernel<tile::OUT_F32><<<stream_grid(ctx, total), TPB, 0, ctx->stream>>>(x, y, total, R0, C0, g, image_output::Affine{});
+    PL_LAUNCH_CHECK();
+    return PL_OK;
+}
+
+int pl_tile_blend_u8(pl_ctx *ctx, const float *x, unsigned char *y, int n, int C, int oh, int ow, const int *R0, const int *C0, int gr,
+                     int gc, int OH, int OW, int ramp, int Co, const int *order, int nhwc, const float *k, const float *b, int trunc) {
+    namespace io = image_output;
+    tile::Blend g;
+    PL_REQUIRE(k && b, PL_EINVAL, "pl_tile_blend_u8: null argument");
+    if (int rc = blend_geometry(ctx, "pl_tile_blend_u8", x, y, n, C, oh, ow, R0, C0, gr, gc, OH, OW, ramp, g)) return rc;
+    PL_REQUIRE(Co >= 1 && Co <= io::MAX_CO, PL_EUNSUPPORTED, "pl_tile_blend_u8: 1 to 4 output channels, got Co = %d", Co);
+    PL_REQUIRE(order || Co == C, PL_EINVAL, "pl_tile_blend_u8: no channel order given and Co = %d != C = %d", Co, C);
+    io::Affine af;
+    for (int c = 0; c < io::MAX_CO; ++c) {
+        af.k[c] = c < Co ? k[c] : 0.f;
+        af.b[c] = c < Co ? b[c] : 0.f;
+        af.order[c] = c < Co ? (order ? order[c] : c) : 0;
+        PL_REQUIRE(af.order[c] >= 0 && af.order[c] < C, PL_EINVAL, "pl_tile_blend_u8: order[%d] = %d is no source plane", c, af.order[c]);
+    }
+    g.Co = Co, g.trunc = trunc != 0;
+    const size_t total = (size_t)OH * g.groups;
+    if (!total) return PL_OK;
+    CtxGuard guard(ctx);
+    if (nhwc) tile::tile_blend_kernel<tile::OUT_U8_NHWC><<<stream_grid(ctx, total), TPB, 0, ctx->stream>>>(x, y, total, R0, C0, g, af);
+    else tile::tile_blend_kernel<tile::OUT_U8_NCHW><<<stream_grid(ctx, total), TPB, 0, ctx->stream>>>(x, y, total, R0, C0, g, af);
+    PL_LAUNCH_CHECK();
+    return PL_OK;
+}
+
+int pl_tile_blend_labels_u8(pl_ctx *ctx, const float *x, unsigned char *y, int n, int C, int oh, int ow, const int *R0, const int *C0,
+                            int gr, int gc, int OH, int OW, int ramp, double threshold) {
+    tile::Blend g;
+    if (int rc = blend_geometry(ctx, "pl_tile_blend_labels_u8", x, y, n, C, oh, ow, R0, C0, gr, gc, OH, OW, ramp, g)) return rc;
+    PL_REQUIRE(C <= image_output::MAX_LABELS, PL_EUNSUPPORTED, "pl_tile_blend_labels_u8: at most 256 planes fit a byte, got C = %d", C);
+    g.threshold = (float)threshold;
+    const size_t total = (size_t)OH * g.groups;
+    if (!total) return PL_OK;
+    CtxGuard guard(ctx);
+    tile::tile_blend_kernel<tile::OUT_LABELS><<<stream_grid(ctx, total), TPB, 0, ctx->stream>>>(x, y, total, R0, C0, g, image_output::Affine{});
     PL_LAUNCH_CHECK();
     return PL_OK;
 }

@@ -30,7 +30,8 @@ from . import q4 as _q4
 from .conv_layouts import DIRECT_Q4, IGEMM_NCHW, LAYOUTS, STEM_POOL, STEM_POOL_NCHW, WINO4_Q4, WINO43_Q4, experiment, suffix
 from .layer import layer_map, wrap
 from .plan import compile_front, fuse_upsample_concat, lower
-from .util import DetectionSpec, ImageFeed, ImageOutSpec, ImageSpec, LabelSpec
+from .util import BlendGeometry, DetectionSpec, ImageFeed, ImageOutSpec, ImageSpec, LabelSpec, WindowFeed, _Tiling
+from .util import blend_windows as _blend_windows, resize as _resize
 
 STEM_WINO_DEFAULT = 1      # whether the stem + max-pool step takes the F(4,4) form where it applies
 
@@ -475,6 +476,97 @@ class Net:
             raise ValueError("detection output: output %d is already declared an image or label output" % taken[0])
         self._detect = (spec, indices)
         return self
+
+    def tiled(self, image, window=1024, margin=0.1, sample=1, glob=1, batch=None, progress=None):
+        """Whole-image inference, util.tile's job as a mode of the net: `image`, (H, W[, C]) as a host ndarray or a DeviceArray,
+        is cut into overlapping windows (util.tile's geometry: `sample`, `glob`, `window`, `margin` as there), the windows go
+        through the net in chunks of `batch` (default: all of them, one pass) and the results are blended with util.tile's
+        border-distance weights -- bit for bit the reference's float32 loop.  One gather kernel in front of each pass
+        (pl_tile_windows_*_nchw_f32) writes the plan's NCHW input, one blend kernel behind the last (pl_tile_blend_*) reads the
+        plan's NCHW results: no per-window launches, no transposes, no blend buffers.
+        A uint8 image needs a declared `image_input`, whose k, b and order are used (its `size` and `layout` are not: the image
+        is one (H, W, C) array and the working size is `sample`'s); a float32 image is taken as it is.  Returns float32
+        (OH, OW, Co); with `label_output` declared on output 0 the uint8 label map (OH, OW); with `image_output` the uint8 image in
+        its layout: (OH, OW, Co') or (Co', OH, OW).  Host image in, host array out; device in, device out.
+        Every chunk runs the plan of ONE signature, (batch, Co, h, w): a short last chunk is padded with its last window.
+        `progress(i, n)` is called after each chunk with the number of its last window (not at all for a single window).
+        Where the working size differs from the image's (`sample`, or an image smaller than the window grown to `glob`), the
+        gather kernel resamples on the way in and the float32 result goes through util.resize on the way out; a declared uint8
+        or label output then raises NotImplementedError.  All n window results stay resident until the blend:
+        n Co oh ow 4 bytes.  Nets with several inputs or outputs, or with `detection_output` declared, raise ValueError."""
+        if len(self.input) != 1:
+            raise ValueError("Net.tiled: a net with one input, this one has %d" % len(self.input))
+        if self._detect is not None:
+            raise ValueError("Net.tiled: detections of windows cannot be blended; `float_output` removes the declaration")
+        host_in = isinstance(image, numpy.ndarray)
+        if host_in and image.dtype != numpy.uint8:
+            image = numpy.ascontiguousarray(image, dtype=numpy.float32)
+        if not isinstance(image, (numpy.ndarray, DeviceArray)) or image.ndim not in (2, 3) or image.dtype not in (numpy.uint8, numpy.float32):
+            raise ValueError("Net.tiled: an (H, W[, C]) image, uint8 or float32, host ndarray or DeviceArray, got %r" % (image,))
+        spec = None
+        if image.dtype == numpy.uint8:
+            spec = self._image_spec(0)
+            if spec is None:
+                raise ValueError("Net.tiled: a uint8 image needs `image_input` declared (its k, b and order are used)")
+        out_spec = self._image_out.get(0)
+        geo = _Tiling(image.shape[0], image.shape[1], sample, glob, window, margin)
+        if geo.resampled and out_spec is not None:
+            raise NotImplementedError("Net.tiled: the working size %s differs from the image's %s, so the blended result is resampled "
+                                      "back -- and the argmax or the bytes of a resampled blend are a different product from the "
+                                      "resampled label map or image; use `float_output` and encode the result" % (geo.work, geo.src))
+        n = len(geo.windows)
+        batch = n if batch is None else int(batch)
+        if batch < 1:
+            raise ValueError("Net.tiled: batch is a count >= 1, got %r" % (batch,))
+        batch = min(batch, n)
+        dev = hip.asarray(image, ctx=self.ctx)
+        feeds = WindowFeed(dev, geo.windows, spec, geo.work)
+        results = shape = blend = None
+        for lo in range(0, n, batch):
+            hi = min(lo + batch, n)
+            out = self._run_windows(feeds.chunk(lo, batch))
+            if shape is None:
+                shape = tuple(out.shape)
+                if out.dtype != numpy.float32 or len(shape) != 4:
+                    raise ValueError("Net.tiled: the net's result is no float32 (N, C, H, W) tensor: %s %s" % (out.dtype, shape))
+                k = shape[2] / geo.win_h                 # output pixels per working pixel
+                blend = BlendGeometry(geo.windows, k, geo.margin, geo.work, shape[2], shape[3])
+                if out_spec is not None:
+                    out_spec.geometry((n,) + shape[1:])
+            if batch == n:
+                results = out                            # one pass: the blend reads the plan's own buffer
+            else:
+                if results is None:
+                    results = hip.empty((n,) + shape[1:], ctx=self.ctx)
+                results.rows(lo, hi).copy_from(out.rows(0, hi - lo))
+            if progress is not None and n > 1:
+                progress(hi, n)
+        rst = _blend_windows(results, geo.windows, blend.k, geo.margin, geo.work, out_spec if out_spec is not None else "float")
+        if geo.resampled:
+            rst = _resize(rst, geo.back_size(blend.k))
+        return rst.get() if host_in else rst
+
+    def _run_windows(self, feed):
+        """The net's single float32 result for the windows of `feed`, as the pass left it (a plan's own output buffer)."""
+        out = None
+        if self.use_graph and not self.profile:
+            try:
+                plan = self.compile(feed)
+                if isinstance(plan.outputs, tuple) and len(plan.outputs) != 1:      # (before anything is launched)
+                    raise ValueError("Net.tiled: a net with one output, this one returns %d" % len(plan.outputs))
+                out = self._launch([feed], declared=False).outputs
+            except _lib.NotCapturable:
+                self.use_graph = False
+        if out is None:
+            x = feed.materialise()
+            out = self._interpret(self._eager_program([x]), [x]) if self._eager_prog else self.forward(x)
+        if isinstance(out, (tuple, list)):
+            if len(out) != 1:
+                raise ValueError("Net.tiled: a net with one output, this one returns %d" % len(out))
+            out = out[0]
+        if not isinstance(out, DeviceArray):
+            raise ValueError("Net.tiled: the net's result is no device tensor: %s" % type(out).__name__)
+        return out
 
     def _unclaimed(self, index):
         index = self._out_index(index)
@@ -1277,8 +1369,15 @@ class Net:
         return v.shape
 
     def _replay(self, xs, private=True):
+        # private copies (the plan's buffers are rewritten by the next replay) unless the caller copies to the host right away;
+        # a declared uint8 output is encoded into a fresh array either way
+        return self._hand_back(self._launch(xs).outputs, private)
+
+    def _launch(self, xs, declared=True):
+        """One pass of the plan for `xs`, joined into the net's own stream; the plan (its outputs are the plan's own buffers).
+        `declared`: the outputs are checked against the declared output forms before anything is launched."""
         plan = self.compile(*xs)
-        if self._image_out or self._detect is not None:
+        if declared and (self._image_out or self._detect is not None):
             self._check_outputs(plan.outputs)          # (before anything is launched)
         if isinstance(plan, _PipelinePlan):
             # the replica whose turn it is gets the inputs (plan.inputs are those of the replica launched LAST);
@@ -1288,9 +1387,7 @@ class Net:
         else:
             self._feed_on_main(plan, xs)
         plan.launch()
-        # private copies (the plan's buffers are rewritten by the next replay) unless the caller copies to the host right away;
-        # a declared uint8 output is encoded into a fresh array either way
-        return self._hand_back(plan.outputs, private)
+        return plan
 
     def _feed_on_main(self, plan, xs):
         """Inputs of a one-graph or sub-batch plan, copied on the net's OWN stream (where the caller produced them);

@@ -71,6 +71,20 @@ def image_affine(mean, std, scale=255.0):
     return (1.0 / (float(scale) * std)).astype(numpy.float32), (-mean / std).astype(numpy.float32)
 
 
+def _sampling_tables(ctx, h, w, oh, ow):
+    """util.resize's sampling tables (ra, rs, ca, cs) for (h, w) -> (oh, ow) as device arrays, or None where the sizes agree."""
+    key = (h, w, oh, ow)
+    if key[:2] == key[2:]:
+        return None
+    cache = ctx.__dict__.setdefault("_image_tables", {})
+    if key not in cache:
+        ra, rs = _axis_samples(key[0], key[2])
+        ca, cs = _axis_samples(key[1], key[3])
+        cache[key] = tuple(hip.asarray(a, ctx=ctx) for a in (ra, rs, ca, cs))
+        ctx.synchronize()
+    return cache[key]
+
+
 class ImageSpec:
     """How a uint8 image batch becomes a net's float32 NCHW input: y[:, c] = fl(fl(r * k[c]) + b[c]) with r the byte of source
     channel order[c], or util.resize's sample of those bytes where `size` differs from the batch's H x W.  Host values only."""
@@ -116,16 +130,7 @@ class ImageSpec:
     def tables(self, ctx, src, out):
         """util.resize's sampling tables for (H, W) -> (OH, OW) as device arrays, or None where the sizes agree.  Kept on the
         Context object for its lifetime (every stream of the device may read them: the upload is over on return)."""
-        key = (src[1], src[2], out[2], out[3])
-        if key[:2] == key[2:]:
-            return None
-        cache = ctx.__dict__.setdefault("_image_tables", {})
-        if key not in cache:
-            ra, rs = _axis_samples(key[0], key[2])
-            ca, cs = _axis_samples(key[1], key[3])
-            cache[key] = tuple(hip.asarray(a, ctx=ctx) for a in (ra, rs, ca, cs))
-            ctx.synchronize()
-        return cache[key]
+        return _sampling_tables(ctx, src[1], src[2], out[2], out[3])
 
     def bind(self, x):
         return ImageFeed(self, x)
@@ -412,6 +417,187 @@ def nms(boxes, scores, classes=None, iou=0.45, max_det=100, floor=-math.inf):
         raise ValueError("nms: max_det is a count >= 1, got %r" % (max_det,))
     k = min(r, _lib.NMS_MAX_CANDIDATES)
     return _nms_sorted(boxes, classes, scores, n, r, k, float(floor), _f32v(iou), classes is not None, min(int(max_det), k), boxes.ctx)
+
+
+# ---- tiled inference around a plan: windows cut and blended in one launch each ----------------------------------
+def _window_origins(windows):
+    """(r0, c0, h, w) of a list of (row slice, column slice) windows of one size: int32 origin arrays and the extent."""
+    windows = list(windows)
+    if not windows:
+        raise ValueError("tile windows: at least one window")
+    r0 = numpy.array([r.start for r, _ in windows], numpy.int32)
+    c0 = numpy.array([c.start for _, c in windows], numpy.int32)
+    h, w = windows[0][0].stop - windows[0][0].start, windows[0][1].stop - windows[0][1].start
+    if h < 1 or w < 1 or any((r.stop - r.start, c.stop - c.start) != (h, w) for r, c in windows):
+        raise ValueError("tile windows: every window has the first one's size, %d x %d" % (h, w))
+    return r0, c0, h, w
+
+
+class WindowFeed(ImageFeed):
+    """Windows of ONE device image (H, W[, C]), uint8 or float32, standing for the float32 (slots, Co, h, w) batch they are cut
+    into (pl_tile_windows_*_nchw_f32): what `ImageFeed` is for a uint8 batch, so a plan is looked up by `shape` / `dtype` and fed
+    by `decode_into`.  uint8 images need an `ImageSpec`, whose k, b and order are used (its size and layout are not); `work`:
+    the working size the windows are cut from, the image resampled as util.resize does where it differs from H x W.  Slots
+    past the last window repeat it.  The origins are uploaded once, here; `chunk` / `rows` hand out runs of slots."""
+
+    def __init__(self, image, windows, spec=None, work=None, slots=None):
+        if not isinstance(image, DeviceArray) or image.dtype not in (numpy.uint8, numpy.float32) or image.ndim not in (2, 3):
+            raise TypeError("tile windows: expected a uint8 or float32 DeviceArray (H, W[, C]), got %r" % (image,))
+        height, width = image.shape[:2]
+        c = image.shape[2] if image.ndim == 3 else 1
+        r0, c0, h, w = _window_origins(windows)
+        wh, ww = (height, width) if work is None else (int(work[0]), int(work[1]))
+        if min(r0.min(), c0.min()) < 0 or r0.max() + h > wh or c0.max() + w > ww:
+            raise ValueError("tile windows: a %d x %d window lies outside the %d x %d working image" % (h, w, wh, ww))
+        if (wh, ww) != (height, width) and (height < 2 or width < 2):
+            raise ValueError("tile windows: resampling needs H, W >= 2, got %d x %d" % (height, width))
+        if image.dtype == numpy.uint8:
+            if spec is None:
+                raise ValueError("tile windows: a uint8 image needs k and b (util.image_affine)")
+            if not 1 <= c <= 4:
+                raise NotImplementedError("tile windows: 1 to 4 uint8 source channels, got %d" % c)
+            if spec.order is None and spec.channels != c:
+                raise ValueError("tile windows: %d values in k for %d source channels and no order" % (spec.channels, c))
+            if spec.order is not None and max(spec.order) >= c:
+                raise ValueError("tile windows: order %r names a channel the %d-channel image does not have" % (spec.order, c))
+            co = spec.channels
+        else:
+            if c < 1:
+                raise ValueError("tile windows: an image without channels, shape %s" % (tuple(image.shape),))
+            spec, co = None, c
+        n = len(r0)
+        slots = n if slots is None else int(slots)
+        if slots < n:
+            raise ValueError("tile windows: %d slots for %d windows" % (slots, n))
+        self.spec, self.u8, self.ctx = spec, image, image.ctx
+        self.src, self.work, self.shape = (height, width, c), (wh, ww), (slots, co, h, w)
+        self.dtype, self.ndim = numpy.dtype(numpy.float32), 4
+        self.tabs = _sampling_tables(image.ctx, height, width, wh, ww)
+        self.origins = hip.asarray(numpy.concatenate([r0, c0]), ctx=image.ctx)      # [r0 of every window, c0 of every window]
+        self.count, self.first, self.n = n, 0, n
+
+    def chunk(self, lo, slots):
+        """The feed of `slots` slots that starts at window `lo` of this one (windows past the last repeat it)."""
+        if not 0 <= lo < self.n or slots < 1:
+            raise IndexError((lo, slots))
+        sub = WindowFeed.__new__(WindowFeed)
+        for key, v in self.__dict__.items():
+            setattr(sub, key, v)
+        sub.first, sub.n, sub.shape = self.first + lo, min(self.n - lo, slots), (slots,) + self.shape[1:]
+        return sub
+
+    def rows(self, lo, hi):
+        return self.chunk(min(lo, self.n - 1), hi - lo)
+
+    def decode_into(self, ptr, ctx=None):
+        height, width, c = self.src
+        slots, co, h, w = self.shape
+        r0 = self.origins.ptr + 4 * self.first
+        geo = (r0, r0 + 4 * self.count, self.n, slots, h, w, self.work[0], self.work[1])
+        tabs = [a.ptr for a in self.tabs] if self.tabs else [None] * 4
+        handle = (ctx or self.ctx).handle
+        if self.spec is not None:
+            sp = self.spec
+            _lib.call("pl_tile_windows_u8_nchw_f32", handle, self.u8.ptr, ptr, height, width, c, co, sp._order, *geo, *tabs, sp._k, sp._b)
+        else:
+            _lib.call("pl_tile_windows_f32_nchw_f32", handle, self.u8.ptr, ptr, height, width, c, *geo, *tabs)
+
+
+def cut_windows(image, windows, k=None, b=None, order=None, work=None, slots=None):
+    """The windows `windows` ((row slice, column slice) pairs of one size, as `grid_slice` returns them) of the device image
+    (H, W[, C]) as the float32 (slots, Co, h, w) DeviceArray a net reads, in ONE launch (pl_tile_windows_*_nchw_f32).  uint8
+    images: fl(fl(r * k[c]) + b[c]) of source channel order[c] ((k, b) from `image_affine`); float32 images: a copy (k, b, order
+    unused).  `work`: the (height, width) the windows are cut from; where it differs from H x W the image is resampled as
+    util.resize does, on the way and never as a whole.  `slots` (default: the number of windows): slots past the last window
+    repeat it.  Asynchronous on the image's stream."""
+    if isinstance(image, DeviceArray) and image.dtype == numpy.uint8:
+        if k is None or b is None:
+            raise ValueError("tile windows: a uint8 image needs k and b (util.image_affine)")
+        spec = ImageSpec(k, b, "nhwc", None, order)
+    else:
+        spec = None
+    return WindowFeed(image, windows, spec, work, slots).materialise()
+
+
+class BlendGeometry:
+    """Host arithmetic of one blend (util.py:317-343 of the reference): for windows cut from a working image of `work` pixels
+    whose results are (oh, ow) each, the scale k, the scaled origins R0 / C0 (int(start * k), int32), the row-major grid shape
+    (gr, gc), the output size (OH, OW) = (int(work_h * k), int(work_w * k)) and ramp = int(margin * k); one window: the output is
+    the window result, ramp 0.  ValueError where a scaled window is not oh x ow (the reference's broadcast error), where a pixel
+    is covered by no window, or where the weight total could pass the reference's uint16."""
+
+    def __init__(self, windows, k, margin, work, oh, ow):
+        windows = list(windows)
+        r0, c0, _, _ = _window_origins(windows)
+        self.n, self.k, self.oh, self.ow = len(windows), k, int(oh), int(ow)
+        for gc in range(self.n, 0, -1):                   # (the widest grid that fits: any that fits visits the windows alike)
+            rows, cols = [r for r, _ in windows[::gc]], [c for _, c in windows[:gc]]
+            if self.n % gc == 0 and windows == list(itertools.product(rows, cols)):
+                break
+        else:
+            raise ValueError("tile blend: the windows are no row-major grid (itertools.product(rows, columns))")
+        self.gr, self.gc = self.n // gc, gc
+        if self.n == 1:
+            self.R0, self.C0 = numpy.zeros(1, numpy.int32), numpy.zeros(1, numpy.int32)
+            self.OH, self.OW, self.ramp = self.oh, self.ow, 0
+            return
+        for axis, (cuts, size) in enumerate(((rows, self.oh), (cols, self.ow))):
+            for s in cuts:
+                if int(s.stop * k) - int(s.start * k) != size:
+                    raise ValueError("tile blend: window %s [%d, %d) scales by %r to %d pixels, the net's result has %d"
+                                     % ("rows" if axis == 0 else "columns", s.start, s.stop, k, int(s.stop * k) - int(s.start * k), size))
+        self.R0 = numpy.array([int(r.start * k) for r, _ in windows], numpy.int32)
+        self.C0 = numpy.array([int(c.start * k) for _, c in windows], numpy.int32)
+        self.OH, self.OW, self.ramp = int(work[0] * k), int(work[1] * k), int(margin * k)
+        most = 1
+        for cuts, size, total in ((rows, self.oh, self.OH), (cols, self.ow, self.OW)):
+            cover = numpy.zeros(total + 1, numpy.int64)
+            for s in cuts:
+                a = int(s.start * k)
+                if a + size > total:
+                    raise ValueError("tile blend: a window result ends at %d, the output has %d" % (a + size, total))
+                cover[a] += 1
+                cover[a + size] -= 1
+            cover = numpy.cumsum(cover)[:total]
+            if total and cover.min() < 1:
+                raise ValueError("tile blend: output pixel %d is covered by no window" % int(cover.argmin()))
+            most *= int(cover.max()) if total else 1
+        if (self.ramp + 1) * most > 65535:
+            raise ValueError("tile blend: weight %d on %d windows over one pixel passes 65535, the reference's uint16 count"
+                             % (self.ramp + 1, most))
+
+
+def blend_windows(outs, windows, k, margin, work, out="float"):
+    """All window results `outs`, float32 (n, Co, oh, ow) as a net wrote them for `windows` (see `cut_windows`), blended into the
+    whole output in ONE launch (pl_tile_blend_*): per pixel the covering windows in grid order, weights rising from 1 at a
+    window's edge to int(margin * k) + 1, the reference's float32 loop bit for bit.  k: output pixels per working pixel; margin
+    in working pixels; work: the working image's (height, width).  out="float": float32 (OH, OW, Co); an `ImageOutSpec`: the uint8
+    image in its layout, (OH, OW, Co') or (Co', OH, OW); a `LabelSpec`: the uint8 label map (OH, OW).  Asynchronous on outs'
+    stream; `BlendGeometry` raises ValueError for geometries the reference cannot blend."""
+    n, c, oh, ow = _f32_nchw("tile blend", outs)
+    windows = list(windows)
+    if n != len(windows):
+        raise ValueError("tile blend: %d results for %d windows" % (n, len(windows)))
+    geo = BlendGeometry(windows, k, margin, work, oh, ow)
+    ctx = outs.ctx
+    origins = hip.asarray(numpy.concatenate([geo.R0, geo.C0]), ctx=ctx)
+    args = (n, c, oh, ow, origins.ptr, origins.ptr + 4 * n, geo.gr, geo.gc, geo.OH, geo.OW, geo.ramp)
+    if isinstance(out, ImageOutSpec):
+        co = out.geometry((n, c, oh, ow))[4]
+        y = hip.empty((geo.OH, geo.OW, co) if out.layout == "nhwc" else (co, geo.OH, geo.OW), numpy.uint8, ctx=ctx)
+        kk, bb = out._affine(co)
+        _lib.call("pl_tile_blend_u8", ctx.handle, outs.ptr, y.ptr, *args, co, out._order, int(out.layout == "nhwc"), kk, bb,
+                  int(out.rounding == "truncate"))
+    elif isinstance(out, LabelSpec):
+        out.geometry((n, c, oh, ow))
+        y = hip.empty((geo.OH, geo.OW), numpy.uint8, ctx=ctx)
+        _lib.call("pl_tile_blend_labels_u8", ctx.handle, outs.ptr, y.ptr, *args, out.threshold)
+    elif out == "float":
+        y = hip.empty((geo.OH, geo.OW, c), ctx=ctx)
+        _lib.call("pl_tile_blend_f32", ctx.handle, outs.ptr, y.ptr, *args)
+    else:
+        raise ValueError("tile blend: out is 'float', an ImageOutSpec or a LabelSpec, got %r" % (out,))
+    return y
 
 
 def _window(img, rc):
