@@ -1125,6 +1125,7 @@ int convt_q4_launch(pl_ctx *ctx, const float *x, int N, int Cin, int H, int W, c
     a.divMt = FastDiv(1); a.divCpt = FastDiv(1);
     a.ep = make_epilogue(bias, scale, shift, res, act, alpha);
     a.ph_sh = sh; a.ph_sw = sw; a.ph_oh = pt % sh; a.ph_ow = pl % sw; a.ph_Ho = Ho; a.ph_Wo = Wo;
+    a.ph_kh = kh; a.ph_kw = kw;
     const int rc = plan_and_run(ctx, 14, a, key, true, y, res != y && x != y);
     if (rc == PL_OK) {
         char buf[64];

@@ -283,6 +283,15 @@ __device__ __forceinline__ void conv_q4_body(const ConvArgs &p, unsigned bid = b
         j_n = (int)n;
     }
     constexpr int OOB = (int)0x80000000;
+    // PH: where kh (kw) is no multiple of the stride, the sub-filters of the higher phases are shorter: their first rows
+    // (columns) lie beyond the filter.  wq holds zeros there; the input under such a tap is a real pixel that the output does
+    // not depend on, so it is not loaded (0 x inf is no zero).  Taps a < ph_a0 or b < ph_b0 read nothing.
+    int ph_a0 = 0, ph_b0 = 0;
+    if constexpr (PH) {
+        const int rh = (int)(g / (unsigned)p.ph_sw), rw = (int)g - rh * p.ph_sw;
+        ph_a0 = p.kh - (p.ph_kh - rh + p.ph_sh - 1) / p.ph_sh;
+        ph_b0 = p.kw - (p.ph_kw - rw + p.ph_sw - 1) / p.ph_sw;
+    }
     // row-packed input: byte offset of (n, ho*sh, wo*sw, channel 0) in the padded NHWC image
     // (hbase / wbase carry -pad; the padded image starts at -pad)
     const int rp_base = (p.rp_rq && jok) ? (((j_n * p.H + hbase + p.pt) * p.W + wbase + p.pl) * p.Cin) << 2 : OOB;
@@ -327,17 +336,28 @@ __device__ __forceinline__ void conv_q4_body(const ConvArgs &p, unsigned bid = b
             // Row-packed small-Cin input (the 3-channel 7x7 stem): x is [N][H+2p][Wp][Cin] with the
             // zero border already in place, so a filter row's kw*Cin floats are contiguous and K runs
             // (filter row, quad of that row segment).  The thread's base offset never changes, the
-            // k-quad offset is scalar, there is nothing to range-check but the column itself.
+            // k-quad offset is scalar, there is nothing to range-check but the column itself.  What the filter pads with zeros
+            // reads as zero here too, by a select: the K padding quads past Qtot, and in the last quad of a filter row the floats
+            // past its kw*Cin -- the channels of the next pixel, which this output does not depend on.
 #pragma unroll
             for (int ps = 0; ps < C::B_PASSES; ++ps) {
-                const int q = min(q0 + kg0 + ps * C::KG_PER_PASS, p.Qtot - 1);     // K padding: zero filter rows
+                const int qq = q0 + kg0 + ps * C::KG_PER_PASS;
+                const int q = min(qq, p.Qtot - 1);
                 const int a = (int)p.divCpt.div((unsigned)q);
-                const int off = (a * p.W * p.Cin + (q - a * p.rp_rq) * 4) << 2;     // p.W = padded row length
+                const int r = q - a * p.rp_rq;
+                const int off = (a * p.W * p.Cin + r * 4) << 2;                     // p.W = padded row length
+                const bool live = qq < p.Qtot;
                 if constexpr (KG_UNIFORM)
-                    breg[ps] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(xrsrc, rp_base, off, 0));
+                    breg[ps] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(xrsrc, live ? rp_base : OOB, off, 0));
                 else
                     breg[ps] = __builtin_bit_cast(
-                        float4, __builtin_amdgcn_raw_buffer_load_b128(xrsrc, jok ? rp_base + off : OOB, 0, 0));
+                        float4, __builtin_amdgcn_raw_buffer_load_b128(xrsrc, (jok && live) ? rp_base + off : OOB, 0, 0));
+                const int inside = p.kw * p.Cin - 4 * r;                            // floats of this quad inside the filter row
+                if (inside < 4) {
+                    breg[ps].w = 0.f;
+                    if (inside < 3) breg[ps].z = 0.f;
+                    if (inside < 2) breg[ps].y = 0.f;
+                }
             }
         } else if (p.uni) {
             // chunks are requested in order, each at most one further than the last (c is clamped at the end)
@@ -350,7 +370,8 @@ __device__ __forceinline__ void conv_q4_body(const ConvArgs &p, unsigned bid = b
             st_b = wb ? 0 : nb;
             st_a += wb ? 1 : 0;
             const int dy = st_a * p.dh, dx = st_b * p.dw;
-            const bool ok = (unsigned)(hbase + dy) < (unsigned)p.H && (unsigned)(wbase + dx) < (unsigned)p.W;
+            const bool ok = (unsigned)(hbase + dy) < (unsigned)p.H && (unsigned)(wbase + dx) < (unsigned)p.W &&
+                            (!PH || (st_a >= ph_a0 && st_b >= ph_b0));
             const int voff = ok ? (int)((unsigned)(cbase + dy * p.W + dx) << 4) : OOB;
 #pragma unroll
             for (int ps = 0; ps < C::B_PASSES; ++ps) {
@@ -369,7 +390,8 @@ __device__ __forceinline__ void conv_q4_body(const ConvArgs &p, unsigned bid = b
                 unsigned a, b;
                 p.divKw.divmod(tap, a, b);
                 const int dy = q < p.Qtot ? (int)a * p.dh : (1 << 15), dx = (int)b * p.dw;   // |hbase| < 2^14
-                const bool ok = (unsigned)(hbase + dy) < (unsigned)p.H && (unsigned)(wbase + dx) < (unsigned)p.W;
+                const bool ok = (unsigned)(hbase + dy) < (unsigned)p.H && (unsigned)(wbase + dx) < (unsigned)p.W &&
+                                (!PH || ((int)a >= ph_a0 && (int)b >= ph_b0));
                 const int voff = (int)((unsigned)(cbase + dy * p.W + dx) << 4);   // garbage when !ok, never used
                 const int coff = (cq * p.HW) << 4;
                 if constexpr (KG_UNIFORM)

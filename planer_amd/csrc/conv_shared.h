@@ -42,6 +42,7 @@ struct ConvArgs {
     // (g / ph_sw, g % ph_sw), and pixel (i, j) of the Ho x Wo phase grid lands on output pixel
     // (ph_sh*i + g/ph_sw - ph_oh, ph_sw*j + g%ph_sw - ph_ow) of the ph_Ho x ph_Wo output, or nowhere
     int ph_sh, ph_sw, ph_oh, ph_ow, ph_Ho, ph_Wo;
+    int ph_kh, ph_kw; // the transposed filter's own extents (kh / kw above are the sub-filters')
 };
 // blockIdx.x -> (group, m-tile, n-tile).  XCD-aware: the 8 XCDs (private L2s)
 // each walk a contiguous range of tiles, M-tiles fastest, so workgroups that

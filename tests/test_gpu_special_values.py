@@ -12,6 +12,10 @@ float64 with -0 mapped to -1e-300 -- and the one named divergence from numpy, ZE
 differs.
 
 The last cases are the empty extents: numpy's answer (or its exception type) without a kernel launch.
+
+The conv kernels are not here: test_stem_maxpool_nan_mask keeps its one NaN pixel, and tests/test_gpu_conv_nonfinite.py plants
+NaN and +-inf in the input, the filter and the tail of every conv family (the stem + max-pool kernels among them) under the
+contract of tests/nonfinite_ref.py.
 """
 import zlib
 
