@@ -758,6 +758,39 @@ int pl_yolo_decode_f32(pl_ctx *ctx, const float *x, int N, int A, int C, int Gh,
                        double sy, double conf, int row, int offset, float *scores, int *classes, float *boxes);
 int pl_nms_f32(pl_ctx *ctx, const float *boxes, const int *classes, const float *sorted_scores, const long long *order, int N,
                int R, int K, double floor, double iou, int class_aware, int max_det, float *det, int *num);
+/* ---- objects as net output ----
+ * pl_components_u8_i32: connected components of the uint8 class map m (N, H, W) -- pl_labels_f32_u8's output, or any label map --
+ * and the region table of each image's first max_objects objects.  An object is a maximal set of pixels of one image with equal
+ * class other than `background` (0..255, or -1: every pixel belongs to an object), joined through 4- or 8-neighbour steps
+ * (`connectivity`); pixels of different images, and the last pixel of a row and the first of the next, are no neighbours.
+ *   labels    int32 (N, H, W): 0 on background, else the object's number 1, 2, ... per image, objects numbered by the raster
+ *             position y W + x of their first pixel (scipy.ndimage.label's numbering for a binary map; the same rule over all
+ *             classes together otherwise).
+ *   num       int32 (N): the objects of each image; it may exceed max_objects.
+ *   objects   int32 (N, max_objects, 6): row j is object j + 1, [class, area, y0, x0, y1, x1], the box half-open; rows at and
+ *             behind num are 0.  Objects numbered above max_objects keep their number in labels and have no row.
+ *   centroids float32 (N, max_objects, 2): [cy, cx] = float32(float64(sum of y) / float64(area)), the sums exact integers, one
+ *             IEEE double division, one rounding; +0.0 in the unused rows.
+ * Everything is exact and unique: nothing depends on the order in which atomics land.  All four outputs are written completely
+ * and nothing relies on zeroed memory.  Asynchronous on ctx's stream; seven launches (six where max_objects == 0, one fewer
+ * where the image is a single tile), no host wait, no host-computed value: capturable into a hipGraph.
+ * scratch: PL_CC_SCRATCH_BYTES(N, H, W, max_objects) bytes of the caller's, 8-byte aligned, contents irrelevant.
+ * A workgroup of the tile passes takes PL_CC_TILE_H x PL_CC_TILE_W pixels; roots are counted per PL_CC_BLOCK raster-consecutive
+ * pixels and one workgroup per image scans those counts PL_CC_SCAN_STEP at a time.
+ * PL_EINVAL: a null pointer (objects / centroids may be NULL when max_objects == 0), a negative dimension or max_objects,
+ * connectivity other than 4 or 8, background outside -1..255.  PL_EUNSUPPORTED: H W >= 2^31 or N H W >= 2^31,
+ * max_objects > PL_CC_MAX_OBJECTS, N max_objects 6 >= 2^31.  N == 0 or H W == 0: PL_OK, no launch.  Every refusal comes before any
+ * launch and leaves the outputs untouched. */
+#define PL_CC_TILE_H 32
+#define PL_CC_TILE_W 64
+#define PL_CC_BLOCK 2048
+#define PL_CC_SCAN_STEP 1024
+#define PL_CC_MAX_OBJECTS 65536
+#define PL_CC_SCRATCH_BYTES(N, H, W, max_objects)                                                        \
+    ((size_t)(N) * (size_t)(max_objects) * 16 + (size_t)(N) * (size_t)(H) * (size_t)(W) * 4 +            \
+     (size_t)(N) * (((size_t)(H) * (size_t)(W) + PL_CC_BLOCK - 1) / PL_CC_BLOCK) * 4)
+int pl_components_u8_i32(pl_ctx *ctx, const unsigned char *m, int N, int H, int W, int connectivity, int background,
+                         int max_objects, void *scratch, int *labels, int *num, int *objects, float *centroids);
 /* split-K combine + epilogue (internal to conv, exported for tests) */
 int pl_splitk_reduce_f32(pl_ctx *ctx, const float *ws, int splits, float *y,
                          int N, int C, int inner, const float *bias,

@@ -22,6 +22,10 @@ IMAGE_OUT_TILE_PIXELS = 1024        # include/planer_hip.h PL_IMAGE_OUT_TILE_PIX
 IMAGE_OUT_LANE_PIXELS = 4           # include/planer_hip.h PL_IMAGE_OUT_LANE_PIXELS
 YOLO_MAX_ANCHORS = 8                # include/planer_hip.h PL_YOLO_MAX_ANCHORS
 NMS_MAX_CANDIDATES = 4096           # include/planer_hip.h PL_NMS_MAX_CANDIDATES
+CC_TILE_H, CC_TILE_W = 32, 64      # include/planer_hip.h PL_CC_TILE_H, PL_CC_TILE_W
+CC_BLOCK = 2048                     # include/planer_hip.h PL_CC_BLOCK
+CC_SCAN_STEP = 1024                 # include/planer_hip.h PL_CC_SCAN_STEP
+CC_MAX_OBJECTS = 65536              # include/planer_hip.h PL_CC_MAX_OBJECTS
 ACT_NONE, ACT_RELU, ACT_LEAKY = 0, 1, 2
 ACT_RES_AFTER = 16
 UNIQUE_ID_BYTES = 128
@@ -197,6 +201,7 @@ SIGNATURES = {
     "pl_labels_f32_u8": [_P, _P, _P, _I, _I, _I, _I, c_double],
     "pl_yolo_decode_f32": [_P, _P, _I, _I, _I, _I, _I, POINTER(c_float), c_double, c_double, c_double, _I, _I, _P, _P, _P],
     "pl_nms_f32": [_P, _P, _P, _P, _P, _I, _I, _I, c_double, c_double, _I, _I, _P, _P],
+    "pl_components_u8_i32": [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
     "pl_tile_accumulate_f32": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I],
     "pl_tile_normalise_f32": [_P, _P, _P, _I, _I, _I],
     "pl_tile_windows_u8_nchw_f32": [_P, _P, _P, _I, _I, _I, _I, POINTER(c_int), _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P,

@@ -11,6 +11,7 @@
 #include "image_input_kernel.h"
 #include "image_output_kernel.h"
 #include "detect_kernel.h"
+#include "components_kernel.h"
 #include "tile_kernel.h"
 
 namespace {
@@ -1027,6 +1028,51 @@ int pl_nms_f32(pl_ctx *ctx, const float *boxes, const int *classes, const float 
         PL_HIP(hipFuncSetAttribute((const void *)dt::nms_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     dt::nms_kernel<<<(unsigned)N, dt::TPB, lds, ctx->stream>>>(boxes, classes, sorted_scores, order, R, K, (float)floor, (float)iou,
                                                                class_aware != 0, max_det, det, num);
+    PL_LAUNCH_CHECK();
+    return PL_OK;
+}
+
+// uint8 class map -> objects (components_kernel.h).  Every refusal comes before any launch.
+int pl_components_u8_i32(pl_ctx *ctx, const unsigned char *m, int N, int H, int W, int connectivity, int background, int max_objects,
+                         void *scratch, int *labels, int *num, int *objects, float *centroids) {
+    namespace cc = components;
+    PL_REQUIRE(ctx && m && scratch && labels && num && (max_objects <= 0 || (objects && centroids)), PL_EINVAL,
+               "pl_components_u8_i32: null argument");
+    PL_REQUIRE(N >= 0 && H >= 0 && W >= 0 && max_objects >= 0, PL_EINVAL, "pl_components_u8_i32: bad shape (%d, %d, %d), max_objects = %d", N,
+               H, W, max_objects);
+    PL_REQUIRE(connectivity == 4 || connectivity == 8, PL_EINVAL, "pl_components_u8_i32: connectivity is 4 or 8, got %d", connectivity);
+    PL_REQUIRE(background >= -1 && background <= 255, PL_EINVAL, "pl_components_u8_i32: background is a class 0..255 or -1, got %d",
+               background);
+    const size_t HW = (size_t)H * W;
+    PL_REQUIRE(HW < (1ull << 31) && (size_t)N * HW < (1ull << 31), PL_EUNSUPPORTED, "pl_components_u8_i32: 2^31 or more pixels");
+    PL_REQUIRE(max_objects <= PL_CC_MAX_OBJECTS, PL_EUNSUPPORTED, "pl_components_u8_i32: at most %d table rows per image, got max_objects = %d",
+               PL_CC_MAX_OBJECTS, max_objects);
+    if (N == 0 || HW == 0) return PL_OK;
+    cc::Geo g;
+    g.H = H, g.W = W, g.HW = (int)HW;
+    g.tiles_x = (int)cdiv(W, cc::TILE_W), g.tiles_y = (int)cdiv(H, cc::TILE_H), g.blocks = (int)cdiv(HW, cc::BLOCK);
+    const size_t tiles = (size_t)N * g.tiles_x * g.tiles_y;
+    PL_REQUIRE(tiles < (1ull << 31) && (size_t)N * max_objects * 6 < (1ull << 31), PL_EUNSUPPORTED,
+               "pl_components_u8_i32: 2^31 or more tiles or table entries");
+    // scratch: the int64 coordinate sums in front (8-byte aligned), then link, then the per-block root counts
+    long long *sums = reinterpret_cast<long long *>(scratch);
+    int *link = reinterpret_cast<int *>(sums + (size_t)N * max_objects * 2);
+    int *counts = link + (size_t)N * HW;
+    const int conn8 = connectivity == 8;
+    CtxGuard guard(ctx);
+    cc::tile_kernel<<<(unsigned)tiles, cc::TPB, 0, ctx->stream>>>(m, link, g, conn8, background);
+    const size_t per_image = (size_t)(g.tiles_y - 1) * W + (size_t)(g.tiles_x - 1) * H;      // (below H W)
+    if (per_image)
+        cc::seam_kernel<<<cdiv(N * per_image, cc::TPB), cc::TPB, 0, ctx->stream>>>(m, link, g, conn8, background, (unsigned)per_image,
+                                                                                 (unsigned)(N * per_image));
+    const unsigned nblocks = (unsigned)N * (unsigned)g.blocks;
+    cc::resolve_kernel<<<nblocks, cc::TPB, 0, ctx->stream>>>(link, labels, counts, g);
+    cc::scan_kernel<<<(unsigned)N, cc::SCAN_STEP, 0, ctx->stream>>>(counts, g.blocks, num, max_objects, objects, sums);
+    cc::rank_kernel<<<nblocks, cc::TPB, 0, ctx->stream>>>(labels, counts, g);
+    cc::region_kernel<<<(unsigned)tiles, cc::TPB, 0, ctx->stream>>>(m, link, labels, g, max_objects, objects, sums);
+    if (max_objects)
+        cc::centroid_kernel<<<cdiv((size_t)N * max_objects, cc::TPB), cc::TPB, 0, ctx->stream>>>(objects, sums, centroids,
+                                                                                              (unsigned)N * (unsigned)max_objects);
     PL_LAUNCH_CHECK();
     return PL_OK;
 }

@@ -30,7 +30,7 @@ from . import q4 as _q4
 from .conv_layouts import DIRECT_Q4, IGEMM_NCHW, LAYOUTS, STEM_POOL, STEM_POOL_NCHW, WINO4_Q4, WINO43_Q4, experiment, suffix
 from .layer import layer_map, wrap
 from .plan import compile_front, fuse_upsample_concat, lower
-from .util import BlendGeometry, DetectionSpec, ImageFeed, ImageOutSpec, ImageSpec, LabelSpec, WindowFeed, _Tiling
+from .util import BlendGeometry, DetectionSpec, ImageFeed, ImageOutSpec, ImageSpec, LabelSpec, ObjectSpec, WindowFeed, _Tiling
 from .util import blend_windows as _blend_windows, resize as _resize
 
 STEM_WINO_DEFAULT = 1      # whether the stem + max-pool step takes the F(4,4) form where it applies
@@ -367,7 +367,8 @@ class Net:
         self.algo_misses = 0         # conv algorithm picks that had to be measured (no cached choice)
         self.stream_misses = 0       # stream-plan picks that had to be measured
         self._image_in = {}          # input key (None: the first input) -> util.ImageSpec: uint8 batches that input also takes
-        self._image_out = {}         # output position -> util.ImageOutSpec / util.LabelSpec: that output comes back as uint8
+        self._image_out = {}         # output position -> util.ImageOutSpec / util.LabelSpec: that output comes back as uint8;
+                                     # util.ObjectSpec: as labels, num, objects, centroids in its place
         self._detect = None          # (util.DetectionSpec, positions of its heads or None: every output): they come back as det, num
 
     # ---- loading ----------------------------------------------------------------
@@ -448,6 +449,17 @@ class Net:
         self._image_out[self._unclaimed(index)] = spec
         return self
 
+    def object_output(self, threshold=0.0, connectivity=8, background=0, max_objects=256, index=0):
+        """Output number `index`, float32 (N, C, H, W) scores, comes back as its objects, four arrays in its place: labels int32
+        (N, H, W), num int32 (N,), objects int32 (N, max_objects, 6) rows [class, area, y0, x0, y1, x1] and centroids float32
+        (N, max_objects, 2) rows [cy, cx] -- the connected components (`connectivity` 4 or 8, class `background` left out, -1:
+        none) of `label_output`'s map, numbered per image by the raster position of their first pixel (util.ObjectSpec:
+        pl_labels_f32_u8, then pl_components_u8_i32).  For a one-output net: labels, num, objects, centroids = net(x).  See
+        `image_output`."""
+        spec = ObjectSpec(threshold, connectivity, background, max_objects)
+        self._image_out[self._unclaimed(index)] = spec
+        return self
+
     def float_output(self, index=0):
         """Output number `index` comes back as the float32 tensor again; if it is a head of a detection declaration, so do all
         of that declaration's heads."""
@@ -487,7 +499,8 @@ class Net:
         A uint8 image needs a declared `image_input`, whose k, b and order are used (its `size` and `layout` are not: the image
         is one (H, W, C) array and the working size is `sample`'s); a float32 image is taken as it is.  Returns float32
         (OH, OW, Co); with `label_output` declared on output 0 the uint8 label map (OH, OW); with `image_output` the uint8 image in
-        its layout: (OH, OW, Co') or (Co', OH, OW).  Host image in, host array out; device in, device out.
+        its layout: (OH, OW, Co') or (Co', OH, OW); with `object_output` the objects of the blended label map, labels (OH, OW),
+        num (1,), objects (1, max_objects, 6) and centroids (1, max_objects, 2).  Host image in, host array out; device in, device out.
         Every chunk runs the plan of ONE signature, (batch, Co, h, w): a short last chunk is padded with its last window.
         `progress(i, n)` is called after each chunk with the number of its last window (not at all for a single window).
         Where the working size differs from the image's (`sample`, or an image smaller than the window grown to `glob`), the
@@ -541,7 +554,13 @@ class Net:
                 results.rows(lo, hi).copy_from(out.rows(0, hi - lo))
             if progress is not None and n > 1:
                 progress(hi, n)
-        rst = _blend_windows(results, geo.windows, blend.k, geo.margin, geo.work, out_spec if out_spec is not None else "float")
+        objects = isinstance(out_spec, ObjectSpec)
+        rst = _blend_windows(results, geo.windows, blend.k, geo.margin, geo.work,
+                             out_spec.labels if objects else out_spec if out_spec is not None else "float")
+        if objects:                                      # the objects of the scan, not of the windows: one chain on the whole map
+            labels, num, table, centroids = out_spec.components(rst.reshape((1,) + tuple(rst.shape)))
+            rst = labels.reshape(labels.shape[1:]), num, table, centroids
+            return tuple(a.get() for a in rst) if host_in else rst
         if geo.resampled:
             rst = _resize(rst, geo.back_size(blend.k))
         return rst.get() if host_in else rst
@@ -614,12 +633,15 @@ class Net:
         seq = out if isinstance(out, tuple) else (out,)
         rst = [self._image_out[i].encode(o) if i in self._image_out else
                o.copy() if private and isinstance(o, DeviceArray) and not (heads and i in heads) else o for i, o in enumerate(seq)]
+        # an object output's four arrays take four places
+        places = [r if isinstance(self._image_out.get(i), ObjectSpec) else (r,) for i, r in enumerate(rst)]
         if heads is None:
-            return tuple(rst) if isinstance(out, tuple) else rst[0]
+            flat = tuple(a for p in places for a in p)
+            return flat if isinstance(out, tuple) or len(flat) > 1 else flat[0]
         # det, num where the lowest head was; the heads themselves are not handed back (nor copied)
         first = min(heads)
         det_num = self._detect[0].encode([seq[i] for i in heads])
-        return tuple(r for i, o in enumerate(rst) for r in (det_num if i == first else () if i in heads else (o,)))
+        return tuple(r for i, p in enumerate(places) for r in (det_num if i == first else () if i in heads else p))
 
     def _image_spec(self, pos):
         name = self.input[pos] if pos < len(self.input) else None

@@ -419,6 +419,102 @@ def nms(boxes, scores, classes=None, iou=0.45, max_det=100, floor=-math.inf):
     return _nms_sorted(boxes, classes, scores, n, r, k, float(floor), _f32v(iou), classes is not None, min(int(max_det), k), boxes.ctx)
 
 
+# ---- objects as net output --------------------------------------------------------------------------------------
+def _cc_scratch_bytes(n, h, w, max_objects):
+    """include/planer_hip.h PL_CC_SCRATCH_BYTES"""
+    return n * max_objects * 16 + n * h * w * 4 + n * ((h * w + _lib.CC_BLOCK - 1) // _lib.CC_BLOCK) * 4
+
+
+def _cc_arguments(what, connectivity, background, max_objects):
+    if isinstance(connectivity, bool) or connectivity not in (4, 8):
+        raise ValueError("%s: connectivity is 4 or 8, got %r" % (what, connectivity))
+    if isinstance(background, bool) or not isinstance(background, (int, numpy.integer)) or not -1 <= background <= 255:
+        raise ValueError("%s: background is a class 0 to 255, or -1 for none, got %r" % (what, background))
+    if isinstance(max_objects, bool) or not isinstance(max_objects, (int, numpy.integer)) or not 0 <= max_objects <= _lib.CC_MAX_OBJECTS:
+        raise ValueError("%s: max_objects is 0 to %d, got %r" % (what, _lib.CC_MAX_OBJECTS, max_objects))
+    return int(connectivity), int(background), int(max_objects)
+
+
+def _cc_geometry(what, n, h, w, max_objects):
+    if h * w >= 1 << 31 or n * h * w >= 1 << 31:
+        raise ValueError("%s: %d x %d x %d is 2^31 or more pixels" % (what, n, h, w))
+    if n * max_objects * 6 >= 1 << 31:
+        raise ValueError("%s: %d images x %d rows is 2^31 or more table entries" % (what, n, max_objects))
+
+
+def _components(m, n, h, w, connectivity, background, max_objects, ctx):
+    """pl_components_u8_i32 on the uint8 map `m` (n, h, w): fresh (labels, num, objects, centroids); link, counts and the
+    coordinate sums are scratch from `ctx`'s pool."""
+    labels, num = hip.empty((n, h, w), numpy.int32, ctx=ctx), hip.empty((n,), numpy.int32, ctx=ctx)
+    objects = hip.empty((n, max_objects, 6), numpy.int32, ctx=ctx)
+    centroids = hip.empty((n, max_objects, 2), numpy.float32, ctx=ctx)
+    if n and not h * w:                                   # nothing to label: no launch writes the counts and the table
+        for a in (num, objects, centroids):
+            if a.nbytes:
+                _lib.call("pl_memset", ctx.handle, a.ptr, 0, a.nbytes)
+        return labels, num, objects, centroids
+    scratch = hip.empty(((_cc_scratch_bytes(n, h, w, max_objects) + 7) // 8,), numpy.int64, ctx=ctx)      # (8-byte aligned)
+    _lib.call("pl_components_u8_i32", ctx.handle, m.ptr, n, h, w, connectivity, background, max_objects, scratch.ptr, labels.ptr,
+              num.ptr, objects.ptr if max_objects else None, centroids.ptr if max_objects else None)
+    return labels, num, objects, centroids
+
+
+class ObjectSpec:
+    """A float32 (N, C, H, W) result as objects: `LabelSpec`'s uint8 label map (argmax over the C planes, or x > threshold for
+    C == 1), then its connected components.  An object is a maximal set of pixels of one image with equal class other than
+    `background` (0 to 255; -1: every pixel belongs to an object), joined through 4- or 8-neighbour steps.  Objects are numbered
+    1, 2, ... per image by the raster position of their first pixel; the first `max_objects` of them get a table row.  Host
+    values only."""
+
+    def __init__(self, threshold=0.0, connectivity=8, background=0, max_objects=256):
+        self.labels = LabelSpec(threshold)
+        self.threshold = self.labels.threshold
+        self.connectivity, self.background, self.max_objects = _cc_arguments("object output", connectivity, background, max_objects)
+
+    def geometry(self, shape):
+        """(N, C, H, W) for a float32 result of `shape`, or a ValueError that names what does not fit."""
+        n, c, h, w = shape
+        if not 1 <= c <= 256:
+            raise ValueError("object output: 1 to 256 planes fit a byte, got %d in shape %s" % (c, tuple(shape)))
+        _cc_geometry("object output", n, h, w, self.max_objects)
+        return n, c, h, w
+
+    def check(self, x):
+        self.geometry(_f32_nchw("object output", x))
+
+    def components(self, m, ctx=None):
+        """The four arrays of the uint8 label map `m` (N, H, W), a DeviceArray."""
+        n, h, w = m.shape
+        _cc_geometry("object output", n, h, w, self.max_objects)
+        return _components(m, n, h, w, self.connectivity, self.background, self.max_objects, ctx or m.ctx)
+
+    def encode(self, x, ctx=None):
+        """(labels, num, objects, centroids) of float32 (N, C, H, W) `x`, fresh arrays: labels int32 (N, H, W), 0 on background;
+        num int32 (N,), which may exceed max_objects; objects int32 (N, max_objects, 6), row j = object j + 1 as
+        [class, area, y0, x0, y1, x1] with a half-open box; centroids float32 (N, max_objects, 2) as [cy, cx]; unused rows are
+        zero.  pl_labels_f32_u8 into scratch from `ctx`'s pool, then pl_components_u8_i32; asynchronous on `ctx`'s stream
+        (default: x's), nothing waits for the host."""
+        n, c, h, w = self.geometry(_f32_nchw("object output", x))
+        ctx = ctx or x.ctx
+        m = hip.empty((n, h, w), numpy.uint8, ctx=ctx)
+        _lib.call("pl_labels_f32_u8", ctx.handle, x.ptr, m.ptr, n, c, h, w, self.threshold)
+        return _components(m, n, h, w, self.connectivity, self.background, self.max_objects, ctx)
+
+
+def connected_components(m, connectivity=8, background=0, max_objects=256):
+    """(labels, num, objects, centroids) of a uint8 class map `m`, a DeviceArray (N, H, W) or (H, W): see `ObjectSpec.encode`;
+    for (H, W) labels is (H, W) and the others keep their leading 1.  Asynchronous on m's stream (pl_components_u8_i32)."""
+    if not isinstance(m, DeviceArray):
+        raise TypeError("connected components: expected a uint8 DeviceArray (N, H, W) or (H, W), got %s" % type(m).__name__)
+    if m.dtype != numpy.uint8 or m.ndim not in (2, 3):
+        raise ValueError("connected components: expected a uint8 map (N, H, W) or (H, W), got %s of shape %s" % (m.dtype, tuple(m.shape)))
+    connectivity, background, max_objects = _cc_arguments("connected components", connectivity, background, max_objects)
+    n, h, w = (1,) + tuple(m.shape) if m.ndim == 2 else m.shape
+    _cc_geometry("connected components", n, h, w, max_objects)
+    labels, num, objects, centroids = _components(m, n, h, w, connectivity, background, max_objects, m.ctx)
+    return (labels.reshape(h, w) if m.ndim == 2 else labels), num, objects, centroids
+
+
 # ---- tiled inference around a plan: windows cut and blended in one launch each (DESIGN 4.25) ----------------------------------
 def _window_origins(windows):
     """(r0, c0, h, w) of a list of (row slice, column slice) windows of one size: int32 origin arrays and the extent."""
