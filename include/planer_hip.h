@@ -791,6 +791,43 @@ int pl_nms_f32(pl_ctx *ctx, const float *boxes, const int *classes, const float 
      (size_t)(N) * (((size_t)(H) * (size_t)(W) + PL_CC_BLOCK - 1) / PL_CC_BLOCK) * 4)
 int pl_components_u8_i32(pl_ctx *ctx, const unsigned char *m, int N, int H, int W, int connectivity, int background,
                          int max_objects, void *scratch, int *labels, int *num, int *objects, float *centroids);
+/* ---- keypoints as net output ----
+ * pl_peaks_f32: the local maxima of every plane of the float32 heat maps x (N, K, H, W), counted, and the best max_peaks of each
+ * plane as points.  Pixel p = y W + x of a plane is a peak iff v[p] > threshold holds and, for each of its up to eight
+ * neighbours q inside the same plane (planes and images are no neighbours, nor are a row's last pixel and the next row's first),
+ *   ties == PL_PEAKS_TIES_ALL:   v[p] >= v[q]  (maxpool 3x3 with -inf padding == the map),
+ *   ties == PL_PEAKS_TIES_FIRST: v[p] > v[q] where q < p, v[p] >= v[q] where q > p  (of a plateau, the pixel that comes first).
+ * The comparisons are IEEE float32: a NaN pixel is no peak, a NaN neighbour cancels one, -0.0 ties with +0.0.  A plane's peaks
+ * are ordered by score descending, equal scores (IEEE ==) by ascending p.
+ *   num   int32 (N, K): all peaks of the plane; it may exceed max_peaks.
+ *   peaks float32 (N, K, max_peaks, 3): row j < min(num, max_peaks) is the j-th peak, [x, y, score]; the rows behind are +0.0.
+ *         score carries the pixel's own bits.  x = fl(fl(px + dx) * fl(sx)), y = fl(fl(py + dy) * fl(sy)); px + dx is exact, so
+ *         the product is the single rounding.  refine == PL_PEAKS_REFINE_NONE: dx = dy = 0.  PL_PEAKS_REFINE_QUARTER:
+ *         dx = +0.25 if v[py, px + 1] > v[py, px - 1] holds, -0.25 if < holds, else 0, and 0 at px == 0 or px == W - 1; dy
+ *         likewise along y.
+ * Everything is exact and unique.  Both outputs are written completely and nothing relies on zeroed memory.  Asynchronous on
+ * ctx's stream; two launches (one where H W == 0), no global atomics, no host wait: capturable into a hipGraph.
+ * scratch: PL_PEAKS_SCRATCH_BYTES(N, K, H, W, max_peaks) bytes of the caller's, 8-byte aligned, contents irrelevant.
+ * A workgroup of the first launch takes a PL_PEAKS_TILE_H x PL_PEAKS_TILE_W tile of one plane and hands on its best max_peaks; one
+ * workgroup per plane then merges the tiles' candidates, PL_PEAKS_MERGE_KEYS of them in one sort, more in rounds.
+ * PL_EINVAL: a null pointer, a negative dimension, max_peaks < 1, ties or refine outside their codes, a NaN threshold or stride.
+ * PL_EUNSUPPORTED: max_peaks > PL_PEAKS_MAX_PEAKS, H or W above PL_PEAKS_MAX_EXTENT (below it px + 0.25 is exact in float32),
+ * H W >= 2^31, N K H W >= 2^31, 3 N K max_peaks >= 2^31.  N K == 0: PL_OK, no launch; H W == 0: num = 0 and +0.0 rows.  Every
+ * refusal comes before any launch and leaves the outputs untouched. */
+#define PL_PEAKS_TILE_H 32
+#define PL_PEAKS_TILE_W 64
+#define PL_PEAKS_MAX_PEAKS 256
+#define PL_PEAKS_MERGE_KEYS 2048
+#define PL_PEAKS_MAX_EXTENT 4194304
+#define PL_PEAKS_TIES_ALL 0
+#define PL_PEAKS_TIES_FIRST 1
+#define PL_PEAKS_REFINE_NONE 0
+#define PL_PEAKS_REFINE_QUARTER 1
+#define PL_PEAKS_SCRATCH_BYTES(N, K, H, W, max_peaks)                                                                  \
+    ((size_t)(N) * (size_t)(K) * (((size_t)(H) + PL_PEAKS_TILE_H - 1) / PL_PEAKS_TILE_H) *                             \
+     (((size_t)(W) + PL_PEAKS_TILE_W - 1) / PL_PEAKS_TILE_W) * ((size_t)(max_peaks) * 8 + 4))
+int pl_peaks_f32(pl_ctx *ctx, const float *x, int N, int K, int H, int W, double threshold, int ties, int max_peaks, int refine,
+                 double sy, double sx, void *scratch, float *peaks, int *num);
 /* split-K combine + epilogue (internal to conv, exported for tests) */
 int pl_splitk_reduce_f32(pl_ctx *ctx, const float *ws, int splits, float *y,
                          int N, int C, int inner, const float *bias,

@@ -26,6 +26,12 @@ CC_TILE_H, CC_TILE_W = 32, 64      # include/planer_hip.h PL_CC_TILE_H, PL_CC_TI
 CC_BLOCK = 2048                     # include/planer_hip.h PL_CC_BLOCK
 CC_SCAN_STEP = 1024                 # include/planer_hip.h PL_CC_SCAN_STEP
 CC_MAX_OBJECTS = 65536              # include/planer_hip.h PL_CC_MAX_OBJECTS
+PEAKS_TILE_H, PEAKS_TILE_W = 32, 64  # include/planer_hip.h PL_PEAKS_TILE_H, PL_PEAKS_TILE_W
+PEAKS_MAX_PEAKS = 256               # include/planer_hip.h PL_PEAKS_MAX_PEAKS
+PEAKS_MERGE_KEYS = 2048             # include/planer_hip.h PL_PEAKS_MERGE_KEYS
+PEAKS_MAX_EXTENT = 1 << 22          # include/planer_hip.h PL_PEAKS_MAX_EXTENT
+PEAKS_TIES = {"all": 0, "first": 1}       # include/planer_hip.h PL_PEAKS_TIES_*
+PEAKS_REFINE = {"none": 0, "quarter": 1}  # include/planer_hip.h PL_PEAKS_REFINE_*
 ACT_NONE, ACT_RELU, ACT_LEAKY = 0, 1, 2
 ACT_RES_AFTER = 16
 UNIQUE_ID_BYTES = 128
@@ -202,6 +208,7 @@ SIGNATURES = {
     "pl_yolo_decode_f32": [_P, _P, _I, _I, _I, _I, _I, POINTER(c_float), c_double, c_double, c_double, _I, _I, _P, _P, _P],
     "pl_nms_f32": [_P, _P, _P, _P, _P, _I, _I, _I, c_double, c_double, _I, _I, _P, _P],
     "pl_components_u8_i32": [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
+    "pl_peaks_f32": [_P, _P, _I, _I, _I, _I, c_double, _I, _I, _I, c_double, c_double, _P, _P, _P],
     "pl_tile_accumulate_f32": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I],
     "pl_tile_normalise_f32": [_P, _P, _P, _I, _I, _I],
     "pl_tile_windows_u8_nchw_f32": [_P, _P, _P, _I, _I, _I, _I, POINTER(c_int), _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P,

@@ -12,6 +12,7 @@
 #include "image_output_kernel.h"
 #include "detect_kernel.h"
 #include "components_kernel.h"
+#include "peaks_kernel.h"
 #include "tile_kernel.h"
 
 namespace {
@@ -1073,6 +1074,44 @@ int pl_components_u8_i32(pl_ctx *ctx, const unsigned char *m, int N, int H, int 
     if (max_objects)
         cc::centroid_kernel<<<cdiv((size_t)N * max_objects, cc::TPB), cc::TPB, 0, ctx->stream>>>(objects, sums, centroids,
                                                                                               (unsigned)N * (unsigned)max_objects);
+    PL_LAUNCH_CHECK();
+    return PL_OK;
+}
+
+// float32 heat maps -> peaks per plane (peaks_kernel.h).  Every refusal comes before any launch.
+int pl_peaks_f32(pl_ctx *ctx, const float *x, int N, int K, int H, int W, double threshold, int ties, int max_peaks, int refine,
+                 double sy, double sx, void *scratch, float *peaks, int *num) {
+    namespace pk = peaks;
+    PL_REQUIRE(ctx && x && scratch && peaks && num, PL_EINVAL, "pl_peaks_f32: null argument");
+    PL_REQUIRE(N >= 0 && K >= 0 && H >= 0 && W >= 0 && max_peaks >= 1, PL_EINVAL, "pl_peaks_f32: bad shape (%d, %d, %d, %d), max_peaks = %d",
+               N, K, H, W, max_peaks);
+    PL_REQUIRE(ties == PL_PEAKS_TIES_ALL || ties == PL_PEAKS_TIES_FIRST, PL_EINVAL, "pl_peaks_f32: ties is 0 (all) or 1 (first), got %d", ties);
+    PL_REQUIRE(refine == PL_PEAKS_REFINE_NONE || refine == PL_PEAKS_REFINE_QUARTER, PL_EINVAL,
+               "pl_peaks_f32: refine is 0 (none) or 1 (quarter), got %d", refine);
+    PL_REQUIRE(threshold == threshold && sy == sy && sx == sx, PL_EINVAL, "pl_peaks_f32: threshold or stride is NaN");
+    PL_REQUIRE(max_peaks <= PL_PEAKS_MAX_PEAKS, PL_EUNSUPPORTED, "pl_peaks_f32: at most %d rows per plane, got max_peaks = %d",
+               PL_PEAKS_MAX_PEAKS, max_peaks);
+    PL_REQUIRE(H <= PL_PEAKS_MAX_EXTENT && W <= PL_PEAKS_MAX_EXTENT, PL_EUNSUPPORTED, "pl_peaks_f32: a plane of at most %d x %d, got %d x %d",
+               PL_PEAKS_MAX_EXTENT, PL_PEAKS_MAX_EXTENT, H, W);
+    const size_t HW = (size_t)H * W, planes = (size_t)N * K;
+    PL_REQUIRE(HW < (1ull << 31) && planes < (1ull << 31) && planes * HW < (1ull << 31), PL_EUNSUPPORTED,
+               "pl_peaks_f32: 2^31 or more pixels");
+    PL_REQUIRE(3 * planes * max_peaks < (1ull << 31), PL_EUNSUPPORTED, "pl_peaks_f32: 2^31 or more output floats");
+    if (planes == 0) return PL_OK;
+    pk::Geo g;
+    g.H = H, g.W = W, g.HW = (int)HW;
+    g.tiles_x = (int)cdiv(W, pk::TILE_W), g.tiles_y = (int)cdiv(H, pk::TILE_H);
+    const size_t tiles = planes * g.tiles_x * g.tiles_y;  // (a tile holds a pixel at least: below 2^31)
+    // scratch: every tile's best max_peaks keys in front (8-byte aligned), then every tile's count
+    pk::u64 *keys = reinterpret_cast<pk::u64 *>(scratch);
+    int *counts = reinterpret_cast<int *>(keys + tiles * max_peaks);
+    const int vec = W % 4 == 0 && reinterpret_cast<uintptr_t>(x) % 16 == 0;
+    CtxGuard guard(ctx);
+    if (tiles)
+        pk::tile_kernel<<<(unsigned)tiles, pk::TPB, 0, ctx->stream>>>(x, g, (float)threshold, ties == PL_PEAKS_TIES_FIRST, max_peaks, vec, keys,
+                                                                     counts);
+    pk::merge_kernel<<<(unsigned)planes, pk::TPB, 0, ctx->stream>>>(x, keys, counts, g, max_peaks, refine == PL_PEAKS_REFINE_QUARTER, (float)sy,
+                                                                   (float)sx, peaks, num);
     PL_LAUNCH_CHECK();
     return PL_OK;
 }

@@ -30,7 +30,7 @@ from . import q4 as _q4
 from .conv_layouts import DIRECT_Q4, IGEMM_NCHW, LAYOUTS, STEM_POOL, STEM_POOL_NCHW, WINO4_Q4, WINO43_Q4, experiment, suffix
 from .layer import layer_map, wrap
 from .plan import compile_front, fuse_upsample_concat, lower
-from .util import BlendGeometry, DetectionSpec, ImageFeed, ImageOutSpec, ImageSpec, LabelSpec, ObjectSpec, WindowFeed, _Tiling
+from .util import BlendGeometry, DetectionSpec, ImageFeed, ImageOutSpec, ImageSpec, KeypointSpec, LabelSpec, ObjectSpec, WindowFeed, _Tiling
 from .util import blend_windows as _blend_windows, resize as _resize
 
 STEM_WINO_DEFAULT = 1      # whether the stem + max-pool step takes the F(4,4) form where it applies
@@ -368,7 +368,8 @@ class Net:
         self.stream_misses = 0       # stream-plan picks that had to be measured
         self._image_in = {}          # input key (None: the first input) -> util.ImageSpec: uint8 batches that input also takes
         self._image_out = {}         # output position -> util.ImageOutSpec / util.LabelSpec: that output comes back as uint8;
-                                     # util.ObjectSpec: as labels, num, objects, centroids in its place
+                                     # util.ObjectSpec: as labels, num, objects, centroids in its place; util.KeypointSpec: as
+                                     # peaks, num (a spec's `places` says how many arrays it hands back)
         self._detect = None          # (util.DetectionSpec, positions of its heads or None: every output): they come back as det, num
 
     # ---- loading ----------------------------------------------------------------
@@ -460,6 +461,19 @@ class Net:
         self._image_out[self._unclaimed(index)] = spec
         return self
 
+    def keypoint_output(self, threshold=0.0, ties="all", max_peaks=32, refine="none", stride=1.0, index=0):
+        """Output number `index`, float32 (N, K, H, W) heat maps, comes back as points, two arrays in its place: peaks float32
+        (N, K, max_peaks, 3), per plane the best `max_peaks` 3 x 3 local maxima above `threshold` as rows [x, y, score] by
+        descending score (equal scores by raster position; +0.0 in unused rows), x and y scaled by `stride` (a number or
+        (sy, sx)) and with refine="quarter" moved a quarter pixel towards the higher neighbour; and num int32 (N, K), all peaks
+        of the plane, which may exceed max_peaks.  ties "all" keeps every pixel of a plateau, "first" its first
+        (util.KeypointSpec: pl_peaks_f32).  For a one-output net: peaks, num = net(x).  With max_peaks=1, ties="first",
+        threshold=-inf, row 0 is numpy's argmax of each plane (on planes without NaN, maximum above -inf).  `Net.tiled` refuses
+        a net with this declared.  See `image_output`."""
+        spec = KeypointSpec(threshold, ties, max_peaks, refine, stride)
+        self._image_out[self._unclaimed(index)] = spec
+        return self
+
     def float_output(self, index=0):
         """Output number `index` comes back as the float32 tensor again; if it is a head of a detection declaration, so do all
         of that declaration's heads."""
@@ -501,6 +515,7 @@ class Net:
         (OH, OW, Co); with `label_output` declared on output 0 the uint8 label map (OH, OW); with `image_output` the uint8 image in
         its layout: (OH, OW, Co') or (Co', OH, OW); with `object_output` the objects of the blended label map, labels (OH, OW),
         num (1,), objects (1, max_objects, 6) and centroids (1, max_objects, 2).  Host image in, host array out; device in, device out.
+        A declared `keypoint_output` raises ValueError: peaks of a blended scan are not built.
         Every chunk runs the plan of ONE signature, (batch, Co, h, w): a short last chunk is padded with its last window.
         `progress(i, n)` is called after each chunk with the number of its last window (not at all for a single window).
         Where the working size differs from the image's (`sample`, or an image smaller than the window grown to `glob`), the
@@ -522,6 +537,9 @@ class Net:
             if spec is None:
                 raise ValueError("Net.tiled: a uint8 image needs `image_input` declared (its k, b and order are used)")
         out_spec = self._image_out.get(0)
+        if isinstance(out_spec, KeypointSpec):
+            raise ValueError("Net.tiled: a keypoint output is declared, and the peaks of a blended scan are not built; "
+                             "`float_output` removes the declaration, `util.heatmap_peaks` takes the blended heat maps")
         geo = _Tiling(image.shape[0], image.shape[1], sample, glob, window, margin)
         if geo.resampled and out_spec is not None:
             raise NotImplementedError("Net.tiled: the working size %s differs from the image's %s, so the blended result is resampled "
@@ -633,8 +651,8 @@ class Net:
         seq = out if isinstance(out, tuple) else (out,)
         rst = [self._image_out[i].encode(o) if i in self._image_out else
                o.copy() if private and isinstance(o, DeviceArray) and not (heads and i in heads) else o for i, o in enumerate(seq)]
-        # an object output's four arrays take four places
-        places = [r if isinstance(self._image_out.get(i), ObjectSpec) else (r,) for i, r in enumerate(rst)]
+        # a spec says how many places its arrays take: an object output's four, a keypoint output's two
+        places = [tuple(r) if i in self._image_out and self._image_out[i].places > 1 else (r,) for i, r in enumerate(rst)]
         if heads is None:
             flat = tuple(a for p in places for a in p)
             return flat if isinstance(out, tuple) or len(flat) > 1 else flat[0]

@@ -198,6 +198,8 @@ class ImageOutSpec:
     source plane order[c]; NaN -> 0, clamped to [0, 255], then rounded to nearest even ("nearest") or truncated ("truncate", what
     `astype(uint8)` does).  One value in k and b serves every output channel.  Host values only."""
 
+    places = 1                                            # what `Net` hands back in this output's place: one array
+
     def __init__(self, k, b, layout="nhwc", order=None, rounding="nearest"):
         k, b = numpy.atleast_1d(numpy.asarray(k)), numpy.atleast_1d(numpy.asarray(b))
         if layout not in ("nhwc", "nchw"):
@@ -254,6 +256,8 @@ class ImageOutSpec:
 class LabelSpec:
     """A float32 (N, C, H, W) result as the uint8 label map (N, H, W): numpy's argmax over the C planes (2 to 256), for C == 1
     the comparison x > threshold.  Host values only."""
+
+    places = 1
 
     def __init__(self, threshold=0.0):
         t = float(numpy.float32(threshold))
@@ -466,6 +470,8 @@ class ObjectSpec:
     1, 2, ... per image by the raster position of their first pixel; the first `max_objects` of them get a table row.  Host
     values only."""
 
+    places = 4                                            # labels, num, objects, centroids
+
     def __init__(self, threshold=0.0, connectivity=8, background=0, max_objects=256):
         self.labels = LabelSpec(threshold)
         self.threshold = self.labels.threshold
@@ -513,6 +519,100 @@ def connected_components(m, connectivity=8, background=0, max_objects=256):
     _cc_geometry("connected components", n, h, w, max_objects)
     labels, num, objects, centroids = _components(m, n, h, w, connectivity, background, max_objects, m.ctx)
     return (labels.reshape(h, w) if m.ndim == 2 else labels), num, objects, centroids
+
+
+# ---- keypoints as net output ------------------------------------------------------------------------------------
+def _peaks_scratch_bytes(n, k, h, w, max_peaks):
+    """include/planer_hip.h PL_PEAKS_SCRATCH_BYTES"""
+    return n * k * (-(-h // _lib.PEAKS_TILE_H)) * (-(-w // _lib.PEAKS_TILE_W)) * (max_peaks * 8 + 4)
+
+
+def _peaks_arguments(what, threshold, ties, max_peaks, refine, stride):
+    t = _f32v(threshold)
+    if t != t:
+        raise ValueError("%s: threshold is a number, got %r" % (what, threshold))
+    if ties not in _lib.PEAKS_TIES:
+        raise ValueError("%s: ties is 'all' or 'first', got %r" % (what, ties))
+    if refine not in _lib.PEAKS_REFINE:
+        raise ValueError("%s: refine is 'none' or 'quarter', got %r" % (what, refine))
+    if isinstance(max_peaks, bool) or not isinstance(max_peaks, (int, numpy.integer)) or not 1 <= max_peaks <= _lib.PEAKS_MAX_PEAKS:
+        raise ValueError("%s: max_peaks is 1 to %d, got %r" % (what, _lib.PEAKS_MAX_PEAKS, max_peaks))
+    pair = tuple(stride) if isinstance(stride, (tuple, list)) else (stride, stride)
+    number = (int, float, numpy.integer, numpy.floating)
+    if len(pair) != 2 or any(isinstance(v, bool) or not isinstance(v, number) for v in pair):
+        raise ValueError("%s: stride is a number or an (sy, sx) pair, got %r" % (what, stride))
+    sy, sx = _f32v(pair[0]), _f32v(pair[1])
+    if not (0 < sy < math.inf and 0 < sx < math.inf):
+        raise ValueError("%s: stride is positive and finite, got %r" % (what, stride))
+    return t, ties, int(max_peaks), refine, (sy, sx)
+
+
+def _peaks_geometry(what, n, k, h, w, max_peaks):
+    if h > _lib.PEAKS_MAX_EXTENT or w > _lib.PEAKS_MAX_EXTENT:
+        raise ValueError("%s: a plane of %d x %d is above %d in one extent" % (what, h, w, _lib.PEAKS_MAX_EXTENT))
+    if h * w >= 1 << 31 or n * k >= 1 << 31 or n * k * h * w >= 1 << 31:
+        raise ValueError("%s: %d x %d x %d x %d is 2^31 or more pixels" % (what, n, k, h, w))
+    if 3 * n * k * max_peaks >= 1 << 31:
+        raise ValueError("%s: %d planes x %d rows is 2^31 or more output floats" % (what, n * k, max_peaks))
+
+
+class KeypointSpec:
+    """Float32 heat maps (N, K, H, W) as points: per plane the 3 x 3 local maxima above `threshold`, counted, and the best
+    `max_peaks` (1 to 256) of them as [x, y, score] rows by descending score, equal scores by ascending raster position.  Pixel p
+    is a peak iff v[p] > threshold and, against each of its up to eight neighbours q inside the plane, v[p] >= v[q] (`ties`
+    "all": the `maximum_filter(h, 3) == h` idiom) or v[p] > v[q] for q in front of p in raster order and >= behind ("first": a
+    plateau yields the pixel that comes first).  IEEE float32 comparisons: a NaN is no peak and cancels its neighbours.  `refine`
+    "quarter" moves a peak a quarter pixel towards the higher of its two neighbours along each axis (not on the plane's border);
+    `stride` (a number or (sy, sx), held as float32) scales pixel positions to input pixels in one rounding.
+    With max_peaks=1, ties="first" and threshold=-inf row 0 is numpy's argmax of the plane -- on planes without NaN whose maximum
+    is above -inf, the single-person pose case; numpy's argmax returns a NaN's position, this returns the largest number that no
+    NaN touches, or nothing.  Host values only."""
+
+    places = 2                                            # what `Net` hands back in this output's place: peaks, num
+
+    def __init__(self, threshold=0.0, ties="all", max_peaks=32, refine="none", stride=1.0):
+        self.threshold, self.ties, self.max_peaks, self.refine, self.stride = _peaks_arguments(
+            "keypoint output", threshold, ties, max_peaks, refine, stride)
+
+    def geometry(self, shape):
+        """(N, K, H, W) for a float32 result of `shape`, or a ValueError that names what does not fit."""
+        n, k, h, w = shape
+        _peaks_geometry("keypoint output", n, k, h, w, self.max_peaks)
+        return n, k, h, w
+
+    def check(self, x):
+        self.geometry(_f32_nchw("keypoint output", x))
+
+    def encode(self, x, ctx=None):
+        """(peaks, num) of float32 (N, K, H, W) `x`, fresh arrays: peaks float32 (N, K, max_peaks, 3), row j the plane's j-th
+        peak as [x, y, score] and +0.0 from row min(num, max_peaks) on; num int32 (N, K), all peaks of the plane, which may
+        exceed max_peaks.  pl_peaks_f32 with scratch from `ctx`'s pool; asynchronous on `ctx`'s stream (default: x's), nothing
+        waits for the host."""
+        n, k, h, w = self.geometry(_f32_nchw("keypoint output", x))
+        ctx = ctx or x.ctx
+        peaks, num = hip.empty((n, k, self.max_peaks, 3), numpy.float32, ctx=ctx), hip.empty((n, k), numpy.int32, ctx=ctx)
+        if n * k and not h * w:                               # no pixel: no peak (and x may own no memory to point at)
+            for a in (peaks, num):
+                _lib.call("pl_memset", ctx.handle, a.ptr, 0, a.nbytes)
+        elif n * k:
+            scratch = hip.empty(((_peaks_scratch_bytes(n, k, h, w, self.max_peaks) + 7) // 8,), numpy.int64, ctx=ctx)
+            _lib.call("pl_peaks_f32", ctx.handle, x.ptr, n, k, h, w, self.threshold, _lib.PEAKS_TIES[self.ties], self.max_peaks,
+                      _lib.PEAKS_REFINE[self.refine], self.stride[0], self.stride[1], scratch.ptr, peaks.ptr, num.ptr)
+        return peaks, num
+
+
+def heatmap_peaks(x, threshold=0.0, ties="all", max_peaks=32, refine="none", stride=1.0):
+    """(peaks, num) of float32 heat maps `x`, a DeviceArray (N, K, H, W), (K, H, W) or (H, W): see `KeypointSpec`; peaks is
+    x.shape[:-2] + (max_peaks, 3) and num x.shape[:-2].  Asynchronous on x's stream (pl_peaks_f32)."""
+    if not isinstance(x, DeviceArray):
+        raise TypeError("heat-map peaks: expected a float32 DeviceArray (N, K, H, W), (K, H, W) or (H, W), got %s" % type(x).__name__)
+    if x.dtype != numpy.float32 or x.ndim not in (2, 3, 4):
+        raise ValueError("heat-map peaks: expected float32 maps (N, K, H, W), (K, H, W) or (H, W), got %s of shape %s"
+                         % (x.dtype, tuple(x.shape)))
+    spec = KeypointSpec(threshold, ties, max_peaks, refine, stride)
+    lead = tuple(x.shape[:-2])
+    peaks, num = spec.encode(x.reshape((1,) * (4 - x.ndim) + tuple(x.shape)))
+    return peaks.reshape(lead + (spec.max_peaks, 3)), num.reshape(lead)
 
 
 # ---- tiled inference around a plan: windows cut and blended in one launch each (DESIGN 4.25) ----------------------------------
