@@ -828,6 +828,50 @@ int pl_components_u8_i32(pl_ctx *ctx, const unsigned char *m, int N, int H, int 
      (((size_t)(W) + PL_PEAKS_TILE_W - 1) / PL_PEAKS_TILE_W) * ((size_t)(max_peaks) * 8 + 4))
 int pl_peaks_f32(pl_ctx *ctx, const float *x, int N, int K, int H, int W, double threshold, int ties, int max_peaks, int refine,
                  double sy, double sx, void *scratch, float *peaks, int *num);
+/* ---- instances as net output ----
+ * pl_flow_instances_f32: instance masks by flow following.  Per image three float32 planes over (H, W): a flow field dy, dx and
+ * a probability prob; element (n, plane, y, x) is x[n image_stride + off_plane + (y W + x) pixel_stride]  (NCHW: pixel_stride 1,
+ * off = c H W; an (H, W, C) map: pixel_stride C, off = c).  Pixel p = y W + x.  fl() is one float32 rounding, nothing is
+ * contracted into an FMA.
+ *   1. fg[p] iff prob[p] > (float)level  (a NaN is background).
+ *   2. ay = fl(dy dy), ax = fl(dx dx), l2 = fl(ay + ax).  p moves iff fg[p] and l2 > g2 = fl((float)min_flow (float)min_flow)  (a NaN
+ *      l2 does not move).  sy = sign(dy) if fl(3 ay) >= ax else 0, sx = sign(dx) if fl(3 ax) >= ay else 0: the unit vector's
+ *      components rounded half away from zero, eight directions, total on inf.  t = (clamp(y + sy, 0, H - 1), clamp(x + sx, 0, W - 1)).
+ *      next[p] = t if p moves and fg[t], else p: trajectories never leave the foreground.
+ *   3. end[p] = next applied exactly 2^rounds times (`rounds` pointer doublings, each from one buffer into another): fixed points
+ *      stay, pixels on a cycle land where 2^rounds steps take them.
+ *   4. cnt[q] = the foreground p with end[p] == q; the sink map cnt > 0 is labelled by pl_components_u8_i32 (connectivity 8): S, nS.
+ *   5. The raw instance of a foreground p is S[end[p]], vol[j] its pixel count  (at most PL_FLOW_MAX_RAW(H, W) raw instances).
+ *   6. Instance j is kept iff vol[j] >= min_size; the kept ones are renumbered 1, 2, ... in ascending j.
+ *   masks     int32 (N, H, W): the new number; 0 on background and on dropped instances.
+ *   num       int32 (N): the kept instances of each image; it may exceed max_instances.
+ *   instances int32 (N, max_instances, 5): row j is instance j + 1, [area, y0, x0, y1, x1], the box half-open; rows at and behind
+ *             num are 0.  Instances numbered above max_instances keep their number in masks and have no row.
+ *   centres   float32 (N, max_instances, 2): [cy, cx] = float32(float64(sum of y) / float64(area)); +0.0 in the unused rows.
+ * Everything is exact and unique: nothing depends on the order in which atomics land.  All four outputs are written completely
+ * and nothing relies on zeroed memory.  Asynchronous on ctx's stream; step, ceil(rounds / 2) doublings (two fused per launch),
+ * count, sink map, the components chain, volume, renumber, table and centres (none where max_instances == 0); no host wait, no
+ * host-computed value: capturable into a hipGraph.
+ * scratch: PL_FLOW_SCRATCH_BYTES(N, H, W, max_instances) bytes of the caller's, 8-byte aligned, contents irrelevant: coordinate
+ * sums, two pointer buffers, hit counts, sink labels, the volume table, the sink map and the components chain's scratch.
+ * The table pass takes the components tile, PL_CC_TILE_H x PL_CC_TILE_W pixels per workgroup; one workgroup per image renumbers
+ * PL_FLOW_SCAN_STEP raw instances at a time.
+ * PL_EINVAL: a null pointer (instances / centres may be NULL when max_instances == 0), a negative dimension, rounds, min_size or
+ * max_instances, a stride <= 0, a negative offset, a NaN level or min_flow.  PL_EUNSUPPORTED: H W >= 2^31 or N H W >= 2^31,
+ * rounds > PL_FLOW_MAX_ROUNDS, max_instances > PL_FLOW_MAX_INSTANCES, N max_instances 5 >= 2^31.  N == 0 or H W == 0: PL_OK, no
+ * launch.  Every refusal comes before any launch and leaves the outputs untouched. */
+#define PL_FLOW_SCAN_STEP 1024
+#define PL_FLOW_MAX_ROUNDS 30
+#define PL_FLOW_MAX_INSTANCES 65536
+#define PL_FLOW_ALIGN(bytes) (((size_t)(bytes) + 15) / 16 * 16)
+#define PL_FLOW_MAX_RAW(H, W) ((((size_t)(H) + 1) / 2) * (((size_t)(W) + 1) / 2))
+#define PL_FLOW_SCRATCH_BYTES(N, H, W, max_instances)                                                                  \
+    (16 + (size_t)(N) * (size_t)(max_instances) * 16 + 4 * PL_FLOW_ALIGN((size_t)(N) * (size_t)(H) * (size_t)(W) * 4) + \
+     PL_FLOW_ALIGN((size_t)(N) * PL_FLOW_MAX_RAW(H, W) * 4) + PL_FLOW_ALIGN((size_t)(N) * 4) +                         \
+     PL_FLOW_ALIGN((size_t)(N) * (size_t)(H) * (size_t)(W)) + PL_CC_SCRATCH_BYTES(N, H, W, 0))
+int pl_flow_instances_f32(pl_ctx *ctx, const float *x, int N, int H, int W, long long image_stride, long long pixel_stride,
+                          long long off_dy, long long off_dx, long long off_prob, double level, double min_flow, int rounds,
+                          int min_size, int max_instances, void *scratch, int *masks, int *num, int *instances, float *centres);
 /* split-K combine + epilogue (internal to conv, exported for tests) */
 int pl_splitk_reduce_f32(pl_ctx *ctx, const float *ws, int splits, float *y,
                          int N, int C, int inner, const float *bias,

@@ -32,6 +32,9 @@ PEAKS_MERGE_KEYS = 2048             # include/planer_hip.h PL_PEAKS_MERGE_KEYS
 PEAKS_MAX_EXTENT = 1 << 22          # include/planer_hip.h PL_PEAKS_MAX_EXTENT
 PEAKS_TIES = {"all": 0, "first": 1}       # include/planer_hip.h PL_PEAKS_TIES_*
 PEAKS_REFINE = {"none": 0, "quarter": 1}  # include/planer_hip.h PL_PEAKS_REFINE_*
+FLOW_SCAN_STEP = 1024               # include/planer_hip.h PL_FLOW_SCAN_STEP
+FLOW_MAX_ROUNDS = 30                # include/planer_hip.h PL_FLOW_MAX_ROUNDS
+FLOW_MAX_INSTANCES = 65536          # include/planer_hip.h PL_FLOW_MAX_INSTANCES
 ACT_NONE, ACT_RELU, ACT_LEAKY = 0, 1, 2
 ACT_RES_AFTER = 16
 UNIQUE_ID_BYTES = 128
@@ -209,6 +212,7 @@ SIGNATURES = {
     "pl_nms_f32": [_P, _P, _P, _P, _P, _I, _I, _I, c_double, c_double, _I, _I, _P, _P],
     "pl_components_u8_i32": [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
     "pl_peaks_f32": [_P, _P, _I, _I, _I, _I, c_double, _I, _I, _I, c_double, c_double, _P, _P, _P],
+    "pl_flow_instances_f32": [_P, _P, _I, _I, _I] + [c_longlong] * 5 + [c_double, c_double, _I, _I, _I, _P, _P, _P, _P, _P],
     "pl_tile_accumulate_f32": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I],
     "pl_tile_normalise_f32": [_P, _P, _P, _I, _I, _I],
     "pl_tile_windows_u8_nchw_f32": [_P, _P, _P, _I, _I, _I, _I, POINTER(c_int), _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P,

@@ -12,6 +12,7 @@
 #include "image_output_kernel.h"
 #include "detect_kernel.h"
 #include "components_kernel.h"
+#include "flow_kernel.h"
 #include "peaks_kernel.h"
 #include "tile_kernel.h"
 
@@ -1074,6 +1075,84 @@ int pl_components_u8_i32(pl_ctx *ctx, const unsigned char *m, int N, int H, int 
     if (max_objects)
         cc::centroid_kernel<<<cdiv((size_t)N * max_objects, cc::TPB), cc::TPB, 0, ctx->stream>>>(objects, sums, centroids,
                                                                                               (unsigned)N * (unsigned)max_objects);
+    PL_LAUNCH_CHECK();
+    return PL_OK;
+}
+
+// flow field and probability planes -> instance masks (flow_kernel.h).  Every refusal comes before any launch.
+int pl_flow_instances_f32(pl_ctx *ctx, const float *x, int N, int H, int W, long long image_stride, long long pixel_stride,
+                          long long off_dy, long long off_dx, long long off_prob, double level, double min_flow, int rounds, int min_size,
+                          int max_instances, void *scratch, int *masks, int *num, int *instances, float *centres) {
+    namespace fl = flow;
+    PL_REQUIRE(ctx && x && scratch && masks && num && (max_instances <= 0 || (instances && centres)), PL_EINVAL,
+               "pl_flow_instances_f32: null argument");
+    PL_REQUIRE(N >= 0 && H >= 0 && W >= 0 && max_instances >= 0, PL_EINVAL, "pl_flow_instances_f32: bad shape (%d, %d, %d), max_instances = %d",
+               N, H, W, max_instances);
+    PL_REQUIRE(rounds >= 0 && min_size >= 0, PL_EINVAL, "pl_flow_instances_f32: rounds = %d and min_size = %d are counts >= 0", rounds,
+               min_size);
+    PL_REQUIRE(image_stride > 0 && pixel_stride > 0 && off_dy >= 0 && off_dx >= 0 && off_prob >= 0, PL_EINVAL,
+               "pl_flow_instances_f32: strides are positive and plane offsets are not negative");
+    PL_REQUIRE(level == level && min_flow == min_flow, PL_EINVAL, "pl_flow_instances_f32: level or min_flow is NaN");
+    const size_t HW = (size_t)H * W;
+    PL_REQUIRE(HW < (1ull << 31) && (size_t)N * HW < (1ull << 31), PL_EUNSUPPORTED, "pl_flow_instances_f32: 2^31 or more pixels");
+    PL_REQUIRE(rounds <= PL_FLOW_MAX_ROUNDS, PL_EUNSUPPORTED, "pl_flow_instances_f32: at most %d pointer doublings, got rounds = %d",
+               PL_FLOW_MAX_ROUNDS, rounds);
+    PL_REQUIRE(max_instances <= PL_FLOW_MAX_INSTANCES, PL_EUNSUPPORTED,
+               "pl_flow_instances_f32: at most %d table rows per image, got max_instances = %d", PL_FLOW_MAX_INSTANCES, max_instances);
+    PL_REQUIRE((size_t)N * max_instances * 5 < (1ull << 31), PL_EUNSUPPORTED, "pl_flow_instances_f32: 2^31 or more table entries");
+    if (N == 0 || HW == 0) return PL_OK;
+    fl::Geo g;
+    g.N = N, g.H = H, g.W = W, g.HW = (int)HW, g.total = (int)(N * HW);
+    g.tiles_x = (int)cdiv(W, fl::TILE_W), g.tiles_y = (int)cdiv(H, fl::TILE_H);
+    g.max_raw = (int)PL_FLOW_MAX_RAW(H, W);
+    g.image_stride = image_stride, g.pixel_stride = pixel_stride, g.off_dy = off_dy, g.off_dx = off_dx, g.off_prob = off_prob;
+    // scratch, from its first 16-byte boundary on: the int64 coordinate sums, two pointer buffers, the hit counts, the sink
+    // labels, the volume table, the sink regions per image, the sink map, and the components chain's own scratch
+    char *at = reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(scratch) + 15) / 16 * 16);
+    auto take = [&at](size_t bytes) {
+        char *p = at;
+        at += PL_FLOW_ALIGN(bytes);
+        return p;
+    };
+    const size_t total = (size_t)g.total;
+    long long *sums = reinterpret_cast<long long *>(take((size_t)N * max_instances * 16));
+    int *buf[2] = {reinterpret_cast<int *>(take(total * 4)), reinterpret_cast<int *>(take(total * 4))};
+    int *cnt = reinterpret_cast<int *>(take(total * 4)), *S = reinterpret_cast<int *>(take(total * 4));
+    int *vol = reinterpret_cast<int *>(take((size_t)N * g.max_raw * 4)), *raw_num = reinterpret_cast<int *>(take((size_t)N * 4));
+    unsigned char *sink = reinterpret_cast<unsigned char *>(take(total));
+    void *cc_scratch = at;
+    const float lv = (float)level, mf = (float)min_flow, g2 = mf * mf;      // (one product: nothing to contract)
+    const bool vec = pixel_stride == 1 && W % 4 == 0 && image_stride % 4 == 0 && off_dy % 4 == 0 && off_dx % 4 == 0 && off_prob % 4 == 0 &&
+                     reinterpret_cast<uintptr_t>(x) % 16 == 0;
+    const unsigned quads = cdiv(total, (size_t)fl::QUAD * fl::TPB), pixels = cdiv(total, fl::TPB);
+    CtxGuard guard(ctx);
+    if (vec)
+        fl::step_kernel<true><<<quads, fl::TPB, 0, ctx->stream>>>(x, g, lv, g2, buf[0], cnt, vol, N * g.max_raw);
+    else
+        fl::step_kernel<false><<<quads, fl::TPB, 0, ctx->stream>>>(x, g, lv, g2, buf[0], cnt, vol, N * g.max_raw);
+    int cur = 0;
+    for (int r = 0; r < rounds; cur ^= 1) {
+        if (rounds - r >= 2) {
+            fl::double_kernel<true><<<quads, fl::TPB, 0, ctx->stream>>>(buf[cur], buf[cur ^ 1], g.total);
+            r += 2;
+        } else {
+            fl::double_kernel<false><<<quads, fl::TPB, 0, ctx->stream>>>(buf[cur], buf[cur ^ 1], g.total);
+            r += 1;
+        }
+    }
+    const int *end = buf[cur];
+    fl::count_kernel<<<pixels, fl::TPB, 0, ctx->stream>>>(end, cnt, g.total);
+    fl::sink_kernel<<<quads, fl::TPB, 0, ctx->stream>>>(cnt, sink, g.total);
+    PL_LAUNCH_CHECK();
+    const int rc = pl_components_u8_i32(ctx, sink, N, H, W, 8, 0, 0, cc_scratch, S, raw_num, nullptr, nullptr);
+    if (rc != PL_OK) return rc;
+    fl::volume_kernel<<<pixels, fl::TPB, 0, ctx->stream>>>(cnt, S, vol, g);
+    fl::renumber_kernel<<<(unsigned)N, fl::SCAN_STEP, 0, ctx->stream>>>(vol, raw_num, g.max_raw, min_size, num, max_instances, instances, sums);
+    const size_t tiles = (size_t)N * g.tiles_x * g.tiles_y;                  // (below 2^31: pl_components_u8_i32 took them)
+    fl::table_kernel<<<(unsigned)tiles, fl::TPB, 0, ctx->stream>>>(end, S, vol, masks, g, max_instances, instances, sums);
+    if (max_instances)
+        fl::centre_kernel<<<cdiv((size_t)N * max_instances, fl::TPB), fl::TPB, 0, ctx->stream>>>(instances, sums, centres,
+                                                                                            (unsigned)N * (unsigned)max_instances);
     PL_LAUNCH_CHECK();
     return PL_OK;
 }

@@ -30,7 +30,7 @@ from . import q4 as _q4
 from .conv_layouts import DIRECT_Q4, IGEMM_NCHW, LAYOUTS, STEM_POOL, STEM_POOL_NCHW, WINO4_Q4, WINO43_Q4, experiment, suffix
 from .layer import layer_map, wrap
 from .plan import compile_front, fuse_upsample_concat, lower
-from .util import BlendGeometry, DetectionSpec, ImageFeed, ImageOutSpec, ImageSpec, KeypointSpec, LabelSpec, ObjectSpec, WindowFeed, _Tiling
+from .util import BlendGeometry, DetectionSpec, FlowSpec, ImageFeed, ImageOutSpec, ImageSpec, KeypointSpec, LabelSpec, ObjectSpec, WindowFeed, _Tiling
 from .util import blend_windows as _blend_windows, resize as _resize
 
 STEM_WINO_DEFAULT = 1      # whether the stem + max-pool step takes the F(4,4) form where it applies
@@ -369,7 +369,8 @@ class Net:
         self._image_in = {}          # input key (None: the first input) -> util.ImageSpec: uint8 batches that input also takes
         self._image_out = {}         # output position -> util.ImageOutSpec / util.LabelSpec: that output comes back as uint8;
                                      # util.ObjectSpec: as labels, num, objects, centroids in its place; util.KeypointSpec: as
-                                     # peaks, num (a spec's `places` says how many arrays it hands back)
+                                     # peaks, num; util.FlowSpec: as masks, num, instances, centres (a spec's `places` says how
+                                     # many arrays it hands back)
         self._detect = None          # (util.DetectionSpec, positions of its heads or None: every output): they come back as det, num
 
     # ---- loading ----------------------------------------------------------------
@@ -474,6 +475,18 @@ class Net:
         self._image_out[self._unclaimed(index)] = spec
         return self
 
+    def flow_output(self, level=0.0, min_flow=0.0, rounds=10, min_size=15, max_instances=256, planes=(0, 1, 2), index=0):
+        """Output number `index`, float32 (N, C, H, W) with a flow field (dy, dx) and a probability in the planes `planes`, comes
+        back as instance masks by flow following, four arrays in its place: masks int32 (N, H, W), num int32 (N,), instances
+        int32 (N, max_instances, 5) rows [area, y0, x0, y1, x1] and centres float32 (N, max_instances, 2) rows [cy, cx].  A pixel
+        is foreground iff prob > level; it follows the flow (where longer than min_flow) for 2^rounds steps inside the
+        foreground, and the pixels that meet at one 8-connected sink region are one instance; instances below `min_size`
+        pixels are dropped (util.FlowSpec: pl_flow_instances_f32).  For a one-output net: masks, num, instances, centres =
+        net(x).  `Net.tiled` follows the flows of the blended scan.  See `image_output`."""
+        spec = FlowSpec(level, min_flow, rounds, min_size, max_instances, planes)
+        self._image_out[self._unclaimed(index)] = spec
+        return self
+
     def float_output(self, index=0):
         """Output number `index` comes back as the float32 tensor again; if it is a head of a detection declaration, so do all
         of that declaration's heads."""
@@ -514,7 +527,9 @@ class Net:
         is one (H, W, C) array and the working size is `sample`'s); a float32 image is taken as it is.  Returns float32
         (OH, OW, Co); with `label_output` declared on output 0 the uint8 label map (OH, OW); with `image_output` the uint8 image in
         its layout: (OH, OW, Co') or (Co', OH, OW); with `object_output` the objects of the blended label map, labels (OH, OW),
-        num (1,), objects (1, max_objects, 6) and centroids (1, max_objects, 2).  Host image in, host array out; device in, device out.
+        num (1,), objects (1, max_objects, 6) and centroids (1, max_objects, 2); with `flow_output` the instances of the blended flow and
+        probability planes (the windows are blended as floats, then one chain follows the whole map), masks (OH, OW), num (1,),
+        instances (1, max_instances, 5) and centres (1, max_instances, 2).  Host image in, host array out; device in, device out.
         A declared `keypoint_output` raises ValueError: peaks of a blended scan are not built.
         Every chunk runs the plan of ONE signature, (batch, Co, h, w): a short last chunk is padded with its last window.
         `progress(i, n)` is called after each chunk with the number of its last window (not at all for a single window).
@@ -572,9 +587,13 @@ class Net:
                 results.rows(lo, hi).copy_from(out.rows(0, hi - lo))
             if progress is not None and n > 1:
                 progress(hi, n)
-        objects = isinstance(out_spec, ObjectSpec)
+        objects, flows = isinstance(out_spec, ObjectSpec), isinstance(out_spec, FlowSpec)
         rst = _blend_windows(results, geo.windows, blend.k, geo.margin, geo.work,
-                             out_spec.labels if objects else out_spec if out_spec is not None else "float")
+                             out_spec.labels if objects else "float" if flows or out_spec is None else out_spec)
+        if flows:                                        # the instances of the scan: one chain on the blended (OH, OW, C) map
+            masks, num, table, centres = out_spec.encode_hwc(rst)
+            rst = masks.reshape(masks.shape[1:]), num, table, centres
+            return tuple(a.get() for a in rst) if host_in else rst
         if objects:                                      # the objects of the scan, not of the windows: one chain on the whole map
             labels, num, table, centroids = out_spec.components(rst.reshape((1,) + tuple(rst.shape)))
             rst = labels.reshape(labels.shape[1:]), num, table, centroids

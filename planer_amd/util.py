@@ -615,6 +615,116 @@ def heatmap_peaks(x, threshold=0.0, ties="all", max_peaks=32, refine="none", str
     return peaks.reshape(lead + (spec.max_peaks, 3)), num.reshape(lead)
 
 
+# ---- instances as net output ------------------------------------------------------------------------------------
+def _flow_scratch_bytes(n, h, w, max_instances):
+    """include/planer_hip.h PL_FLOW_SCRATCH_BYTES"""
+    def align(b):
+        return (b + 15) // 16 * 16
+    return (16 + n * max_instances * 16 + 4 * align(n * h * w * 4) + align(n * ((h + 1) // 2) * ((w + 1) // 2) * 4) + align(n * 4)
+            + align(n * h * w) + _cc_scratch_bytes(n, h, w, 0))
+
+
+def _flow_arguments(what, level, min_flow, rounds, min_size, max_instances, planes):
+    number = (int, float, numpy.integer, numpy.floating)
+    for name, v in (("level", level), ("min_flow", min_flow)):
+        if isinstance(v, bool) or not isinstance(v, number) or v != v:
+            raise ValueError("%s: %s is a number, got %r" % (what, name, v))
+    for name, v, top in (("rounds", rounds, _lib.FLOW_MAX_ROUNDS), ("min_size", min_size, (1 << 31) - 1),
+                         ("max_instances", max_instances, _lib.FLOW_MAX_INSTANCES)):
+        if isinstance(v, bool) or not isinstance(v, (int, numpy.integer)) or not 0 <= v <= top:
+            raise ValueError("%s: %s is 0 to %d, got %r" % (what, name, top, v))
+    try:
+        planes = tuple(planes)
+    except TypeError:
+        planes = ()
+    if len(planes) != 3 or any(isinstance(p, bool) or not isinstance(p, (int, numpy.integer)) or p < 0 for p in planes) \
+            or len(set(planes)) != 3:
+        raise ValueError("%s: planes names three distinct planes (dy, dx, prob), got %r" % (what, planes))
+    return _f32v(level), _f32v(min_flow), int(rounds), int(min_size), int(max_instances), tuple(int(p) for p in planes)
+
+
+def _flow_geometry(what, n, h, w, max_instances):
+    if h * w >= 1 << 31 or n * h * w >= 1 << 31:
+        raise ValueError("%s: %d x %d x %d is 2^31 or more pixels" % (what, n, h, w))
+    if n * max_instances * 5 >= 1 << 31:
+        raise ValueError("%s: %d images x %d rows is 2^31 or more table entries" % (what, n, max_instances))
+
+
+class FlowSpec:
+    """A float32 (N, C, H, W) result as instance masks by flow following (cellpose's product): planes[0], planes[1] are a flow
+    field (dy, dx), planes[2] a probability.  A pixel is foreground iff prob > level.  A foreground pixel whose flow is longer
+    than min_flow points at the neighbour in the flow's direction (eight directions, clamped at the border) if that neighbour is
+    foreground, else at itself; every pixel follows the pointers for exactly 2^rounds steps; the pixels that were arrived at form
+    the sink map, whose 8-connected regions number the raw instances (by the raster position of a region's first pixel); raw
+    instances of fewer than `min_size` pixels are dropped and the rest renumbered 1, 2, ... in the same order.  The first
+    `max_instances` of them get a table row.  Everything behind one float32 decision per pixel is integer arithmetic: the result is
+    exact (include/planer_hip.h states the rule operation by operation).  level and min_flow are rounded to float32.  Host
+    values only."""
+
+    places = 4                                            # masks, num, instances, centres
+
+    def __init__(self, level=0.0, min_flow=0.0, rounds=10, min_size=15, max_instances=256, planes=(0, 1, 2)):
+        self.level, self.min_flow, self.rounds, self.min_size, self.max_instances, self.planes = _flow_arguments(
+            "flow output", level, min_flow, rounds, min_size, max_instances, planes)
+
+    def geometry(self, shape):
+        """(N, C, H, W) for a float32 result of `shape`, or a ValueError that names what does not fit."""
+        n, c, h, w = shape
+        if c < 3 or max(self.planes) >= c:
+            raise ValueError("flow output: planes %s of a result with %d planes, shape %s" % (self.planes, c, tuple(shape)))
+        _flow_geometry("flow output", n, h, w, self.max_instances)
+        return n, c, h, w
+
+    def check(self, x):
+        self.geometry(_f32_nchw("flow output", x))
+
+    def follow(self, x, n, h, w, image_stride, pixel_stride, offsets, ctx):
+        """pl_flow_instances_f32 on the float32 DeviceArray `x`, element (i, plane, y, x) at i image_stride + offsets[plane] +
+        (y w + x) pixel_stride: fresh (masks, num, instances, centres); everything else is scratch from `ctx`'s pool."""
+        m = self.max_instances
+        _flow_geometry("flow output", n, h, w, m)
+        masks, num = hip.empty((n, h, w), numpy.int32, ctx=ctx), hip.empty((n,), numpy.int32, ctx=ctx)
+        instances, centres = hip.empty((n, m, 5), numpy.int32, ctx=ctx), hip.empty((n, m, 2), numpy.float32, ctx=ctx)
+        if n and not h * w:                                   # no pixel: no instance (and x may own no memory to point at)
+            for a in (num, instances, centres):
+                if a.nbytes:
+                    _lib.call("pl_memset", ctx.handle, a.ptr, 0, a.nbytes)
+        elif n:
+            scratch = hip.empty(((_flow_scratch_bytes(n, h, w, m) + 7) // 8,), numpy.int64, ctx=ctx)      # (8-byte aligned)
+            _lib.call("pl_flow_instances_f32", ctx.handle, x.ptr, n, h, w, image_stride, pixel_stride, offsets[0], offsets[1], offsets[2],
+                      self.level, self.min_flow, self.rounds, self.min_size, m, scratch.ptr, masks.ptr, num.ptr,
+                      instances.ptr if m else None, centres.ptr if m else None)
+        return masks, num, instances, centres
+
+    def encode(self, x, ctx=None):
+        """(masks, num, instances, centres) of float32 (N, C, H, W) `x`, fresh arrays: masks int32 (N, H, W), 0 on background
+        and on dropped instances; num int32 (N,), which may exceed max_instances; instances int32 (N, max_instances, 5), row j =
+        instance j + 1 as [area, y0, x0, y1, x1] with a half-open box; centres float32 (N, max_instances, 2) as [cy, cx]; unused
+        rows are zero.  pl_flow_instances_f32 with scratch from `ctx`'s pool; asynchronous on `ctx`'s stream (default: x's),
+        nothing waits for the host."""
+        n, c, h, w = self.geometry(_f32_nchw("flow output", x))
+        return self.follow(x, n, h, w, c * h * w, 1, [p * h * w for p in self.planes], ctx or x.ctx)
+
+    def encode_hwc(self, x, ctx=None):
+        """The same of ONE float32 map (H, W, C), `Net.tiled`'s blended result: (masks (1, H, W), num (1,), ...)."""
+        h, w, c = x.shape
+        self.geometry((1, c, h, w))
+        return self.follow(x, 1, h, w, max(h * w * c, 1), c, list(self.planes), ctx or x.ctx)
+
+
+def follow_flows(x, level=0.0, min_flow=0.0, rounds=10, min_size=15, max_instances=256, planes=(0, 1, 2)):
+    """(masks, num, instances, centres) of float32 flow and probability planes `x`, a DeviceArray (N, C, H, W) or (C, H, W): see
+    `FlowSpec`; for (C, H, W) masks is (H, W) and the others keep their leading 1.  Asynchronous on x's stream
+    (pl_flow_instances_f32)."""
+    if not isinstance(x, DeviceArray):
+        raise TypeError("flow following: expected a float32 DeviceArray (N, C, H, W) or (C, H, W), got %s" % type(x).__name__)
+    if x.dtype != numpy.float32 or x.ndim not in (3, 4):
+        raise ValueError("flow following: expected float32 planes (N, C, H, W) or (C, H, W), got %s of shape %s" % (x.dtype, tuple(x.shape)))
+    spec = FlowSpec(level, min_flow, rounds, min_size, max_instances, planes)
+    masks, num, instances, centres = spec.encode(x.reshape((1,) * (4 - x.ndim) + tuple(x.shape)))
+    return (masks.reshape(masks.shape[1:]) if x.ndim == 3 else masks), num, instances, centres
+
+
 # ---- tiled inference around a plan: windows cut and blended in one launch each (DESIGN 4.25) ----------------------------------
 def _window_origins(windows):
     """(r0, c0, h, w) of a list of (row slice, column slice) windows of one size: int32 origin arrays and the extent."""
