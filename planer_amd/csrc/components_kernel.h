@@ -19,44 +19,37 @@
 //                 initialised (rows at and behind num: zeros, for good).
 // rank_kernel     a root gets its number, offset + roots in front of it inside the block + 1, in `labels`.
 // region_kernel   one workgroup per tile: a pixel takes its root's number (labels is final behind this), and area, box and
-//                 coordinate sums of the objects numbered up to max_objects are accumulated tile-relative in an LDS hash table
-//                 keyed by the number, then flushed: one set of global integer atomics per (tile, object).  A wave whose pixels
-//                 in the image all carry one number adds them with one lane.  The root's thread stores the class.
+//                 coordinate sums of the objects numbered up to max_objects go through the tile's table (region_table.h) into
+//                 the rows [class, area, y0, x0, y1, x1].  The root's thread stores the class.
 // centroid_kernel float32(float64(sum) / float64(area)) per row, +0.0 in the unused rows.
 //
 // union (Playne & Hawick's atomicMin form): find both roots; atomicMin on the larger root's word towards the smaller; if the word
 // no longer held that root, go on from the value the atomic returned (a word that was lowered past its former parent has cut
 // that parent off: the next round joins it again).  The result is the unique partition, whatever order the atomics land in.
 #pragma once
-#include <climits>
-
 #include "common.h"
 #include "device_utils.h"
+#include "region_table.h"
 
 namespace components {
 
-constexpr int TPB = PL_STREAM_TPB;
-constexpr int TILE_H = PL_CC_TILE_H, TILE_W = PL_CC_TILE_W, TILE_PX = TILE_H * TILE_W;
-constexpr int PER_THREAD = TILE_PX / TPB;
+using namespace regions;                                  // TPB, the tile, RLX, AGENT
+
 constexpr int BLOCK = PL_CC_BLOCK;                        // raster-consecutive pixels behind one root count
 constexpr int BLOCK_PER_THREAD = BLOCK / TPB;
 constexpr int SCAN_STEP = PL_CC_SCAN_STEP;                // counts one step of scan_kernel's workgroup takes
-constexpr int SLOTS = TILE_PX;                            // a tile holds at most TILE_PX objects: the table never overflows
-static_assert(TILE_W == 64, "a wave takes one row of a tile");
-static_assert(TILE_PX % TPB == 0 && BLOCK % TPB == 0 && (SLOTS & (SLOTS - 1)) == 0, "whole passes");
-static_assert(TILE_PX <= 4096 && TILE_W * TILE_PX < (1 << 20), "region_kernel packs area (12 bits) over the x sum (20 bits)");
-
-#define PL_CC_RLX __ATOMIC_RELAXED
+constexpr int ROW = 6, AREA = 1;                          // a table row: [class, area, y0, x0, y1, x1]
+static_assert(BLOCK % TPB == 0, "whole passes");
 
 // ---- union-find on an int array; SCOPE is the HIP memory scope of every access ----
-template <int SCOPE> __device__ __forceinline__ int uf_load(int *a, int i) { return __hip_atomic_load(a + i, PL_CC_RLX, SCOPE); }
+template <int SCOPE> __device__ __forceinline__ int uf_load(int *a, int i) { return __hip_atomic_load(a + i, RLX, SCOPE); }
 
 // the root of x; words passed on the way are lowered to their grandparent (path halving)
 template <int SCOPE> __device__ __forceinline__ int uf_find(int *a, int x) {
     int p = uf_load<SCOPE>(a, x);
     while (p != x) {
         const int g = uf_load<SCOPE>(a, p);
-        if (g != p) __hip_atomic_fetch_min(a + x, g, PL_CC_RLX, SCOPE);
+        if (g != p) __hip_atomic_fetch_min(a + x, g, RLX, SCOPE);
         x = p;
         p = g;
     }
@@ -73,13 +66,13 @@ template <int SCOPE> __device__ __forceinline__ void uf_union(int *a, int x, int
             x = y;
             y = t;
         }
-        const int old = __hip_atomic_fetch_min(a + x, y, PL_CC_RLX, SCOPE);
+        const int old = __hip_atomic_fetch_min(a + x, y, RLX, SCOPE);
         if (old == x) return;
         x = old;
     }
 }
 
-constexpr int WG = __HIP_MEMORY_SCOPE_WORKGROUP, AGENT = __HIP_MEMORY_SCOPE_AGENT;
+constexpr int WG = __HIP_MEMORY_SCOPE_WORKGROUP;
 
 struct Geo {
     int H, W, HW, tiles_x, tiles_y, blocks;               // blocks = ceil(HW / BLOCK)
@@ -203,38 +196,11 @@ __global__ void __launch_bounds__(TPB) resolve_kernel(int *link, int *labels, in
 // grid = N, SCAN_STEP threads.  counts of image n -> exclusive offsets in place; num[n]; table rows of image n.
 __global__ void __launch_bounds__(SCAN_STEP) scan_kernel(int *counts, int blocks, int *num, int max_objects, int *objects,
                                                          long long *sums) {
-    __shared__ int wtot[SCAN_STEP / 64];
-    __shared__ int carry_s;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     int *c = counts + (size_t)blockIdx.x * blocks;
-    if (t == 0) carry_s = 0;
-    __syncthreads();
-    for (int b0 = 0; b0 < blocks; b0 += SCAN_STEP) {
-        const int i = b0 + t;
-        const int v = i < blocks ? c[i] : 0;
-        int inc = v;
-        for (int o = 1; o < 64; o <<= 1) {
-            const int u = __shfl_up(inc, o);
-            if (lane >= o) inc += u;
-        }
-        if (lane == 63) wtot[wave] = inc;
-        __syncthreads();
-        int before = carry_s;
-        for (int w = 0; w < wave; ++w) before += wtot[w];
-        if (i < blocks) c[i] = before + inc - v;
-        __syncthreads();
-        if (t == SCAN_STEP - 1) carry_s = before + inc;
-        __syncthreads();
-    }
-    const int total = carry_s;
-    if (t == 0) num[blockIdx.x] = total;
-    for (int j = t; j < max_objects; j += SCAN_STEP) {
-        const size_t row = (size_t)blockIdx.x * max_objects + j;
-        int *o = objects + row * 6;
-        const bool used = j < total;
-        o[0] = 0, o[1] = 0, o[2] = used ? INT_MAX : 0, o[3] = used ? INT_MAX : 0, o[4] = 0, o[5] = 0;
-        sums[row * 2] = 0, sums[row * 2 + 1] = 0;
-    }
+    const int total = carry_scan<SCAN_STEP>(blocks, [c](int i) { return c[i]; }, [c](int i, int v, int inc) { c[i] = inc - v; });
+    if (threadIdx.x == 0) num[blockIdx.x] = total;
+    const size_t row = (size_t)blockIdx.x * max_objects;
+    init_rows<ROW, AREA, SCAN_STEP>(objects + row * ROW, sums + row * 2, max_objects, total);
 }
 
 // grid = N * blocks; a thread takes BLOCK_PER_THREAD consecutive pixels.  A root (labels[p] == p) gets its number.
@@ -251,11 +217,7 @@ __global__ void __launch_bounds__(TPB) rank_kernel(int *labels, const int *offse
         c += f[e];
     }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int inc = c;
-    for (int o = 1; o < 64; o <<= 1) {
-        const int u = __shfl_up(inc, o);
-        if (lane >= o) inc += u;
-    }
+    const int inc = wave_inclusive_sum(c, lane);
     if (lane == 63) wsum[wave] = inc;
     __syncthreads();
     int pos = offsets[(size_t)n * g.blocks + b] + inc - c;
@@ -269,14 +231,13 @@ __global__ void __launch_bounds__(TPB) rank_kernel(int *labels, const int *offse
 // thread of this launch writes, and root indices elsewhere, which only their own thread reads and replaces.
 __global__ void __launch_bounds__(TPB) region_kernel(const unsigned char *m, const int *link, int *labels, Geo g, int max_objects,
                                                      int *objects, long long *sums) {
-    __shared__ int key[SLOTS], y_lo[SLOTS], x_lo[SLOTS], y_hi[SLOTS], x_hi[SLOTS];
-    __shared__ unsigned area_sx[SLOTS], sy[SLOTS];        // area << 20 | sum of x; sum of y (tile-relative)
+    __shared__ Tile table;
     const int t = threadIdx.x, lane = t & 63;
     const unsigned tile = blockIdx.x % (unsigned)(g.tiles_x * g.tiles_y), n = blockIdx.x / (unsigned)(g.tiles_x * g.tiles_y);
     const int y0 = (int)(tile / (unsigned)g.tiles_x) * TILE_H, x0 = (int)(tile % (unsigned)g.tiles_x) * TILE_W;
     const int *li = link + (size_t)n * g.HW;
     int *la = labels + (size_t)n * g.HW;
-    for (int s = t; s < SLOTS; s += TPB) key[s] = 0, area_sx[s] = 0u, sy[s] = 0u, y_lo[s] = INT_MAX, x_lo[s] = INT_MAX, y_hi[s] = -1, x_hi[s] = -1;
+    table.clear();
     __syncthreads();
     const int inside = min(TILE_W, g.W - x0);             // columns of the tile inside the image: lanes [0, inside)
     for (int k = 0; k < PER_THREAD; ++k) {
@@ -287,7 +248,7 @@ __global__ void __launch_bounds__(TPB) region_kernel(const unsigned char *m, con
             const int p = y * g.W + x, l = li[p];
             if (l == p) {
                 number = la[p];
-                if (number <= max_objects) objects[((size_t)n * max_objects + (number - 1)) * 6] = m[(size_t)n * g.HW + p];
+                if (number <= max_objects) objects[((size_t)n * max_objects + (number - 1)) * ROW] = m[(size_t)n * g.HW + p];
             } else if (l >= 0) {
                 number = la[la[p]];
                 la[p] = number;
@@ -296,50 +257,18 @@ __global__ void __launch_bounds__(TPB) region_kernel(const unsigned char *m, con
             }
         }
         if (number > max_objects) number = 0;             // numbered, and without a row
-        const int first = __shfl(number, 0);
-        const bool one = first > 0 && __all(lane >= inside || number == first);
-        if (!one && number == 0) continue;
-        if (one && lane != 0) continue;
-        int s = (int)(((unsigned)number * 2654435761u) >> 16) & (SLOTS - 1);
-        for (;;) {
-            const int old = atomicCAS(&key[s], 0, number);
-            if (old == 0 || old == number) break;
-            s = (s + 1) & (SLOTS - 1);
-        }
-        const unsigned cnt = one ? (unsigned)inside : 1u, lx = (unsigned)lane;
-        atomicAdd(&area_sx[s], one ? (cnt << 20) | (cnt * (cnt - 1) / 2) : (1u << 20) | lx);
-        atomicAdd(&sy[s], cnt * (unsigned)ly);
-        atomicMin(&y_lo[s], ly), atomicMax(&y_hi[s], ly);
-        atomicMin(&x_lo[s], lane), atomicMax(&x_hi[s], one ? inside - 1 : lane);
+        table.add(number, ly, lane, inside);
     }
     __syncthreads();
-    for (int s = t; s < SLOTS; s += TPB) {
-        const int number = key[s];
-        if (number == 0) continue;
-        const size_t row = (size_t)n * max_objects + (number - 1);
-        int *o = objects + row * 6;
-        const long long area = area_sx[s] >> 20;
-        __hip_atomic_fetch_add(o + 1, (int)area, PL_CC_RLX, AGENT);
-        __hip_atomic_fetch_min(o + 2, y0 + y_lo[s], PL_CC_RLX, AGENT);
-        __hip_atomic_fetch_min(o + 3, x0 + x_lo[s], PL_CC_RLX, AGENT);
-        __hip_atomic_fetch_max(o + 4, y0 + y_hi[s] + 1, PL_CC_RLX, AGENT);
-        __hip_atomic_fetch_max(o + 5, x0 + x_hi[s] + 1, PL_CC_RLX, AGENT);
-        __hip_atomic_fetch_add(sums + row * 2, area * y0 + (long long)sy[s], PL_CC_RLX, AGENT);
-        __hip_atomic_fetch_add(sums + row * 2 + 1, area * x0 + (long long)(area_sx[s] & 0xFFFFFu), PL_CC_RLX, AGENT);
-    }
+    const size_t row = (size_t)n * max_objects;
+    table.flush<ROW, AREA>(objects + row * ROW, sums + row * 2, y0, x0);
 }
 
 // one thread per table row
 __global__ void __launch_bounds__(TPB) centroid_kernel(const int *objects, const long long *sums, float *centroids, unsigned rows) {
     const unsigned r = blockIdx.x * (unsigned)TPB + threadIdx.x;
     if (r >= rows) return;
-    const int area = objects[(size_t)r * 6 + 1];
-    float cy = 0.f, cx = 0.f;
-    if (area > 0) {
-        cy = __double2float_rn(__ddiv_rn((double)sums[(size_t)r * 2], (double)area));
-        cx = __double2float_rn(__ddiv_rn((double)sums[(size_t)r * 2 + 1], (double)area));
-    }
-    centroids[(size_t)r * 2] = cy, centroids[(size_t)r * 2 + 1] = cx;
+    centroid_row<ROW, AREA>(objects, sums, centroids, r);
 }
 
 }  // namespace components

@@ -24,6 +24,15 @@ struct FastDiv {
     }
 };
 
+// v of lanes 0 .. lane of the wave64, summed.  The whole wave calls.
+template <class T> __device__ __forceinline__ T wave_inclusive_sum(T v, int lane) {
+    for (int o = 1; o < 64; o <<= 1) {
+        const T u = __shfl_up(v, o);
+        if (lane >= o) v += u;
+    }
+    return v;
+}
+
 // The fused tail of a conv: what layer.BatchNorm / Add / ReLU / LeakyReLU
 // (layer.py:125-127, 93-95, 44-51) would do to the conv output one by one.
 // Multiply and add stay separate roundings like numpy's two passes.

@@ -17,32 +17,22 @@
 // renumber_kernel  one workgroup per image scans vol up to nS (read on the device): a kept instance (vol >= min_size) gets the
 //                  next number, a dropped one 0, in place; num; and the image's table rows are initialised.
 // table_kernel     one workgroup per tile: masks = the number of S[end[p]], and area, box and coordinate sums of the instances
-//                  numbered up to max_instances in an LDS hash table keyed by the number (components::region_kernel's), flushed
-//                  with one set of global integer atomics per (tile, instance).  It works from the final numbers alone: a mask
-//                  need not be connected.
+//                  numbered up to max_instances through the tile's table (region_table.h) into the rows [area, y0, x0, y1, x1].
+//                  It works from the final numbers alone: a mask need not be connected.
 // centre_kernel    float32(float64(sum) / float64(area)) per row, +0.0 in the unused rows.
 #pragma once
-#include <climits>
-
 #include "common.h"
-#include "components_kernel.h"
 #include "device_utils.h"
+#include "region_table.h"
 
 namespace flow {
 
-constexpr int TPB = PL_STREAM_TPB;
-constexpr int TILE_H = PL_CC_TILE_H, TILE_W = PL_CC_TILE_W, TILE_PX = TILE_H * TILE_W;   // table_kernel takes the components tile
-constexpr int PER_THREAD = TILE_PX / TPB;
-constexpr int SLOTS = TILE_PX;                            // a tile holds at most TILE_PX instances: the table never overflows
+using namespace regions;                                  // TPB, the tile, RLX, AGENT
+
 constexpr int SCAN_STEP = PL_FLOW_SCAN_STEP;              // raw instances one step of renumber_kernel's workgroup takes
 constexpr int QUAD = 4;                                   // pixels a thread of the streaming kernels takes: 16-byte accesses
 constexpr int COUNT_GROUPS = 6;                           // sinks a wave of count_kernel adds to with one atomic each
-static_assert(TILE_W == 64 && TILE_PX % TPB == 0 && (SLOTS & (SLOTS - 1)) == 0, "a wave takes one row of a tile; whole passes");
-static_assert(TILE_PX <= 4096 && TILE_W * TILE_PX < (1 << 20), "table_kernel packs area (12 bits) over the x sum (20 bits)");
-static_assert(SCAN_STEP % 64 == 0 && SCAN_STEP <= 1024, "whole waves of one workgroup");
-
-constexpr int AGENT = __HIP_MEMORY_SCOPE_AGENT;
-#define PL_FLOW_RLX __ATOMIC_RELAXED
+constexpr int ROW = 5, AREA = 0;                          // a table row: [area, y0, x0, y1, x1]
 
 struct Geo {
     int N, H, W, HW, total;                               // total = N H W
@@ -145,10 +135,10 @@ __global__ void __launch_bounds__(TPB) count_kernel(const int *end, int *cnt, in
         const int word = __shfl(q, lead);
         const bool same = todo && q == word;
         const unsigned long long group = __ballot(same);
-        if (lane == lead) __hip_atomic_fetch_add(cnt + word, __popcll(group), PL_FLOW_RLX, AGENT);
+        if (lane == lead) __hip_atomic_fetch_add(cnt + word, __popcll(group), RLX, AGENT);
         todo = todo && !same;
     }
-    if (todo) __hip_atomic_fetch_add(cnt + q, 1, PL_FLOW_RLX, AGENT);
+    if (todo) __hip_atomic_fetch_add(cnt + q, 1, RLX, AGENT);
 }
 
 // one thread per QUAD pixels: four bytes of the sink map in one store (the map is 4-byte aligned and padded to whole words)
@@ -173,58 +163,31 @@ __global__ void __launch_bounds__(TPB) volume_kernel(const int *cnt, const int *
     const int c = cnt[f];
     if (c <= 0) return;
     const unsigned n = f / (unsigned)g.HW;
-    __hip_atomic_fetch_add(vol + (size_t)n * g.max_raw + (S[f] - 1), c, PL_FLOW_RLX, AGENT);
+    __hip_atomic_fetch_add(vol + (size_t)n * g.max_raw + (S[f] - 1), c, RLX, AGENT);
 }
 
 // grid = N, SCAN_STEP threads.  vol of image n -> the new numbers in place (0: dropped); num[n]; table rows of image n.
 __global__ void __launch_bounds__(SCAN_STEP) renumber_kernel(int *vol, const int *raw_num, int max_raw, int min_size, int *num,
                                                              int max_instances, int *instances, long long *sums) {
-    __shared__ int wtot[SCAN_STEP / 64];
-    __shared__ int carry_s;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     int *v = vol + (size_t)blockIdx.x * max_raw;
     const int raw = min(raw_num[blockIdx.x], max_raw);    // (nS <= max_raw by construction: the clamp only guards the table)
-    if (t == 0) carry_s = 0;
-    __syncthreads();
-    for (int j0 = 0; j0 < raw; j0 += SCAN_STEP) {
-        const int j = j0 + t;
-        const int keep = j < raw && v[j] >= min_size;
-        int inc = keep;
-        for (int o = 1; o < 64; o <<= 1) {
-            const int u = __shfl_up(inc, o);
-            if (lane >= o) inc += u;
-        }
-        if (lane == 63) wtot[wave] = inc;
-        __syncthreads();
-        int before = carry_s;
-        for (int w = 0; w < wave; ++w) before += wtot[w];
-        if (j < raw) v[j] = keep ? before + inc : 0;
-        __syncthreads();
-        if (t == SCAN_STEP - 1) carry_s = before + inc;
-        __syncthreads();
-    }
-    const int total = carry_s;
-    if (t == 0) num[blockIdx.x] = total;
-    for (int j = t; j < max_instances; j += SCAN_STEP) {
-        const size_t row = (size_t)blockIdx.x * max_instances + j;
-        int *o = instances + row * 5;
-        const bool used = j < total;
-        o[0] = 0, o[1] = used ? INT_MAX : 0, o[2] = used ? INT_MAX : 0, o[3] = 0, o[4] = 0;
-        sums[row * 2] = 0, sums[row * 2 + 1] = 0;
-    }
+    const int total = carry_scan<SCAN_STEP>(raw, [v, min_size](int j) { return (int)(v[j] >= min_size); },
+                                            [v](int j, int keep, int inc) { v[j] = keep ? inc : 0; });
+    if (threadIdx.x == 0) num[blockIdx.x] = total;
+    const size_t row = (size_t)blockIdx.x * max_instances;
+    init_rows<ROW, AREA, SCAN_STEP>(instances + row * ROW, sums + row * 2, max_instances, total);
 }
 
 // grid = N * tiles_y * tiles_x.  renum = vol behind renumber_kernel.
 __global__ void __launch_bounds__(TPB) table_kernel(const int *end, const int *S, const int *renum, int *masks, Geo g, int max_instances,
                                                     int *instances, long long *sums) {
-    __shared__ int key[SLOTS], y_lo[SLOTS], x_lo[SLOTS], y_hi[SLOTS], x_hi[SLOTS];
-    __shared__ unsigned area_sx[SLOTS], sy[SLOTS];        // area << 20 | sum of x; sum of y (tile-relative)
+    __shared__ Tile table;
     const int t = threadIdx.x, lane = t & 63;
     const unsigned tile = blockIdx.x % (unsigned)(g.tiles_x * g.tiles_y), n = blockIdx.x / (unsigned)(g.tiles_x * g.tiles_y);
     const int y0 = (int)(tile / (unsigned)g.tiles_x) * TILE_H, x0 = (int)(tile % (unsigned)g.tiles_x) * TILE_W;
     const size_t base = (size_t)n * g.HW;
     const int *rn = renum + (size_t)n * g.max_raw;
-    for (int s = t; s < SLOTS; s += TPB) key[s] = 0, area_sx[s] = 0u, sy[s] = 0u, y_lo[s] = INT_MAX, x_lo[s] = INT_MAX, y_hi[s] = -1, x_hi[s] = -1;
+    table.clear();
     __syncthreads();
     const int inside = min(TILE_W, g.W - x0);             // columns of the tile inside the image: lanes [0, inside)
     for (int k = 0; k < PER_THREAD; ++k) {
@@ -238,50 +201,18 @@ __global__ void __launch_bounds__(TPB) table_kernel(const int *end, const int *S
             masks[f] = number;
         }
         if (number > max_instances) number = 0;           // numbered, and without a row
-        const int first = __shfl(number, 0);
-        const bool one = first > 0 && __all(lane >= inside || number == first);
-        if (!one && number == 0) continue;
-        if (one && lane != 0) continue;
-        int s = (int)(((unsigned)number * 2654435761u) >> 16) & (SLOTS - 1);
-        for (;;) {
-            const int old = atomicCAS(&key[s], 0, number);
-            if (old == 0 || old == number) break;
-            s = (s + 1) & (SLOTS - 1);
-        }
-        const unsigned c = one ? (unsigned)inside : 1u, lx = (unsigned)lane;
-        atomicAdd(&area_sx[s], one ? (c << 20) | (c * (c - 1) / 2) : (1u << 20) | lx);
-        atomicAdd(&sy[s], c * (unsigned)ly);
-        atomicMin(&y_lo[s], ly), atomicMax(&y_hi[s], ly);
-        atomicMin(&x_lo[s], lane), atomicMax(&x_hi[s], one ? inside - 1 : lane);
+        table.add(number, ly, lane, inside);
     }
     __syncthreads();
-    for (int s = t; s < SLOTS; s += TPB) {
-        const int number = key[s];
-        if (number == 0) continue;
-        const size_t row = (size_t)n * max_instances + (number - 1);
-        int *o = instances + row * 5;
-        const long long area = area_sx[s] >> 20;
-        __hip_atomic_fetch_add(o, (int)area, PL_FLOW_RLX, AGENT);
-        __hip_atomic_fetch_min(o + 1, y0 + y_lo[s], PL_FLOW_RLX, AGENT);
-        __hip_atomic_fetch_min(o + 2, x0 + x_lo[s], PL_FLOW_RLX, AGENT);
-        __hip_atomic_fetch_max(o + 3, y0 + y_hi[s] + 1, PL_FLOW_RLX, AGENT);
-        __hip_atomic_fetch_max(o + 4, x0 + x_hi[s] + 1, PL_FLOW_RLX, AGENT);
-        __hip_atomic_fetch_add(sums + row * 2, area * y0 + (long long)sy[s], PL_FLOW_RLX, AGENT);
-        __hip_atomic_fetch_add(sums + row * 2 + 1, area * x0 + (long long)(area_sx[s] & 0xFFFFFu), PL_FLOW_RLX, AGENT);
-    }
+    const size_t row = (size_t)n * max_instances;
+    table.flush<ROW, AREA>(instances + row * ROW, sums + row * 2, y0, x0);
 }
 
 // one thread per table row
 __global__ void __launch_bounds__(TPB) centre_kernel(const int *instances, const long long *sums, float *centres, unsigned rows) {
     const unsigned r = blockIdx.x * (unsigned)TPB + threadIdx.x;
     if (r >= rows) return;
-    const int area = instances[(size_t)r * 5];
-    float cy = 0.f, cx = 0.f;
-    if (area > 0) {
-        cy = __double2float_rn(__ddiv_rn((double)sums[(size_t)r * 2], (double)area));
-        cx = __double2float_rn(__ddiv_rn((double)sums[(size_t)r * 2 + 1], (double)area));
-    }
-    centres[(size_t)r * 2] = cy, centres[(size_t)r * 2 + 1] = cx;
+    centroid_row<ROW, AREA>(instances, sums, centres, r);
 }
 
 }  // namespace flow

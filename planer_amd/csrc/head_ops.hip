@@ -149,11 +149,7 @@ __global__ void __launch_bounds__(1024) nonzero_scan_kernel(long long *counts, s
     for (size_t b0 = 0; b0 < nb; b0 += 1024) {
         const size_t i = b0 + threadIdx.x;
         const long long v = i < nb ? counts[i] : 0;
-        long long inc = v;                                   // inclusive scan inside the wave
-        for (int o = 1; o < 64; o <<= 1) {
-            const long long t = __shfl_up(inc, o);
-            if (lane >= o) inc += t;
-        }
+        const long long inc = wave_inclusive_sum(v, lane);
         if (lane == 63) wtot[wave] = inc;
         __syncthreads();
         long long before = carry_s;
@@ -181,11 +177,7 @@ __global__ void __launch_bounds__(TPB) nonzero_write_kernel(const void *x, size_
         c += f[e];
     }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int inc = c;
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(inc, o);
-        if (lane >= o) inc += t;
-    }
+    const int inc = wave_inclusive_sum(c, lane);
     if (lane == 63) wsum[wave] = inc;
     __syncthreads();
     long long pos = offsets[blockIdx.x] + inc - c;

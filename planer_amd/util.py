@@ -25,6 +25,28 @@ from .hip import DeviceArray
 from .layer import _strided_map, _contig_strides, _f32
 
 
+def _is_int(v, lo, hi=None):
+    """v is an integer, and no bool, in [lo, hi] (hi None: no upper end)"""
+    return not isinstance(v, bool) and isinstance(v, (int, numpy.integer)) and lo <= v and (hi is None or v <= hi)
+
+
+def _is_number(v, nan=False):
+    """v is an integer or a float, and no bool; a NaN only where `nan`"""
+    return not isinstance(v, bool) and isinstance(v, (int, float, numpy.integer, numpy.floating)) and (nan or v == v)
+
+
+def _launch_or_zero(ctx, images, pixels, zeroed, scratch_bytes, launch):
+    """Behind a head's fresh outputs: with images and no pixel nothing is launched (the input may own no memory to point at) and
+    `zeroed`, what only a launch would write, is memset; with pixels, launch(`scratch_bytes` of scratch from `ctx`'s pool)."""
+    if images and not pixels:
+        for a in zeroed:
+            if a.nbytes:
+                _lib.call("pl_memset", ctx.handle, a.ptr, 0, a.nbytes)
+    elif images:
+        scratch = hip.empty(((scratch_bytes + 7) // 8,), numpy.int64, ctx=ctx)      # (held until the launch is enqueued)
+        launch(scratch.ptr)
+
+
 def make_slice(l, w, mar):
     """util.make_slice (util.py:236-238)"""
     r = numpy.linspace(0, l - w, math.ceil((l - mar) / (w - mar)))
@@ -338,11 +360,11 @@ class DetectionSpec:
             self.heads.append((anchors.astype(numpy.float32), stride))
         if not self.heads:
             raise ValueError("detection output: no heads given")
-        if not isinstance(classes, (int, numpy.integer)) or classes < 1:
+        if not _is_int(classes, 1):
             raise ValueError("detection output: classes is a count >= 1, got %r" % (classes,))
-        if not isinstance(max_candidates, (int, numpy.integer)) or not 1 <= max_candidates <= _lib.NMS_MAX_CANDIDATES:
+        if not _is_int(max_candidates, 1, _lib.NMS_MAX_CANDIDATES):
             raise ValueError("detection output: max_candidates is 1 to %d, got %r" % (_lib.NMS_MAX_CANDIDATES, max_candidates))
-        if not isinstance(max_det, (int, numpy.integer)) or max_det < 1:
+        if not _is_int(max_det, 1):
             raise ValueError("detection output: max_det is a count >= 1, got %r" % (max_det,))
         if size is not None:
             size = tuple(int(s) for s in size)
@@ -417,7 +439,7 @@ def nms(boxes, scores, classes=None, iou=0.45, max_det=100, floor=-math.inf):
     if boxes.shape != (n, r, 4) or (classes is not None and classes.shape != (n, r)):
         raise ValueError("nms: boxes (N, K0, 4), scores (N, K0) and classes (N, K0) do not agree: %s, %s, %s"
                          % (tuple(boxes.shape), tuple(scores.shape), None if classes is None else tuple(classes.shape)))
-    if not isinstance(max_det, (int, numpy.integer)) or max_det < 1:
+    if not _is_int(max_det, 1):
         raise ValueError("nms: max_det is a count >= 1, got %r" % (max_det,))
     k = min(r, _lib.NMS_MAX_CANDIDATES)
     return _nms_sorted(boxes, classes, scores, n, r, k, float(floor), _f32v(iou), classes is not None, min(int(max_det), k), boxes.ctx)
@@ -432,18 +454,19 @@ def _cc_scratch_bytes(n, h, w, max_objects):
 def _cc_arguments(what, connectivity, background, max_objects):
     if isinstance(connectivity, bool) or connectivity not in (4, 8):
         raise ValueError("%s: connectivity is 4 or 8, got %r" % (what, connectivity))
-    if isinstance(background, bool) or not isinstance(background, (int, numpy.integer)) or not -1 <= background <= 255:
+    if not _is_int(background, -1, 255):
         raise ValueError("%s: background is a class 0 to 255, or -1 for none, got %r" % (what, background))
-    if isinstance(max_objects, bool) or not isinstance(max_objects, (int, numpy.integer)) or not 0 <= max_objects <= _lib.CC_MAX_OBJECTS:
+    if not _is_int(max_objects, 0, _lib.CC_MAX_OBJECTS):
         raise ValueError("%s: max_objects is 0 to %d, got %r" % (what, _lib.CC_MAX_OBJECTS, max_objects))
     return int(connectivity), int(background), int(max_objects)
 
 
-def _cc_geometry(what, n, h, w, max_objects):
+def _table_geometry(what, n, h, w, rows, width):
+    """Refuses (n, h, w) maps and tables of `rows` rows of `width` ints per image that int32 indices do not reach."""
     if h * w >= 1 << 31 or n * h * w >= 1 << 31:
         raise ValueError("%s: %d x %d x %d is 2^31 or more pixels" % (what, n, h, w))
-    if n * max_objects * 6 >= 1 << 31:
-        raise ValueError("%s: %d images x %d rows is 2^31 or more table entries" % (what, n, max_objects))
+    if n * rows * width >= 1 << 31:
+        raise ValueError("%s: %d images x %d rows is 2^31 or more table entries" % (what, n, rows))
 
 
 def _components(m, n, h, w, connectivity, background, max_objects, ctx):
@@ -452,14 +475,9 @@ def _components(m, n, h, w, connectivity, background, max_objects, ctx):
     labels, num = hip.empty((n, h, w), numpy.int32, ctx=ctx), hip.empty((n,), numpy.int32, ctx=ctx)
     objects = hip.empty((n, max_objects, 6), numpy.int32, ctx=ctx)
     centroids = hip.empty((n, max_objects, 2), numpy.float32, ctx=ctx)
-    if n and not h * w:                                   # nothing to label: no launch writes the counts and the table
-        for a in (num, objects, centroids):
-            if a.nbytes:
-                _lib.call("pl_memset", ctx.handle, a.ptr, 0, a.nbytes)
-        return labels, num, objects, centroids
-    scratch = hip.empty(((_cc_scratch_bytes(n, h, w, max_objects) + 7) // 8,), numpy.int64, ctx=ctx)      # (8-byte aligned)
-    _lib.call("pl_components_u8_i32", ctx.handle, m.ptr, n, h, w, connectivity, background, max_objects, scratch.ptr, labels.ptr,
-              num.ptr, objects.ptr if max_objects else None, centroids.ptr if max_objects else None)
+    _launch_or_zero(ctx, n, h * w, (num, objects, centroids), _cc_scratch_bytes(n, h, w, max_objects), lambda scratch: _lib.call(
+        "pl_components_u8_i32", ctx.handle, m.ptr, n, h, w, connectivity, background, max_objects, scratch, labels.ptr, num.ptr,
+        objects.ptr if max_objects else None, centroids.ptr if max_objects else None))
     return labels, num, objects, centroids
 
 
@@ -482,7 +500,7 @@ class ObjectSpec:
         n, c, h, w = shape
         if not 1 <= c <= 256:
             raise ValueError("object output: 1 to 256 planes fit a byte, got %d in shape %s" % (c, tuple(shape)))
-        _cc_geometry("object output", n, h, w, self.max_objects)
+        _table_geometry("object output", n, h, w, self.max_objects, 6)
         return n, c, h, w
 
     def check(self, x):
@@ -491,7 +509,7 @@ class ObjectSpec:
     def components(self, m, ctx=None):
         """The four arrays of the uint8 label map `m` (N, H, W), a DeviceArray."""
         n, h, w = m.shape
-        _cc_geometry("object output", n, h, w, self.max_objects)
+        _table_geometry("object output", n, h, w, self.max_objects, 6)
         return _components(m, n, h, w, self.connectivity, self.background, self.max_objects, ctx or m.ctx)
 
     def encode(self, x, ctx=None):
@@ -516,7 +534,7 @@ def connected_components(m, connectivity=8, background=0, max_objects=256):
         raise ValueError("connected components: expected a uint8 map (N, H, W) or (H, W), got %s of shape %s" % (m.dtype, tuple(m.shape)))
     connectivity, background, max_objects = _cc_arguments("connected components", connectivity, background, max_objects)
     n, h, w = (1,) + tuple(m.shape) if m.ndim == 2 else m.shape
-    _cc_geometry("connected components", n, h, w, max_objects)
+    _table_geometry("connected components", n, h, w, max_objects, 6)
     labels, num, objects, centroids = _components(m, n, h, w, connectivity, background, max_objects, m.ctx)
     return (labels.reshape(h, w) if m.ndim == 2 else labels), num, objects, centroids
 
@@ -535,11 +553,10 @@ def _peaks_arguments(what, threshold, ties, max_peaks, refine, stride):
         raise ValueError("%s: ties is 'all' or 'first', got %r" % (what, ties))
     if refine not in _lib.PEAKS_REFINE:
         raise ValueError("%s: refine is 'none' or 'quarter', got %r" % (what, refine))
-    if isinstance(max_peaks, bool) or not isinstance(max_peaks, (int, numpy.integer)) or not 1 <= max_peaks <= _lib.PEAKS_MAX_PEAKS:
+    if not _is_int(max_peaks, 1, _lib.PEAKS_MAX_PEAKS):
         raise ValueError("%s: max_peaks is 1 to %d, got %r" % (what, _lib.PEAKS_MAX_PEAKS, max_peaks))
     pair = tuple(stride) if isinstance(stride, (tuple, list)) else (stride, stride)
-    number = (int, float, numpy.integer, numpy.floating)
-    if len(pair) != 2 or any(isinstance(v, bool) or not isinstance(v, number) for v in pair):
+    if len(pair) != 2 or not all(_is_number(v, nan=True) for v in pair):   # (a NaN is refused below, as not positive)
         raise ValueError("%s: stride is a number or an (sy, sx) pair, got %r" % (what, stride))
     sy, sx = _f32v(pair[0]), _f32v(pair[1])
     if not (0 < sy < math.inf and 0 < sx < math.inf):
@@ -591,13 +608,9 @@ class KeypointSpec:
         n, k, h, w = self.geometry(_f32_nchw("keypoint output", x))
         ctx = ctx or x.ctx
         peaks, num = hip.empty((n, k, self.max_peaks, 3), numpy.float32, ctx=ctx), hip.empty((n, k), numpy.int32, ctx=ctx)
-        if n * k and not h * w:                               # no pixel: no peak (and x may own no memory to point at)
-            for a in (peaks, num):
-                _lib.call("pl_memset", ctx.handle, a.ptr, 0, a.nbytes)
-        elif n * k:
-            scratch = hip.empty(((_peaks_scratch_bytes(n, k, h, w, self.max_peaks) + 7) // 8,), numpy.int64, ctx=ctx)
-            _lib.call("pl_peaks_f32", ctx.handle, x.ptr, n, k, h, w, self.threshold, _lib.PEAKS_TIES[self.ties], self.max_peaks,
-                      _lib.PEAKS_REFINE[self.refine], self.stride[0], self.stride[1], scratch.ptr, peaks.ptr, num.ptr)
+        _launch_or_zero(ctx, n * k, h * w, (peaks, num), _peaks_scratch_bytes(n, k, h, w, self.max_peaks), lambda scratch: _lib.call(
+            "pl_peaks_f32", ctx.handle, x.ptr, n, k, h, w, self.threshold, _lib.PEAKS_TIES[self.ties], self.max_peaks,
+            _lib.PEAKS_REFINE[self.refine], self.stride[0], self.stride[1], scratch, peaks.ptr, num.ptr))
         return peaks, num
 
 
@@ -625,29 +638,20 @@ def _flow_scratch_bytes(n, h, w, max_instances):
 
 
 def _flow_arguments(what, level, min_flow, rounds, min_size, max_instances, planes):
-    number = (int, float, numpy.integer, numpy.floating)
     for name, v in (("level", level), ("min_flow", min_flow)):
-        if isinstance(v, bool) or not isinstance(v, number) or v != v:
+        if not _is_number(v):
             raise ValueError("%s: %s is a number, got %r" % (what, name, v))
     for name, v, top in (("rounds", rounds, _lib.FLOW_MAX_ROUNDS), ("min_size", min_size, (1 << 31) - 1),
                          ("max_instances", max_instances, _lib.FLOW_MAX_INSTANCES)):
-        if isinstance(v, bool) or not isinstance(v, (int, numpy.integer)) or not 0 <= v <= top:
+        if not _is_int(v, 0, top):
             raise ValueError("%s: %s is 0 to %d, got %r" % (what, name, top, v))
     try:
         planes = tuple(planes)
     except TypeError:
         planes = ()
-    if len(planes) != 3 or any(isinstance(p, bool) or not isinstance(p, (int, numpy.integer)) or p < 0 for p in planes) \
-            or len(set(planes)) != 3:
+    if len(planes) != 3 or not all(_is_int(p, 0) for p in planes) or len(set(planes)) != 3:
         raise ValueError("%s: planes names three distinct planes (dy, dx, prob), got %r" % (what, planes))
     return _f32v(level), _f32v(min_flow), int(rounds), int(min_size), int(max_instances), tuple(int(p) for p in planes)
-
-
-def _flow_geometry(what, n, h, w, max_instances):
-    if h * w >= 1 << 31 or n * h * w >= 1 << 31:
-        raise ValueError("%s: %d x %d x %d is 2^31 or more pixels" % (what, n, h, w))
-    if n * max_instances * 5 >= 1 << 31:
-        raise ValueError("%s: %d images x %d rows is 2^31 or more table entries" % (what, n, max_instances))
 
 
 class FlowSpec:
@@ -672,7 +676,7 @@ class FlowSpec:
         n, c, h, w = shape
         if c < 3 or max(self.planes) >= c:
             raise ValueError("flow output: planes %s of a result with %d planes, shape %s" % (self.planes, c, tuple(shape)))
-        _flow_geometry("flow output", n, h, w, self.max_instances)
+        _table_geometry("flow output", n, h, w, self.max_instances, 5)
         return n, c, h, w
 
     def check(self, x):
@@ -682,18 +686,13 @@ class FlowSpec:
         """pl_flow_instances_f32 on the float32 DeviceArray `x`, element (i, plane, y, x) at i image_stride + offsets[plane] +
         (y w + x) pixel_stride: fresh (masks, num, instances, centres); everything else is scratch from `ctx`'s pool."""
         m = self.max_instances
-        _flow_geometry("flow output", n, h, w, m)
+        _table_geometry("flow output", n, h, w, m, 5)
         masks, num = hip.empty((n, h, w), numpy.int32, ctx=ctx), hip.empty((n,), numpy.int32, ctx=ctx)
         instances, centres = hip.empty((n, m, 5), numpy.int32, ctx=ctx), hip.empty((n, m, 2), numpy.float32, ctx=ctx)
-        if n and not h * w:                                   # no pixel: no instance (and x may own no memory to point at)
-            for a in (num, instances, centres):
-                if a.nbytes:
-                    _lib.call("pl_memset", ctx.handle, a.ptr, 0, a.nbytes)
-        elif n:
-            scratch = hip.empty(((_flow_scratch_bytes(n, h, w, m) + 7) // 8,), numpy.int64, ctx=ctx)      # (8-byte aligned)
-            _lib.call("pl_flow_instances_f32", ctx.handle, x.ptr, n, h, w, image_stride, pixel_stride, offsets[0], offsets[1], offsets[2],
-                      self.level, self.min_flow, self.rounds, self.min_size, m, scratch.ptr, masks.ptr, num.ptr,
-                      instances.ptr if m else None, centres.ptr if m else None)
+        _launch_or_zero(ctx, n, h * w, (num, instances, centres), _flow_scratch_bytes(n, h, w, m), lambda scratch: _lib.call(
+            "pl_flow_instances_f32", ctx.handle, x.ptr, n, h, w, image_stride, pixel_stride, offsets[0], offsets[1], offsets[2],
+            self.level, self.min_flow, self.rounds, self.min_size, m, scratch, masks.ptr, num.ptr,
+            instances.ptr if m else None, centres.ptr if m else None))
         return masks, num, instances, centres
 
     def encode(self, x, ctx=None):

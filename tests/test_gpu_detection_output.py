@@ -13,13 +13,10 @@ import pytest
 
 from tests import detect_ref as R
 from tests import image_input_ref as RI
+from tests.head_kit import EINVAL, EUNSUPPORTED, F32, OK, SENT, Framed, host as _host
 
 pytestmark = pytest.mark.gpu
 
-F32 = np.float32
-PAD = 16                                    # sentinel words on either side of an output
-SENT = np.uint32(0xA5A5A5A5)
-OK, EINVAL, EUNSUPPORTED = 0, 1, 2
 NAN, INF = float("nan"), float("inf")
 SPECIALS = np.array([NAN, INF, -INF, -0.0], F32)
 
@@ -29,26 +26,6 @@ def pa():
     import planer_amd
     planer_amd.hip.context()
     return planer_amd
-
-
-class Framed:
-    """`words` 32-bit words on the device between two runs of PAD sentinel words, all of it the sentinel to begin with."""
-
-    def __init__(self, pa, words):
-        self.words = words
-        self.buf = pa.hip.empty((PAD + words + PAD,), np.uint32)
-        self.buf.set(np.full(self.buf.shape, SENT, np.uint32))
-        self.ptr = self.buf.ptr + 4 * PAD
-
-    def get(self, dtype=np.uint32):
-        """(the words as `dtype`, whether both sentinel runs are intact)"""
-        raw = self.buf.get()
-        intact = bool((raw[:PAD] == SENT).all() and (raw[PAD + self.words:] == SENT).all())
-        return raw[PAD:PAD + self.words].view(dtype), intact
-
-    def untouched(self):
-        raw, intact = self.get()
-        return intact and bool((raw == SENT).all())
 
 
 # ---- pl_yolo_decode_f32 -----------------------------------------------------------------------------------------------------
@@ -444,10 +421,6 @@ def _tiny_ref(heads):
 def _declare(net):
     return net.detection_output(TINY_HEADS, TINY["classes"], conf=TINY["conf"], iou=TINY["iou"], max_det=TINY["max_det"],
                                 size=TINY["size"], indices=(1, 2))
-
-
-def _host(y):
-    return tuple(v.get() if hasattr(v, "get") else v for v in y)
 
 
 @pytest.mark.parametrize("streams", [None, "pipe2"])

@@ -8,25 +8,20 @@ before it is written shows up as a wrong answer and a write past a block as a di
 header states (the table pass takes the components tile; the chain adds no tile extent of its own).  Then nets: every call form
 against the mirror applied to what a second, undeclared instance returns."""
 import functools
-import os
-import re
 
 import numpy as np
 import pytest
 
 from tests import flow_ref as R
+from tests import head_kit as K
 from tests import image_input_ref as RI
-from tests.conftest import ROOT
+from tests.head_kit import EINVAL, EUNSUPPORTED, F32, I32, OK, Framed
 
 pytestmark = pytest.mark.gpu
 
-F32, I32 = np.float32, np.int32
-PAD = 16                                    # sentinel words on either side of an output
-SENT = np.uint32(0xA5A5A5A5)
-OK, EINVAL, EUNSUPPORTED = 0, 1, 2
+NAMES = ("masks", "num", "instances", "centres")
 
-_H = open(os.path.join(ROOT, "include", "planer_hip.h")).read()
-_C = {k: int(v) for k, v in re.findall(r"#define (PL_(?:CC|FLOW)_[A-Z_]+) (\d+)", _H)}
+_C = K.header_constants("PL_(?:CC|FLOW)_")
 TH, TW, BLOCK = _C["PL_CC_TILE_H"], _C["PL_CC_TILE_W"], _C["PL_CC_BLOCK"]
 SCAN_STEP, MAX_ROUNDS, MAX_INSTANCES = _C["PL_FLOW_SCAN_STEP"], _C["PL_FLOW_MAX_ROUNDS"], _C["PL_FLOW_MAX_INSTANCES"]
 
@@ -89,25 +84,6 @@ def cases(shape):
     return out
 
 
-class Framed:
-    """`words` 32-bit words on the device between two runs of PAD sentinel words, all of it the sentinel to begin with."""
-
-    def __init__(self, pa, words):
-        self.words = words
-        self.buf = pa.hip.empty((PAD + words + PAD,), np.uint32)
-        self.buf.set(np.full(self.buf.shape, SENT, np.uint32))
-        self.ptr = self.buf.ptr + 4 * PAD
-
-    def get(self, dtype, shape):
-        """(the words as `dtype`, whether both sentinel runs are intact)"""
-        raw = self.buf.get()
-        intact = bool((raw[:PAD] == SENT).all() and (raw[PAD + self.words:] == SENT).all())
-        return raw[PAD:PAD + self.words].view(dtype).reshape(shape), intact
-
-    def untouched(self):
-        return bool((self.buf.get() == SENT).all())
-
-
 def chain(pa, x, kw, hwc=False, null_tables=False):
     """pl_flow_instances_f32 through the C interface on framed outputs and a poisoned scratch block; hwc: the same data as
     (N, H, W, C), read through pixel_stride = C.  -> (status, (masks, num, instances, centres), every frame intact)."""
@@ -134,11 +110,7 @@ def chain(pa, x, kw, hwc=False, null_tables=False):
 
 
 def same(got, want, what):
-    for name, g, r in zip(("masks", "num", "instances", "centres"), got, want):
-        assert g.shape == r.shape and g.dtype == r.dtype, (what, name, g.shape, r.shape, g.dtype, r.dtype)
-        bad = np.flatnonzero((g.view(np.uint32) if g.dtype == F32 else g).ravel() != (r.view(np.uint32) if r.dtype == F32 else r).ravel())
-        assert bad.size == 0, "%s: %s differs at %d places, first flat index %d: got %r, want %r" % (
-            what, name, bad.size, bad[0], g.ravel()[bad[0]], r.ravel()[bad[0]])
+    K.same(got, want, NAMES, what)
 
 
 @pytest.mark.parametrize("shape", SHAPES, ids=str)
@@ -193,20 +165,8 @@ def test_the_patterns_are_what_they_claim(pa):
 
 def test_hygiene_pass_over_every_case(pa):
     """util.follow_flows on every case with the pool in hygiene mode: fresh blocks are poisoned and guarded."""
-    ctx = pa.hip.context()
-    ctx.synchronize()
-    ctx.pool_debug(pa.hip.POOL_GUARD_BYTES, 0xFF)
-    try:
-        got = [tuple(a.get() for a in pa.util.follow_flows(pa.hip.asarray(np.ascontiguousarray(x)), **kw))
-               for shape in SHAPES for _, x, kw, _ in cases(shape)]
-        dirty, report = ctx.pool_debug_check()
-    finally:
-        ctx.pool_debug(0)
-    assert dirty == 0, report
-    want = [(what, ref) for shape in SHAPES for what, _, _, ref in cases(shape)]
-    assert len(got) == len(want) > 200
-    for g, (what, ref) in zip(got, want):
-        same(g, ref, what)
+    K.hygiene_pass(pa, [case for shape in SHAPES for case in cases(shape)],
+                   lambda x, kw: pa.util.follow_flows(pa.hip.asarray(np.ascontiguousarray(x)), **kw), NAMES, 200)
 
 
 def test_one_image_and_empty_inputs(pa):
@@ -253,8 +213,6 @@ def test_refusals_leave_the_outputs_untouched(pa):
 
 def test_chain_replays_from_a_captured_graph(pa):
     """No host wait and no host-computed value: the chain captured once answers for whatever planes are in its input at launch."""
-    from planer_amd import _lib
-    ctx = pa.hip.context()
     n, h, w, m = 2, TH + 5, 2 * TW + 3, 20
     kw = _kw(rounds=3, min_size=2, max_instances=m)
     inputs = [R.random_flows(n, h, w, 21), R.serpentine(n, h, w)[0], R.discs(n, h, w, 22, 0.6)[0], R.vortices(n, h, w, 1)]
@@ -262,23 +220,11 @@ def test_chain_replays_from_a_captured_graph(pa):
     masks, num = pa.hip.empty((n, h, w), I32), pa.hip.empty((n,), I32)
     instances, centres = pa.hip.empty((n, m, 5), I32), pa.hip.empty((n, m, 2), F32)
     scratch = pa.hip.empty(((scratch_bytes(n, h, w, m) + 7) // 8,), np.int64)
-    ctx.synchronize()
-    _lib.call("pl_capture_begin", ctx.handle)
-    graph = _lib.c_void_p()
-    try:
-        rc = _lib.load().pl_flow_instances_f32(ctx.handle, x.ptr, n, h, w, 3 * h * w, 1, 0, h * w, 2 * h * w, kw["level"], kw["min_flow"],
-                                               kw["rounds"], kw["min_size"], m, scratch.ptr, masks.ptr, num.ptr, instances.ptr, centres.ptr)
-    finally:
-        end = _lib.load().pl_capture_end(ctx.handle, _lib.byref(graph))
-    assert rc == OK
-    _lib.check(end)
-    try:
-        for i, host in enumerate(inputs):
-            x.set(host)
-            _lib.call("pl_graph_launch", graph)
-            same(tuple(a.get() for a in (masks, num, instances, centres)), R.flow_ref(host, **kw), "replay %d" % i)
-    finally:
-        _lib.check(_lib.load().pl_graph_destroy(graph))
+    K.replay_from_captured_graph(
+        pa, lambda: pa._lib.load().pl_flow_instances_f32(pa.hip.context().handle, x.ptr, n, h, w, 3 * h * w, 1, 0, h * w, 2 * h * w, kw["level"],
+                                                         kw["min_flow"], kw["rounds"], kw["min_size"], m, scratch.ptr, masks.ptr, num.ptr,
+                                                         instances.ptr, centres.ptr),
+        x, (masks, num, instances, centres), inputs, lambda host: R.flow_ref(host, **kw), NAMES)
 
 
 def test_a_large_map_with_a_known_answer(pa):
@@ -305,32 +251,6 @@ def test_a_large_map_with_a_known_answer(pa):
 SPEC = dict(level=0.0, min_flow=0.5, rounds=6, min_size=2, max_instances=40)
 
 
-def tiny_net(outputs, seed=4):
-    """x (N, 3, 32, 32) -> conv 3x3 (8) + relu = f -> conv 3x3 (3) = s, the three planes.  Small-integer filters and biases: with
-    integer inputs every partial sum is an exact float32, so two instances agree bit for bit whichever kernels they pick (the trick
-    of tests/test_gpu_conv_exact.py)."""
-    from planer_amd.irgen.builder import GraphBuilder
-    rng = np.random.default_rng(seed)
-    g = GraphBuilder(["x"])
-    g.init("K0", rng.integers(-2, 3, (8, 3, 3, 3)).astype(F32))
-    g.init("B0", rng.integers(-3, 4, 8).astype(F32))
-    g.op("conv", ["x", "K0", "B0"], "c0", name="conv0", group=1, strides=[1, 1], dilations=[1, 1], pads=[1, 1, 1, 1])
-    g.op("relu", "c0", "f", name="relu0")
-    g.init("K1", rng.integers(-2, 3, (3, 8, 3, 3)).astype(F32))
-    g.init("B1", rng.integers(-3, 4, 3).astype(F32))
-    g.op("conv", ["f", "K1", "B1"], "s", name="conv1", group=1, strides=[1, 1], dilations=[1, 1], pads=[1, 1, 1, 1])
-    return g.finish(outputs)
-
-
-def tiny_input(seed=7):
-    x = np.random.default_rng(seed).integers(-3, 4, (2, 3, 8, 8)).astype(F32)
-    return np.ascontiguousarray(np.repeat(np.repeat(x, 4, 2), 4, 3))
-
-
-def _host(y):
-    return tuple(v.get() if hasattr(v, "get") else v for v in y)
-
-
 def _want(planes):
     ref = R.flow_ref(planes, **SPEC)
     assert ref[1].min() >= 1, ref[1]                                         # something to find in every image
@@ -339,71 +259,12 @@ def _want(planes):
 
 @pytest.mark.parametrize("streams", [None, "pipe2"])
 def test_tiny_net_every_call_form(pa, streams):
-    g, b = tiny_net(["f", "s"])
-    x = tiny_input()
-    net, plain = pa.from_graph(g, b), pa.from_graph(g, b)
-    if streams:
-        net.streams = plain.streams = streams
-    feat, planes = plain(x)
-    assert feat.shape == (2, 8, 32, 32) and planes.shape == (2, 3, 32, 32)
-    ref = _want(planes)
-
-    def check(y, what, on_device=False):
-        assert isinstance(y, tuple) and len(y) == 5, what
-        assert all(isinstance(v, pa.hip.DeviceArray if on_device else np.ndarray) for v in y), what
-        y = _host(y)
-        assert RI.same_bits(y[0], feat), what                                # the other output: untouched
-        same(y[1:], ref, what)
-
-    base = net(x)                                                            # a plan exists before the declaration
-    assert len(base) == 2 and RI.same_bits(base[1], planes)
-    before = dict(net._plans)
-    assert net.flow_output(index=1, **SPEC) is net
-    check(net(x), "host")
-    check(net(pa.asarray(x)), "device", True)
-    check(net({net.input[0]: x}), "dict")
-    check(net.submit(x).get(), "submit")
-    check(net.submit(pa.asarray(x)).result(), "submit device", True)
-    pend = [net.submit(x) for _ in range(3)]                                 # several in flight
-    for p in pend:
-        check(p.get(), "submits in flight")
-    net.compile(pa.asarray(x))
-    check(net(pa.asarray(x)), "compile + replay", True)
-    assert all(net._plans[key] is before[key] for key in before)             # the declaration touched no plan
-    for how in ("debug", "eager"):                                           # the eager routes
-        if how == "eager":
-            net.use_graph = False
-        check(net(x, debug=True) if how == "debug" else net(x), how)
-    net.use_graph = True
-    # float_output restores the float tensor
-    assert net.float_output(1) is net
-    for got, want in zip(net(x), (feat, planes)):
-        assert RI.same_bits(got, want)
-    # checks come before anything is launched: a position the net does not have
-    net.flow_output(index=2, **SPEC)
-    for call in (lambda: net(x), lambda: net(pa.asarray(x)), lambda: net.submit(x)):
-        with pytest.raises(ValueError, match="returns 2"):
-            call()
-    pa.hip.trim_side_contexts()
+    K.check_every_call_form(pa, streams, lambda net, **at: net.flow_output(**at, **SPEC), _want, NAMES)
 
 
 def test_one_output_net_and_uint8_input(pa):
-    g, b = tiny_net(["s"])
-    net, plain = pa.from_graph(g, b), pa.from_graph(g, b)
-    k, bb = np.ones(3, F32), np.zeros(3, F32)                               # the bytes as they are: integers
-    net.image_input(k, bb).flow_output(**SPEC)
-    i = np.arange(2 * 8 * 8 * 3, dtype=np.int64)
-    x = ((i * 37 + i // 192 * 53 + 11) % 256).astype(np.uint8).reshape(2, 8, 8, 3)
-    x = np.ascontiguousarray(np.repeat(np.repeat(x, 4, 1), 4, 2))
-    planes = plain(RI.decode32(x, k, bb))
-    ref = _want(planes)
-    for what, y in (("host", net(x)), ("device", net(pa.asarray(x))), ("submit", net.submit(x).get()), ("float in", net(RI.decode32(x, k, bb)))):
-        assert len(y) == 4, what
-        same(_host(y), ref, what)
-    masks, num, instances, centres = net(x)
-    assert masks.shape == (2, 32, 32) and num.shape == (2,) and instances.shape == (2, 40, 5) and centres.shape == (2, 40, 2)
-    same(_host(pa.util.FlowSpec(**SPEC).encode(pa.asarray(planes))), ref, "FlowSpec.encode")
-    pa.hip.trim_side_contexts()
+    K.check_one_output_net_and_uint8_input(pa, lambda net: net.flow_output(**SPEC), _want, NAMES,
+                                           [(2, 32, 32), (2,), (2, 40, 5), (2, 40, 2)], pa.util.FlowSpec(**SPEC))
 
 
 def test_cellnet_at_64(pa):
@@ -446,7 +307,7 @@ def test_net_tiled_instances_of_the_scan(pa):
     same(got, want, "tiled, host")
     dev = net.tiled(pa.hip.asarray(img), batch=5, **case["tile"])
     assert all(isinstance(a, pa.hip.DeviceArray) for a in dev)
-    same(_host(dev), want, "tiled, device")
+    same(K.host(dev), want, "tiled, device")
     assert ref[1][0] >= 1
     with pytest.raises(NotImplementedError, match="different product"):      # resampled working sizes: refused as for labels
         net.tiled(img, window=16, sample=(50, 61))

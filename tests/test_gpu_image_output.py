@@ -13,12 +13,12 @@ import pytest
 
 from tests import image_input_ref as RI
 from tests import image_output_ref as R
+from tests.head_kit import framed_call
 
 pytestmark = pytest.mark.gpu
 
 T, L = R.tile_constants()   # PL_IMAGE_OUT_TILE_PIXELS, PL_IMAGE_OUT_LANE_PIXELS
-PAD = 64                    # sentinel bytes on either side of the output
-SENTINEL = 0xA5
+SENTINEL = 0xA5             # what framed_call fills the block around an output with
 K4 = np.array([-0.75, 2.0 ** 20, 2.0 ** -20, 58.4], np.float32)
 B4 = np.array([0.5, -3.0, 1e-3, 124.0], np.float32)
 OK, EINVAL, EUNSUPPORTED = 0, 1, 2
@@ -87,17 +87,6 @@ def _source(pa, host, off):
     return pa.hip.DeviceArray(host.shape, np.float32, buf.ctx, buf.ptr + 4 * off, buf)
 
 
-def _framed(pa, nbytes, y_off, call):
-    """Runs call(pointer to the output) on `nbytes` bytes framed by sentinels.  -> (status, output bytes, frame intact)."""
-    frame = pa.hip.empty((PAD + y_off + nbytes + PAD,), np.uint8)
-    frame.set(np.full(frame.shape, SENTINEL, np.uint8))
-    rc = call(frame.ptr + PAD + y_off)
-    got = frame.get()
-    lo = PAD + y_off
-    intact = bool((got[:lo] == SENTINEL).all() and (got[lo + nbytes:] == SENTINEL).all())
-    return rc, got[lo:lo + nbytes], intact
-
-
 def _image(pa, x, k, b, layout, order=None, trunc=False, y_off=0, raw=None):
     """pl_image_f32_u8 itself on a float32 DeviceArray.  `raw` overrides what the entry point is TOLD (refusals)."""
     lib, ctx = pa._lib.load(), pa.hip.context()
@@ -108,8 +97,8 @@ def _image(pa, x, k, b, layout, order=None, trunc=False, y_off=0, raw=None):
         n, c, h, w, co = [raw.get(key, v) for key, v in zip("n c h w co".split(), (n, c, h, w, co))]
     ka, ba = (ctypes.c_float * len(k))(*[float(v) for v in k]), (ctypes.c_float * len(b))(*[float(v) for v in b])
     oa = None if order is None else (ctypes.c_int * len(order))(*order)
-    return _framed(pa, nbytes, y_off, lambda y: lib.pl_image_f32_u8(ctx.handle, x.ptr, y, n, c, h, w, co, oa,
-                                                                    int(layout == "nhwc"), ka, ba, int(trunc)))
+    return framed_call(pa, (nbytes,), np.uint8, y_off, lambda y: lib.pl_image_f32_u8(ctx.handle, x.ptr, y, n, c, h, w, co, oa,
+                                                                                     int(layout == "nhwc"), ka, ba, int(trunc)))
 
 
 def _labels(pa, x, threshold=0.0, y_off=0, raw=None):
@@ -118,7 +107,7 @@ def _labels(pa, x, threshold=0.0, y_off=0, raw=None):
     nbytes = n * h * w
     if raw:
         n, c, h, w = [raw.get(key, v) for key, v in zip("n c h w".split(), (n, c, h, w))]
-    return _framed(pa, nbytes, y_off, lambda y: lib.pl_labels_f32_u8(ctx.handle, x.ptr, y, n, c, h, w, float(threshold)))
+    return framed_call(pa, (nbytes,), np.uint8, y_off, lambda y: lib.pl_labels_f32_u8(ctx.handle, x.ptr, y, n, c, h, w, float(threshold)))
 
 
 def _same(got, want):

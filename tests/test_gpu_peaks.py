@@ -8,26 +8,20 @@ before it is written shows up as a wrong answer and a write past a block as a di
 merge capacity and the row limit the header states.  Then nets: every call form against the reference applied to what a second,
 undeclared instance returns."""
 import functools
-import os
-import re
 
 import numpy as np
 import pytest
 
-from tests import image_input_ref as RI
+from tests import head_kit as K
 from tests import peaks_ref as R
-from tests.conftest import ROOT
+from tests.head_kit import EINVAL, EUNSUPPORTED, F32, I32, OK, Framed
 
 pytestmark = pytest.mark.gpu
 
-F32, I32 = np.float32, np.int32
-PAD = 16                                    # sentinel words on either side of an output
-SENT = np.uint32(0xA5A5A5A5)
-OK, EINVAL, EUNSUPPORTED = 0, 1, 2
+NAMES = ("peaks", "num")
 TIES, REFINE = {"all": 0, "first": 1}, {"none": 0, "quarter": 1}
 
-_H = open(os.path.join(ROOT, "include", "planer_hip.h")).read()
-_C = {k: int(v) for k, v in re.findall(r"#define (PL_PEAKS_[A-Z_]+) (\d+)", _H)}
+_C = K.header_constants("PL_PEAKS_")
 TH, TW, MERGE_KEYS, MAX_PEAKS, MAX_EXTENT = (_C["PL_PEAKS_" + k] for k in ("TILE_H", "TILE_W", "MERGE_KEYS", "MAX_PEAKS", "MAX_EXTENT"))
 
 MULTI_ROUND = (1, 1, TH, (MERGE_KEYS // MAX_PEAKS + 1) * TW)                   # tiles x MAX_PEAKS candidates > MERGE_KEYS
@@ -79,25 +73,6 @@ def cases(shape):
     return out
 
 
-class Framed:
-    """`words` 32-bit words on the device between two runs of PAD sentinel words, all of it the sentinel to begin with."""
-
-    def __init__(self, pa, words):
-        self.words = words
-        self.buf = pa.hip.empty((PAD + words + PAD,), np.uint32)
-        self.buf.set(np.full(self.buf.shape, SENT, np.uint32))
-        self.ptr = self.buf.ptr + 4 * PAD
-
-    def get(self, dtype, shape):
-        """(the words as `dtype`, whether both sentinel runs are intact)"""
-        raw = self.buf.get()
-        intact = bool((raw[:PAD] == SENT).all() and (raw[PAD + self.words:] == SENT).all())
-        return raw[PAD:PAD + self.words].view(dtype).reshape(shape), intact
-
-    def untouched(self):
-        return bool((self.buf.get() == SENT).all())
-
-
 def chain(pa, x, threshold, ties, max_peaks, refine, stride):
     """pl_peaks_f32 through the C interface on framed outputs and a poisoned scratch block.
     -> (status, (peaks, num), every frame intact)."""
@@ -114,11 +89,7 @@ def chain(pa, x, threshold, ties, max_peaks, refine, stride):
 
 
 def same(got, want, what):
-    for name, g, r in zip(("peaks", "num"), got, want):
-        assert g.shape == r.shape and g.dtype == r.dtype, (what, name, g.shape, r.shape, g.dtype, r.dtype)
-        bad = np.flatnonzero(g.view(np.uint32).ravel() != r.view(np.uint32).ravel())
-        assert bad.size == 0, "%s: %s differs at %d places, first flat index %d: got %r, want %r" % (
-            what, name, bad.size, bad[0], g.ravel()[bad[0]], r.ravel()[bad[0]])
+    K.same(got, want, NAMES, what)
 
 
 def test_the_case_list_covers_what_it_claims():
@@ -162,20 +133,8 @@ def test_chain_equals_the_reference(pa, shape):
 
 def test_hygiene_pass_over_every_case(pa):
     """util.heatmap_peaks on every case with the pool in hygiene mode: fresh blocks are poisoned and guarded."""
-    ctx = pa.hip.context()
-    ctx.synchronize()
-    ctx.pool_debug(pa.hip.POOL_GUARD_BYTES, 0xFF)
-    try:
-        got = [tuple(a.get() for a in pa.util.heatmap_peaks(pa.hip.asarray(x), t, ties, mp, refine, stride))
-               for shape in SHAPES for _, x, t, ties, mp, refine, stride, _ in cases(shape)]
-        dirty, report = ctx.pool_debug_check()
-    finally:
-        ctx.pool_debug(0)
-    assert dirty == 0, report
-    want = [(what, ref) for shape in SHAPES for what, *_, ref in cases(shape)]
-    assert len(got) == len(want) > 500
-    for g, (what, ref) in zip(got, want):
-        same(g, ref, what)
+    K.hygiene_pass(pa, [case for shape in SHAPES for case in cases(shape)],
+                   lambda x, *spec: pa.util.heatmap_peaks(pa.hip.asarray(x), *spec), NAMES, 500)
 
 
 def test_heatmap_peaks_on_two_three_and_four_dimensions(pa):
@@ -243,29 +202,14 @@ def test_refusals_leave_the_outputs_untouched(pa):
 
 def test_chain_replays_from_a_captured_graph(pa):
     """No host wait and no host-computed value: the two launches captured once answer for whatever is in their input at launch."""
-    from planer_amd import _lib
-    ctx = pa.hip.context()
     n, k, h, w, mp = 2, 2, TH + 5, 2 * TW + 4, 20
     maps = [R.random_maps(n, k, h, w, 21), R.constant(n, k, h, w), R.with_nan(n, k, h, w, TH, TW, 22), R.smooth_quantised(n, k, h, w, 23)]
     x = pa.hip.empty((n, k, h, w), F32)
     peaks, num = pa.hip.empty((n, k, mp, 3), F32), pa.hip.empty((n, k), I32)
     scratch = pa.hip.empty(((scratch_bytes(n, k, h, w, mp) + 7) // 8,), np.int64)
-    ctx.synchronize()
-    _lib.call("pl_capture_begin", ctx.handle)
-    graph = _lib.c_void_p()
-    try:
-        rc = _lib.load().pl_peaks_f32(ctx.handle, x.ptr, n, k, h, w, -0.5, 1, mp, 1, 4.0, 4.0, scratch.ptr, peaks.ptr, num.ptr)
-    finally:
-        end = _lib.load().pl_capture_end(ctx.handle, _lib.byref(graph))
-    assert rc == OK
-    _lib.check(end)
-    try:
-        for i, host in enumerate(maps):
-            x.set(host)
-            _lib.call("pl_graph_launch", graph)
-            same((peaks.get(), num.get()), R.peaks_ref(host, -0.5, "first", mp, "quarter", (4, 4)), "replay %d" % i)
-    finally:
-        _lib.check(_lib.load().pl_graph_destroy(graph))
+    K.replay_from_captured_graph(
+        pa, lambda: pa._lib.load().pl_peaks_f32(pa.hip.context().handle, x.ptr, n, k, h, w, -0.5, 1, mp, 1, 4.0, 4.0, scratch.ptr, peaks.ptr, num.ptr),
+        x, (peaks, num), maps, lambda host: R.peaks_ref(host, -0.5, "first", mp, "quarter", (4, 4)), NAMES)
 
 
 def test_a_large_map_with_a_known_answer(pa):
@@ -294,32 +238,6 @@ def test_a_large_map_with_a_known_answer(pa):
 SPEC = dict(threshold=0.0, ties="first", max_peaks=64, refine="quarter", stride=(2, 2))
 
 
-def tiny_net(outputs, seed=4):
-    """x (N, 3, 32, 32) -> conv 3x3 (8) + relu = f -> conv 3x3 (3) = s, the heat maps.  Small-integer filters and biases: with
-    integer inputs every partial sum is an exact float32, so two instances agree bit for bit whichever kernels they pick (the
-    trick of tests/test_gpu_conv_exact.py), and equal values are common: plateaus and ties in the order."""
-    from planer_amd.irgen.builder import GraphBuilder
-    rng = np.random.default_rng(seed)
-    g = GraphBuilder(["x"])
-    g.init("K0", rng.integers(-2, 3, (8, 3, 3, 3)).astype(F32))
-    g.init("B0", rng.integers(-3, 4, 8).astype(F32))
-    g.op("conv", ["x", "K0", "B0"], "c0", name="conv0", group=1, strides=[1, 1], dilations=[1, 1], pads=[1, 1, 1, 1])
-    g.op("relu", "c0", "f", name="relu0")
-    g.init("K1", rng.integers(-2, 3, (3, 8, 3, 3)).astype(F32))
-    g.init("B1", rng.integers(-3, 4, 3).astype(F32))
-    g.op("conv", ["f", "K1", "B1"], "s", name="conv1", group=1, strides=[1, 1], dilations=[1, 1], pads=[1, 1, 1, 1])
-    return g.finish(outputs)
-
-
-def tiny_input(seed=7):
-    x = np.random.default_rng(seed).integers(-3, 4, (2, 3, 8, 8)).astype(F32)
-    return np.ascontiguousarray(np.repeat(np.repeat(x, 4, 2), 4, 3))
-
-
-def _host(y):
-    return tuple(v.get() if hasattr(v, "get") else v for v in y)
-
-
 def _want(maps):
     ref = R.peaks_ref(maps, **SPEC)
     assert ref[1].min() >= 2 and (ref[1] > SPEC["max_peaks"]).any() and (ref[1] < SPEC["max_peaks"]).any(), ref[1]
@@ -328,78 +246,17 @@ def _want(maps):
 
 @pytest.mark.parametrize("streams", [None, "pipe2"])
 def test_tiny_net_every_call_form(pa, streams):
-    g, b = tiny_net(["f", "s"])
-    x = tiny_input()
-    net, plain = pa.from_graph(g, b), pa.from_graph(g, b)
-    if streams:
-        net.streams = plain.streams = streams
-    feat, maps = plain(x)
-    assert feat.shape == (2, 8, 32, 32) and maps.shape == (2, 3, 32, 32)
-    ref = _want(maps)
-
-    def check(y, what, on_device=False):
-        assert isinstance(y, tuple) and len(y) == 3, what
-        assert all(isinstance(v, pa.hip.DeviceArray if on_device else np.ndarray) for v in y), what
-        y = _host(y)
-        assert RI.same_bits(y[0], feat), what                                # the other output: untouched
-        same(y[1:], ref, what)
-
-    base = net(x)                                                            # a plan exists before the declaration
-    assert len(base) == 2 and RI.same_bits(base[1], maps)
-    before = dict(net._plans)
-    assert net.keypoint_output(index=1, **SPEC) is net
-    check(net(x), "host")
-    check(net(pa.asarray(x)), "device", True)
-    check(net({net.input[0]: x}), "dict")
-    check(net.submit(x).get(), "submit")
-    check(net.submit(pa.asarray(x)).result(), "submit device", True)
-    pend = [net.submit(x) for _ in range(3)]                                 # several in flight
-    for p in pend:
-        check(p.get(), "submits in flight")
-    net.compile(pa.asarray(x))
-    check(net(pa.asarray(x)), "compile + replay", True)
-    check(net(pa.asarray(x)), "replay again", True)
-    assert all(net._plans[key] is before[key] for key in before)             # the declaration touched no plan
-    for got, want in zip(plain.submit(x).get(), (feat, maps)):               # (the plain net's throughput plan: the same maps)
-        assert RI.same_bits(got, want)
-    assert sorted(net._plans, key=repr) == sorted(plain._plans, key=repr)
-    for how in ("debug", "eager"):                                           # the eager routes
-        if how == "eager":
-            net.use_graph = False
-        check(net(x, debug=True) if how == "debug" else net(x), how)
-    net.use_graph = True
-    # float_output restores the float tensor
-    assert net.float_output(1) is net
-    for got, want in zip(net(x), (feat, maps)):
-        assert RI.same_bits(got, want)
-    for got, want in zip(net.submit(x).get(), (feat, maps)):
-        assert RI.same_bits(got, want)
-    # checks come before anything is launched: a position the net does not have
-    net.keypoint_output(index=2, **SPEC)
-    for call in (lambda: net(x), lambda: net(pa.asarray(x)), lambda: net.submit(x), lambda: net(x, debug=True)):
-        with pytest.raises(ValueError, match="returns 2"):
-            call()
-    pa.hip.trim_side_contexts()
+    K.check_every_call_form(pa, streams, lambda net, **at: net.keypoint_output(**at, **SPEC), _want, NAMES)
 
 
 def test_one_output_net_and_uint8_input(pa):
-    g, b = tiny_net(["s"])
-    net, plain = pa.from_graph(g, b), pa.from_graph(g, b)
-    k, bb = np.ones(3, F32), np.zeros(3, F32)                               # the bytes as they are: integers
-    net.image_input(k, bb).keypoint_output(**SPEC)
-    i = np.arange(2 * 8 * 8 * 3, dtype=np.int64)
-    x = ((i * 37 + i // 192 * 53 + 11) % 256).astype(np.uint8).reshape(2, 8, 8, 3)
-    x = np.ascontiguousarray(np.repeat(np.repeat(x, 4, 1), 4, 2))
-    maps = plain(RI.decode32(x, k, bb))
-    ref = R.peaks_ref(maps, **SPEC)
-    assert ref[1].min() >= 1
-    for what, y in (("host", net(x)), ("device", net(pa.asarray(x))), ("submit", net.submit(x).get()), ("float in", net(RI.decode32(x, k, bb)))):
-        assert len(y) == 2, what
-        same(_host(y), ref, what)
-    peaks, num = net(x)
-    assert peaks.shape == (2, 3, 64, 3) and num.shape == (2, 3)
-    # util.KeypointSpec on its own, on the float maps
-    same(_host(pa.util.KeypointSpec(**SPEC).encode(pa.asarray(maps))), ref, "KeypointSpec.encode")
+    def mirror(maps):
+        ref = R.peaks_ref(maps, **SPEC)
+        assert ref[1].min() >= 1
+        return ref
+
+    net, x = K.check_one_output_net_and_uint8_input(pa, lambda net: net.keypoint_output(**SPEC), mirror, NAMES, [(2, 3, 64, 3), (2, 3)],
+                                                    pa.util.KeypointSpec(**SPEC))
     # Net.tiled says that it does not take the declaration
     with pytest.raises(ValueError, match="keypoint output is declared"):
         net.tiled(x[0], window=16)

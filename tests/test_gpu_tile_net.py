@@ -11,11 +11,12 @@ import numpy as np
 import pytest
 
 from tests import tile_net_ref as T
+from tests.head_kit import framed_call
 
 pytestmark = pytest.mark.gpu
 
-PAD = 64                     # sentinel elements on either side of an output
-SENT8, SENT32 = 0xA5, 0xA5A5A5A5
+PAD = 64                     # sentinel elements on either side of an input
+SENT8 = 0xA5
 K4 = np.array([-0.75, 2.0 ** 20, 2.0 ** -20, 58.4], np.float32)
 B4 = np.array([0.5, -3.0, 1e-3, 124.0], np.float32)
 SPECIALS = np.array([np.nan, np.inf, -np.inf, -0.0, 0.0], np.float32)
@@ -52,21 +53,6 @@ def _inside(pa, host, off):
     return view, lambda: bool((buf.get().view(np.uint8) == flat.view(np.uint8)).all())
 
 
-def _framed(pa, shape, dtype, off, call):
-    """Runs call(pointer) on an output of `shape` framed by sentinels, `off` elements into its block.  -> (array, frame intact)."""
-    dtype = np.dtype(dtype)
-    size = int(np.prod(shape))
-    word = np.uint8 if dtype == np.uint8 else np.uint32
-    frame = pa.hip.empty((PAD + off + size + PAD,), word)
-    frame.set(np.full(frame.shape, SENT8 if dtype == np.uint8 else SENT32, word))
-    call(frame.ptr + (PAD + off) * dtype.itemsize)
-    got = frame.get()
-    lo = PAD + off
-    sent = SENT8 if dtype == np.uint8 else SENT32
-    intact = bool((got[:lo] == sent).all() and (got[lo + size:] == sent).all())
-    return got[lo:lo + size].view(dtype).reshape(shape), intact
-
-
 def _same(got, want):
     assert got.shape == want.shape and got.dtype == want.dtype, (got.shape, want.shape, got.dtype, want.dtype)
     if got.dtype == np.float32:
@@ -82,7 +68,7 @@ def _cut(pa, host, off, windows, k=None, b=None, order=None, work=None, slots=No
     dev, unchanged = _inside(pa, host, off)
     spec = pa.util.ImageSpec(k, b, "nhwc", None, order) if host.dtype == np.uint8 else None
     feed = pa.util.WindowFeed(dev, windows, spec, work, slots)
-    got, intact = _framed(pa, feed.shape, np.float32, y_off, feed.decode_into)
+    _, got, intact = framed_call(pa, feed.shape, np.float32, y_off, feed.decode_into)
     assert intact and unchanged()
     whole = pa.util.cut_windows(dev, windows, k, b, order, work, slots)
     assert isinstance(whole, pa.hip.DeviceArray) and whole.shape == feed.shape
@@ -126,7 +112,7 @@ def test_cut_windows_odd_window_sizes_and_more_slots_than_windows(pa):
     _same(_cut(pa, fimg, 1, windows, slots=11), T.cut_ref(fimg, windows, slots=11))
     feed = pa.util.WindowFeed(pa.hip.asarray(img), windows, pa.util.ImageSpec(k, b))
     for lo, slots in ((0, 4), (4, 4), (8, 4), (7, 1)):                     # chunks as Net.tiled cuts them: the last one padded
-        got, intact = _framed(pa, (slots, 3, 7, 9), np.float32, 0, feed.chunk(lo, slots).decode_into)
+        _, got, intact = framed_call(pa, (slots, 3, 7, 9), np.float32, 0, feed.chunk(lo, slots).decode_into)
         assert intact
         _same(got, T.cut_ref(img, windows[lo:lo + slots], k, b, slots=slots))
     with pytest.raises(ValueError, match="slots"):
@@ -188,9 +174,8 @@ def _blend(pa, x, geo, k, form, x_off=0, y_off=0):
         ka, ba = (ctypes.c_float * co)(*kk.tolist()), (ctypes.c_float * co)(*bb.tolist())
         oa = None if order is None else (ctypes.c_int * co)(*order)
         call = lambda y: lib.pl_tile_blend_u8(ctx.handle, dev.ptr, y, *args, co, oa, int(layout == "nhwc"), ka, ba, int(trunc))  # noqa: E731
-    status = []
-    got, intact = _framed(pa, shape, dtype, y_off, lambda y: status.append(call(y)))
-    assert status == [0] and intact and unchanged()
+    status, got, intact = framed_call(pa, shape, dtype, y_off, call)
+    assert status == 0 and intact and unchanged()
     whole = pa.util.blend_windows(dev, geo.windows, k, geo.margin, geo.work, _out_spec(pa, form))
     _same(whole.get(), got)
     return got
