@@ -36,7 +36,7 @@
 //     carries a two-row item of chunk c + 1 in pieces behind single MFMAs of chunk c (mma_weave: reads, first stage column by
 //     column, second stage, V writes; scheduling barriers pin the pieces).  One branch-free instruction stream for all four
 //     waves: an item's kind is per-wave DATA (row bases, coefficients; the three-row kind reads its fourth row out of 1 KB of
-//     -0.0 behind the patch buffer), wave 0 repeats wave 1's item.  256 registers, no scratch in the K loop.  Per conv alone /
+//     -0.0 behind the patch buffer), wave 0 repeats wave 1's item.  No scratch.  Per conv alone /
 //     per 32 images at batch 256: layer1 37.0 / 30.3 against 38.7 / 31.9 us, layer2 41.1 / 26.7 against 44.0 / 27.6 us
 //     (profiles/wf4_weave.md).
 //   * The PHASED K step (mma_ga; PLANER_HIP_EXPERIMENT=wf4_weave=0, and the 32-tile block always): the transform is a phase of
@@ -44,6 +44,15 @@
 //     in front of their MFMAs.  32 tiles: six one-row items (wf4_transform_row2: lane = tile x channel pair) -- waves 4-7 rows
 //     0-3 BEFORE their 36 MFMAs of chunk c, waves 0-1 rows 4-5 after theirs, so that the two waves of a SIMD alternate on its
 //     matrix pipe.  The woven step is bit-identical to the phased one (tests/test_gpu_wf4_weave.py).
+//   * HEAD AND TAIL of the 16-tile block (a layer1 block issues as many vector instructions outside its 16 K steps as inside,
+//     beside the sibling workgroup's K loop; profiles/wf4_head_tail.md): the accumulators are never cleared -- K step 0 is a copy
+//     of the step that multiplies into a literal zero; after the loop the first stage of A^T m A runs ONCE over the
+//     accumulators, in place (wf4_column_sums: 156 packed operations where the row-by-row form of the 32-tile block spends 204),
+//     which frees the registers that used to spill in the output rows: 238-244 registers, no scratch anywhere; the four store
+//     offsets of output row 0 are computed once and rows 1-3 add the row pitch (no multiply, no branch inside the rows); scale
+//     and shift of the straight-line tail come by one range-checked 16-byte load each.  The last K step still carries its
+//     transform item: peeling it as well makes the register allocator copy the accumulators (240-510 spilled registers).
+//     The 32-tile block keeps the head and tail these replaced, value for value the same.
 //   * Fragment reads of V are conflict free by layout: a lane's 36 frequencies of one (k, tile) are 144 consecutive bytes.
 //   * What a K step of the 32-tile block with the filter in LDS cost (profiles/r04_wf4_knockout.md): 1.00 us of MFMAs + 0.36
 //     fragment reads + 0.38 transform + 0.13 both LDS-DMA streams = 1.61 us; fp32 MFMAs do not overlap with the other vector
@@ -320,6 +329,45 @@ __device__ __forceinline__ void wf4_output_row_coalesced(const Wf4Args &p, const
     wf4_row_finish<RES, PLAIN>(p, slo, shi, cqc, scale, shift, xb, wr_cell, rd_cell, yrsrc, rrsrc, off);
 }
 
+// 16-tile blocks: the column sums of A^T m A ONCE for all four output rows, in place -- wf4_at2 over acc[a * 6 + b], a = 0 .. 5, per
+// column b and channel pair, its four results back into acc[A * 6 + b], A = 0 .. 3.  wf4_at2's expressions are those of
+// wf4_at_row2<0 .. 3>, so every value is what the row-by-row form computes (which redoes m1 +- m2 and m3 +- m4 in each of the four
+// rows: 204 packed operations against 156); rows 4 and 5 of the accumulators are free afterwards.
+__device__ __forceinline__ void wf4_column_sums(f32x4 (&acc)[36]) {
+#pragma unroll
+    for (int b = 0; b < 6; ++b) {
+        wf4_v2 m[6], lo[4], hi[4];
+#pragma unroll
+        for (int a = 0; a < 6; ++a) m[a] = __builtin_shufflevector(acc[a * 6 + b], acc[a * 6 + b], 0, 1);
+        wf4_at2(m, lo);
+#pragma unroll
+        for (int a = 0; a < 6; ++a) m[a] = __builtin_shufflevector(acc[a * 6 + b], acc[a * 6 + b], 2, 3);
+        wf4_at2(m, hi);
+#pragma unroll
+        for (int A = 0; A < 4; ++A) acc[A * 6 + b] = (f32x4){lo[A].x, lo[A].y, hi[A].x, hi[A].y};
+        // column by column: all six at once keep some forty temporaries alive beside the 144 accumulators, and the kernel spills.
+        // (An empty statement that "uses" this column's results and "defines" the next column's inputs: nothing is emitted, and it
+        // is what keeps the order -- a scheduling barrier does not bind plain arithmetic before instruction selection.)
+        if (b < 5)
+            asm volatile("" : "+v"(acc[b]), "+v"(acc[6 + b]), "+v"(acc[12 + b]), "+v"(acc[18 + b]),
+                              "+v"(acc[b + 1]), "+v"(acc[6 + b + 1]), "+v"(acc[12 + b + 1]), "+v"(acc[18 + b + 1]),
+                              "+v"(acc[24 + b + 1]), "+v"(acc[30 + b + 1]));
+    }
+}
+// output row A from the sums wf4_column_sums left in acc[A * 6 + b]
+template <int A, bool RES, bool PLAIN>
+__device__ __forceinline__ void wf4_output_row_summed(const Wf4Args &p, const f32x4 (&acc)[36], int cqc, float4 scale, float4 shift,
+                                                      float4 *xb, int wr_cell, int rd_cell, const __amdgpu_buffer_rsrc_t yrsrc,
+                                                      const __amdgpu_buffer_rsrc_t rrsrc, const int (&off)[4]) {
+    wf4_v2 slo[6], shi[6];
+#pragma unroll
+    for (int b = 0; b < 6; ++b) {
+        slo[b] = __builtin_shufflevector(acc[A * 6 + b], acc[A * 6 + b], 0, 1);
+        shi[b] = __builtin_shufflevector(acc[A * 6 + b], acc[A * 6 + b], 2, 3);
+    }
+    wf4_row_finish<RES, PLAIN>(p, slo, shi, cqc, scale, shift, xb, wr_cell, rd_cell, yrsrc, rrsrc, off);
+}
+
 // Variants (compile-time; the launcher picks one per block width, so that every patch read is base + immediate): PACK -- spare
 // slot columns carry a donor image's tiles (Wf4Args); HALF -- 16 tiles on four waves instead of 32 on eight; WEAVE -- the woven
 // K step instead of the phased one.
@@ -418,20 +466,6 @@ __device__ __forceinline__ void conv_wf4_body(const Wf4Args &p) {
     //      B^T d B is ONE wave-item: six per step -- waves 4-7 rows 0-3, waves 0-1 rows 4-5.  16 tiles: three two-row items
     //      (wf4_transform_2rows) on waves 1-3, or the same items woven into every wave's MFMAs ----
     constexpr int rs = 16 * S, psz = 4 * S;                      // floats per patch row, per x phase
-    // NOT PART OF THE KERNEL: nothing reads pb0.  These lines are what is left of a dropped transform's lane bases (tile = lane / 4,
-    // channel = lane % 4).  The values are dead, but the compiler merges the epilogue's lane / 4, lane % 4 and tile coordinates
-    // with them before it drops them, and that decides where those sit in 14 of the 21 instantiations: without these lines
-    // the 14 come out with other register numbers and a few instructions in another order (same instructions, same registers,
-    // LDS and scratch).  They go with the next change that is allowed to alter the device code.
-    const int ti = lane >> 2, tch = lane & 3;
-    auto item_base = [&](int &pbase) {
-        const int t_nb = ti >> lT, t_r = (ti >> LBC) & BRm;
-        int t_c = ti & BCm;
-        if (PACK && t_c >= p.tw) t_c += 1;
-        pbase = tch + (((t_nb * p.R + 4 * t_r) * 4) * S + t_c) * 4;
-    };
-    int pb0;
-    item_base(pb0);
     int pb2 = 0, vb2 = 0;
     const int hr = lane >> 5;                                    // HALF: which row of its pair this lane transforms
     if constexpr (HALF) {
@@ -493,9 +527,12 @@ __device__ __forceinline__ void conv_wf4_body(const Wf4Args &p) {
         else if (wave == 1) wf4_transform_row2<5, rs, psz>(Pb, Vb, pb2, vb2);
     };
 
+    // 16-tile blocks never clear the accumulators: their first K step multiplies into a literal zero (FIRST below)
     f32x4 acc[36];
+    if constexpr (!HALF) {
 #pragma unroll
-    for (int f = 0; f < 36; ++f) acc[f] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        for (int f = 0; f < 36; ++f) acc[f] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    }
     const int b_off = ((wn * 4 + lk) * 16 + li) * 36;      // this lane's 36 frequencies of V[k = lk][tile 16 wn + li]
     // filter fragments: u[cout block][chunk][wm][g = 4 frequencies][lane][4] -- group g of chunk c for this wave is ONE load
     // instruction over a contiguous 1 KB; a ring of AHEAD + 1 register slots, the load for group G + AHEAD goes out when group
@@ -510,9 +547,18 @@ __device__ __forceinline__ void conv_wf4_body(const Wf4Args &p) {
         ga[decltype(slot)::value] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(ursrc, ga_voff, soff, 0));
     };
     // the phased K step's MFMAs: 9 groups of 4, chunk c + 2's patch requests behind the first groups
-    auto mma_ga = [&](auto parity, int c, bool more2) {
+    auto mma_ga = [&](auto parity, auto first, int c, bool more2) {
         constexpr int par = decltype(parity)::value;
+        constexpr bool FIRST = decltype(first)::value;
         constexpr bool NOFRAG = (WF4_KNOCK & 16) != 0, NOMMA = (WF4_KNOCK & 8) != 0;
+        auto cin = [&](int f) -> f32x4 {             // FIRST: the step multiplies into a literal zero, acc is written before it is read
+            if constexpr (FIRST) return (f32x4){0.f, 0.f, 0.f, 0.f};
+            else return acc[f];
+        };
+        if constexpr (NOMMA && FIRST) {
+#pragma unroll
+            for (int f = 0; f < 36; ++f) acc[f] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        }
         const float4 *Vp = reinterpret_cast<const float4 *>((par ? Vs1 : Vs0) + b_off);
         float4 fb[3];
         if constexpr (NOFRAG) {
@@ -543,10 +589,10 @@ __device__ __forceinline__ void conv_wf4_body(const Wf4Args &p) {
             if constexpr (NOMMA) {
                 acc[4 * g + 0].x += a.x * b.x; acc[4 * g + 1].x += a.y * b.y; acc[4 * g + 2].x += a.z * b.z; acc[4 * g + 3].x += a.w * b.w;
             } else {
-            acc[4 * g + 0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, acc[4 * g + 0], 0, 0, 0);
-            acc[4 * g + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b.y, acc[4 * g + 1], 0, 0, 0);
-            acc[4 * g + 2] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b.z, acc[4 * g + 2], 0, 0, 0);
-            acc[4 * g + 3] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b.w, acc[4 * g + 3], 0, 0, 0);
+            acc[4 * g + 0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, cin(4 * g + 0), 0, 0, 0);
+            acc[4 * g + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b.y, cin(4 * g + 1), 0, 0, 0);
+            acc[4 * g + 2] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b.z, cin(4 * g + 2), 0, 0, 0);
+            acc[4 * g + 3] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b.w, cin(4 * g + 3), 0, 0, 0);
             }
             __builtin_amdgcn_sched_barrier(0);
             if (g < WF4_P_PASSES) {
@@ -569,9 +615,18 @@ __device__ __forceinline__ void conv_wf4_body(const Wf4Args &p) {
     // hide).  So wave 0 repeats wave 1's item (same values to the same cells) and the last step transforms a patch nobody
     // multiplies (V[nxt] is free until the epilogue's barrier).  Every slot ends in a scheduling barrier, so the pieces stay where
     // they are put; the step's closing barrier publishes V[nxt] as before.
-    auto mma_weave = [&](auto parity, int c, bool more2) {
+    auto mma_weave = [&](auto parity, auto first, int c, bool more2) {
         constexpr int par = decltype(parity)::value;
+        constexpr bool FIRST = decltype(first)::value;
         constexpr bool NOFRAG = (WF4_KNOCK & 16) != 0, NOMMA = (WF4_KNOCK & 8) != 0, ITEM = (WF4_KNOCK & 4) == 0;
+        auto cin = [&](int f) -> f32x4 {
+            if constexpr (FIRST) return (f32x4){0.f, 0.f, 0.f, 0.f};
+            else return acc[f];
+        };
+        if constexpr (NOMMA && FIRST) {
+#pragma unroll
+            for (int f = 0; f < 36; ++f) acc[f] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        }
         const float4 *Vp = reinterpret_cast<const float4 *>((par ? Vs1 : Vs0) + b_off);
         const float *Pn = par ? Ps0 : Ps1;
         float *v0 = (par ? Vs0 : Vs1) + wv_vb, *v1 = v0 + 16 * 36;
@@ -643,13 +698,13 @@ __device__ __forceinline__ void conv_wf4_body(const Wf4Args &p) {
 #pragma unroll
                 for (int h = 0; h < 4; ++h) item_slot(4 * g + h);
             } else {
-                acc[4 * g + 0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, acc[4 * g + 0], 0, 0, 0);
+                acc[4 * g + 0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, cin(4 * g + 0), 0, 0, 0);
                 item_slot(4 * g + 0);
-                acc[4 * g + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b.y, acc[4 * g + 1], 0, 0, 0);
+                acc[4 * g + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b.y, cin(4 * g + 1), 0, 0, 0);
                 item_slot(4 * g + 1);
-                acc[4 * g + 2] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b.z, acc[4 * g + 2], 0, 0, 0);
+                acc[4 * g + 2] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b.z, cin(4 * g + 2), 0, 0, 0);
                 item_slot(4 * g + 2);
-                acc[4 * g + 3] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b.w, acc[4 * g + 3], 0, 0, 0);
+                acc[4 * g + 3] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b.w, cin(4 * g + 3), 0, 0, 0);
                 item_slot(4 * g + 3);
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -685,7 +740,9 @@ __device__ __forceinline__ void conv_wf4_body(const Wf4Args &p) {
     //  the default policy -- neighbouring workgroups share halo pixels and every workgroup the filter -- sc0 39.2 us)
     // one K step; the buffer parity is a compile-time constant, so the compiler can tell the LDS-DMA destination (P[cur]) from
     // what the step reads and writes (V[cur], P[nxt], V[nxt]) and lets the DMA fly
-    auto kstep = [&](auto parity, int c) {
+    // FIRST (16-tile blocks; a compile-time copy of the step): the block's first step multiplies into a literal zero instead of
+    // cleared accumulators -- fma(a, b, +0) either way.
+    auto kstep = [&](auto parity, int c, auto first) {
         constexpr int cur = decltype(parity)::value, nxt = cur ^ 1;
         const bool more = c + 1 < p.nchunks, more2 = c + 2 < p.nchunks;
         // P[cur] was last read by the transform of chunk c: free for the whole step.  Phased: waves 4-7 (16 tiles: 1-3) transform
@@ -695,9 +752,9 @@ __device__ __forceinline__ void conv_wf4_body(const Wf4Args &p) {
         if (!WEAVE && more) transform_first(nxt, nxt);
         WF4_STEP_MARK(c, 1);
         if constexpr (WEAVE) {
-            mma_weave(parity, c, more2);           // every wave carries its item of chunk c + 1 inside its own MFMA stream
+            mma_weave(parity, first, c, more2);           // every wave carries its item of chunk c + 1 inside its own MFMA stream
         } else {
-            mma_ga(parity, c, more2);
+            mma_ga(parity, first, c, more2);
         }
         WF4_STEP_MARK(c, 2);
         if (more) transform_last(nxt, nxt);
@@ -708,9 +765,26 @@ __device__ __forceinline__ void conv_wf4_body(const Wf4Args &p) {
     // 32-tile blocks: static priority for the waves that multiply first (0-3; their SIMD partners 4-7 open every step with the
     // patch transform): 39.2 -> 38.5-38.8 us per layer1 conv; the other half at priority 1 instead: 41.3 us
     if (!HALF && wave < 4) __builtin_amdgcn_s_setprio(1);
-    for (int c = 0; c < p.nchunks; c += 2) {
-        kstep(std::integral_constant<int, 0>{}, c);
-        if (c + 1 < p.nchunks) kstep(std::integral_constant<int, 1>{}, c + 1);
+    {
+        constexpr std::integral_constant<int, 0> even{};
+        constexpr std::integral_constant<int, 1> odd{};
+        constexpr std::false_type no{};
+        constexpr std::true_type yes{};
+        if constexpr (HALF) {
+            // step c keeps parity c & 1 (the filter ring's slots and the buffers are the unpeeled loop's): step 0 on its own, then
+            // pairs (odd, even).  (The last step peeled as well, without its item: the register allocator copies the accumulators
+            // at the joins, 240-510 spilled registers in either loop form tried -- profiles/wf4_head_tail.md.)
+            kstep(even, 0, yes);
+            for (int c = 1; c < p.nchunks; c += 2) {
+                kstep(odd, c, no);
+                if (c + 1 < p.nchunks) kstep(even, c + 1, no);
+            }
+        } else {
+            for (int c = 0; c < p.nchunks; c += 2) {
+                kstep(even, c, no);
+                if (c + 1 < p.nchunks) kstep(odd, c + 1, no);
+            }
+        }
     }
 
     // ---- lane-local output transform; fused tail and stores through the wave's exchange buffer ----
@@ -722,8 +796,19 @@ __device__ __forceinline__ void conv_wf4_body(const Wf4Args &p) {
         __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.ep.res), 0, p.ep.res ? p.y_bytes : 0u, 0x00020000);
     const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f), one4 = make_float4(1.f, 1.f, 1.f, 1.f);
     const bool plain = !p.ep.bias && p.ep.scale && p.ep.shift && p.ep.act == 1 && !(p.ep.res && p.ep.res_post);
-    const float4 scale = plain ? reinterpret_cast<const float4 *>(p.ep.scale)[cqc] : one4;      // the straight-line tail's
-    const float4 shift = plain ? reinterpret_cast<const float4 *>(p.ep.shift)[cqc] : z4;        // parameters, held in registers
+    float4 scale, shift;                       // the straight-line tail's parameters, held in registers
+    if constexpr (HALF) {
+        // one range-checked 16-byte load each, no branch: only the straight-line tail reads them, and elsewhere the empty range
+        // gives zeros without touching memory
+        const unsigned par_bytes = plain ? (unsigned)p.Coq * 16u : 0u;
+        const __amdgpu_buffer_rsrc_t scrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.ep.scale), 0, par_bytes, 0x00020000);
+        const __amdgpu_buffer_rsrc_t shrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.ep.shift), 0, par_bytes, 0x00020000);
+        scale = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(scrsrc, cqc << 4, 0, 0));
+        shift = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(shrsrc, cqc << 4, 0, 0));
+    } else {
+        scale = plain ? reinterpret_cast<const float4 *>(p.ep.scale)[cqc] : one4;
+        shift = plain ? reinterpret_cast<const float4 *>(p.ep.shift)[cqc] : z4;
+    }
     // the K loop is over: V (and, for 16-tile blocks, P) is free -- 4.25 KB of exchange buffer per wave
     float4 *xb = HALF ? reinterpret_cast<float4 *>(wave == 0 ? Vs0 : wave == 1 ? Vs1 : wave == 2 ? Ps0 : Ps1)
                       : reinterpret_cast<float4 *>(wave < 4 ? Vs0 : Vs1) + (wave & 3) * (4 * 68);
@@ -739,16 +824,35 @@ __device__ __forceinline__ void conv_wf4_body(const Wf4Args &p) {
     }
     const int x2 = tx2 * 4 + be, cq0 = (int)coutblk * 16 + wm * 4;
     const bool ok2 = n2 < p.N && ty2 < p.th && tx2 < p.tw && x2 < p.W;
+    // 16-tile blocks: the first stage of A^T m A once, and row 0's four store offsets once -- row A adds A row pitches and selects
+    // the out-of-range offset where the row is off the map (an out-of-range offset stays one with three pitches added: the
+    // tensor is below 2 GB), no branch inside the rows
+    int off0[4] = {OOB, OOB, OOB, OOB};
+    if constexpr (HALF) {
+        wf4_column_sums(acc);
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            if (ok2 && cq0 + q < p.Coq)
+                off0[q] = (int)((((unsigned)(n2 * p.Coq + cq0 + q) * (unsigned)p.H + (unsigned)(ty2 * 4)) * (unsigned)p.W + (unsigned)x2) << 4);
+    }
     auto row = [&](auto first, auto res, auto pl) {
         constexpr int A = decltype(first)::value;
         const int yy = ty2 * 4 + A;
         int off[4];
+        if constexpr (HALF) {
+            const bool in = yy < p.H;
 #pragma unroll
-        for (int q = 0; q < 4; ++q)
-            off[q] = (ok2 && yy < p.H && cq0 + q < p.Coq)
-                         ? (int)((((unsigned)(n2 * p.Coq + cq0 + q) * (unsigned)p.H + (unsigned)yy) * (unsigned)p.W + (unsigned)x2) << 4) : OOB;
-        wf4_output_row_coalesced<A, decltype(res)::value, decltype(pl)::value>(p, acc, cqc, scale, shift, xb, lk * 16 + li,
-                                                                              be * 68 + te, yrsrc, rrsrc, off);
+            for (int q = 0; q < 4; ++q) off[q] = in ? (int)((unsigned)off0[q] + (unsigned)(A * p.W) * 16u) : OOB;
+            wf4_output_row_summed<A, decltype(res)::value, decltype(pl)::value>(p, acc, cqc, scale, shift, xb, lk * 16 + li,
+                                                                               be * 68 + te, yrsrc, rrsrc, off);
+        } else {
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                off[q] = (ok2 && yy < p.H && cq0 + q < p.Coq)
+                             ? (int)((((unsigned)(n2 * p.Coq + cq0 + q) * (unsigned)p.H + (unsigned)yy) * (unsigned)p.W + (unsigned)x2) << 4) : OOB;
+            wf4_output_row_coalesced<A, decltype(res)::value, decltype(pl)::value>(p, acc, cqc, scale, shift, xb, lk * 16 + li,
+                                                                                  be * 68 + te, yrsrc, rrsrc, off);
+        }
     };
     auto rows = [&](auto res, auto pl) {
         row(std::integral_constant<int, 0>{}, res, pl);
