@@ -401,3 +401,181 @@ def drawn_geometries(count=24, seed=31337):
 def geometries():
     return FIXED_GEOMETRIES + drawn_geometries()
 
+
+
+# ---- operands on which the F(4,3) / F(3,3) Winograd pipelines are exact in fp32 -------------------------------------------------
+# Filters whose nonzero taps are +-576 = +-24^2.  The filter kernels (wf4_filter_kernel, wino4_filter_q4_kernel, w43_g, the
+# packer of conv_w1d_kernel.h) apply G in two stages with every product rounded on its own (no contraction), e.g.
+#     g0 * (1.f/24.f) + g1 * (1.f/12.f) + g2 * (1.f/6.f)        -(g0 + g1 + g2) * (1.f/6.f)
+# fl(1/6), fl(1/12), fl(1/24), fl(1/3), fl(2/3) share one mantissa (1.0101...b rounded up) with a relative error of exactly 2^-25,
+# less than half an ulp of any product, so fl(c) * (24 m) rounds to the integer 24 m c: stage one leaves multiples of 24, stage
+# two integers (1/4 and 1/2 are exact).  B^T and A^T are integer matrices, the inputs integers: where the pipeline with every
+# matrix and operand replaced by its absolute value stays below 2^24, every partial sum in any order is an integer below 2^24 and
+# so exact -- a kernel of these families must then equal `ref64` in every bit (tests/test_gpu_wino_exact.py).
+WINO_TAP = 576.0
+WINO_CAP = 2.0 ** 24
+# (24 G) of _F[m], integer: U = (24 G) g (24 G)^T / 576 in exact float64 arithmetic
+_G24 = {1: 24.0 * np.eye(3), 3: np.rint(24.0 * _F[3][1]), 4: np.rint(24.0 * _F[4][1])}
+# the segment sizes (rows, columns) of a family's tiles
+WINO_CLASSES = {"f4x4": [(4, 4)], "w1d4": [(1, 4)], "wino43": [(4, 4), (4, 3), (3, 4), (3, 3)]}
+
+
+def _g_f32(m, g0, g1, g2):
+    """G g along the leading axis for F(m, 3), in float32 the way the kernels write it: every product and sum rounded."""
+    f = np.float32
+    one = f(1.0)
+    c2, c4, c6, c12, c24, c3, c23 = f(0.5), f(0.25), one / f(6), one / f(12), one / f(24), one / f(3), f(2) / f(3)
+    if m == 1:
+        return np.stack([g0, g1, g2])
+    if m == 4:
+        return np.stack([g0 * c4, -(g0 + g1 + g2) * c6, (-g0 + g1 - g2) * c6, g0 * c24 + g1 * c12 + g2 * c6,
+                         g0 * c24 - g1 * c12 + g2 * c6, g2])
+    assert m == 3, m
+    return np.stack([g0 * c2, -(g0 + g1 + g2) * c2, (-g0 + g1 - g2) * c6, g0 * c6 + g1 * c3 + g2 * c23, g2])
+
+
+def wino_filter_f32(K, fam):
+    """G g G^T of the (Cout, Cin, 3, 3) filter K for every tile class of `fam`, evaluated the way the filter kernels write it:
+    G along the filter's rows first, then along its columns, each stage in float32 with separate products.
+    -> {(mr, mc): (Cout, Cin, mr + 2 | 3, mc + 2) float32} (a 1-D family keeps its other axis: 3 rows)."""
+    K = np.asarray(K, np.float32)
+    out = {}
+    for mr, mc in WINO_CLASSES[fam]:
+        t = _g_f32(mr, K[:, :, 0, :], K[:, :, 1, :], K[:, :, 2, :])                # (fr, co, c, 3)
+        u = _g_f32(mc, t[..., 0], t[..., 1], t[..., 2])                            # (fc, fr, co, c)
+        assert u.dtype == np.float32
+        out[(mr, mc)] = np.ascontiguousarray(u.transpose(2, 3, 1, 0))
+    return out
+
+
+def wino_filter_f64(K, fam):
+    """The same U in exact arithmetic: (24 G) g (24 G)^T / 576 on float64 integers -- every step exact where g is integer."""
+    K = _f64(K)
+    return {(mr, mc): np.einsum("ai,ocij,bj->ocab", _G24[mr], K, _G24[mc]) / 576.0 for mr, mc in WINO_CLASSES[fam]}
+
+
+def _wino_tiles(xp, rows, cols, mr, mc):
+    """The (mr + 2) x (mc + 2) input patches of the tiles of class (mr, mc) in the padded map xp -> (n, c, R, S, mr + 2, mc + 2),
+    with the output offsets of the R tile rows and S tile columns."""
+    ro = [o for o, m in zip(np.cumsum([0] + rows[:-1]), rows) if m == mr]
+    co = [o for o, m in zip(np.cumsum([0] + cols[:-1]), cols) if m == mc]
+    ar = 3 if mr == 1 else mr + 2
+    iy = np.asarray(ro, int)[:, None] + np.arange(ar)[None]
+    ix = np.asarray(co, int)[:, None] + np.arange(mc + 2)[None]
+    return xp[:, :, iy[:, None, :, None], ix[None, :, None, :]], ro, co
+
+
+def wino_pipeline(x, U, fam, dtype, mats=_F, order=None):
+    """The tiled pipeline Y = A^T [sum_c U_c * (B^T d_c B)] A of `fam` with the transformed filters U (wino_filter_*) given, all in
+    `dtype`, the channel sum as a running sum in `order` (default: ascending).  -> (y, top): y (N, Cout, H, W) without bias, and
+    the largest magnitude among V, U, the running sums and y's tiles."""
+    x = np.asarray(x, dtype)
+    n, cin, h, w = x.shape
+    rows, cols = wino_family(fam, h, w)
+    H, W = sum(rows), sum(cols)
+    xp = np.zeros((n, cin, H + 2, W + 2), dtype)
+    xp[:, :, 1:1 + h, 1:1 + w] = x
+    cout = next(iter(U.values())).shape[0]
+    out = np.zeros((n, cout, H, W), dtype)
+    top = 0.0
+    for (mr, mc), u in U.items():
+        d, ro, co = _wino_tiles(xp, rows, cols, mr, mc)
+        if not ro or not co:
+            continue
+        BTr, _, ATr = (m.astype(dtype) for m in mats[mr])
+        BTc, _, ATc = (m.astype(dtype) for m in mats[mc])
+        u = np.asarray(u, dtype)
+        V = np.einsum("ai,ncrsij,bj->ncrsab", BTr, d, BTc).astype(dtype)
+        if order is None and dtype == np.float64:
+            # the whole channel sum per frequency at once (a bound: the operands are non-negative, or the sums exact)
+            M = np.empty((n, cout) + V.shape[2:], dtype)
+            for a in range(V.shape[4]):
+                for b in range(V.shape[5]):
+                    M[..., a, b] = np.tensordot(V[..., a, b], u[:, :, a, b], axes=([1], [1])).transpose(0, 3, 1, 2)
+            top = max(top, float(np.abs(M).max(initial=0.0)))
+        else:
+            M = np.zeros((n, cout) + V.shape[2:], dtype)
+            for c in (range(cin) if order is None else order):
+                M += u[None, :, c, None, None] * V[:, None, c]
+                top = max(top, float(np.abs(M).max(initial=0.0)))
+        assert M.dtype == dtype
+        Y = np.einsum("ia,norsab,jb->norsij", ATr, M, ATc).astype(dtype)
+        top = max(top, float(np.abs(V).max(initial=0.0)), float(np.abs(u).max(initial=0.0)), float(np.abs(Y).max(initial=0.0)))
+        for r, oy in enumerate(ro):
+            for s, ox in enumerate(co):
+                out[:, :, oy:oy + mr, ox:ox + mc] = Y[:, :, r, s]
+    return out[:, :, :h, :w], top
+
+
+def wino_abs_top(fam, x, K):
+    """The cap's left side: the pipeline of `fam` with every matrix and operand replaced by its absolute value (what
+    wino_emulate_abs computes tile by tile, here per tile class at once) -> its largest value."""
+    mats = {m: tuple(np.abs(a) for a in f) for m, f in _F.items()}
+    uabs = {k: np.einsum("ai,ocij,bj->ocab", np.abs(_F[k[0]][1]), np.abs(_f64(K)), np.abs(_F[k[1]][1])) for k in WINO_CLASSES[fam]}
+    return wino_pipeline(np.abs(_f64(x)), uabs, fam, np.float64, mats)[1]
+
+
+def wino_exact_operands(rng, xs, cout, bias=False, bn=False, res=False):
+    """Operands on which the F(4,3) / F(3,3) pipelines are exact (above) for a 3x3 / pad 1 conv of input xs -> (x, K, B, scale,
+    shift, res).  Narrow recipe (Cin <= 20): per output channel min(Cin, 12) randomly chosen input channels carry two random taps
+    of +-576 each, x in [-2, 2] ([-3, 3] for Cin <= 8).  Wide recipe (Cin above 20; meant for 64 .. 256): 24 input channels per
+    output channel, one tap each, x in [-1, 1].  The live channels differ per output channel, so that no K chunk is idle."""
+    n, cin, h, w = xs
+    narrow = cin <= 20
+    live, taps, xmax = (min(cin, 12), 2, 3 if cin <= 8 else 2) if narrow else (min(cin, 24), 1, 1)
+    x = int_tensor(rng, xs, -xmax, xmax)
+    K = np.zeros((cout, cin, 9), np.float32)
+    for co in range(cout):
+        for c in rng.choice(cin, live, replace=False):
+            K[co, c, rng.choice(9, taps, replace=False)] = rng.choice([-WINO_TAP, WINO_TAP], taps)
+    return (x, K.reshape(cout, cin, 3, 3)) + int_tail(rng, cout, (n, cout, h, w), bias, bn, res)
+
+
+def wino_exact_assert(fam, x, K, B=None, scale=None, shift=None, res=None):
+    """The precondition of bit-exactness for family `fam` in {"f4x4", "w1d4", "wino43"}: the filter transform as the kernels
+    evaluate it (wino_filter_f32) equals the exact U and is integer; the pipeline in absolute values stays below 2^24; and the
+    tail's absolute bound -- conv(|x|, |K|) + |B| through max(|scale|, 1), |shift| and |res|, which covers the tail with any of
+    its terms left out -- stays below 2^24 units of 0.25 * ALPHA (the finest grain: a leaky value in quarters times 1/8)."""
+    u32, u64 = wino_filter_f32(K, fam), wino_filter_f64(K, fam)
+    for k in u64:
+        assert u32[k].dtype == np.float32 and u32[k].shape == u64[k].shape, k
+        np.testing.assert_array_equal(u32[k].astype(np.float64), u64[k], err_msg="%s filter transform, class %s" % (fam, k))
+        assert np.all(u64[k] == np.rint(u64[k])), "%s: U is not integer" % fam
+    assert np.all(_f64(x) == np.rint(_f64(x))), "x is not integer"
+    top = wino_abs_top(fam, x, K)
+    assert top < WINO_CAP, "%s: |pipeline| reaches %g = %.3f * 2^24" % (fam, top, top / WINO_CAP)
+    t = conv64(np.abs(x), np.abs(K), pads=[1, 1, 1, 1])
+    if B is not None:
+        t = t + np.abs(_chan(B))
+    if scale is not None:
+        t = t * np.maximum(np.abs(_chan(scale)), 1.0)
+    if shift is not None:
+        t = t + np.abs(_chan(shift))
+    if res is not None:
+        t = t + np.abs(_f64(res)).reshape(t.shape)
+    tail = float(t.max(initial=0.0)) / (0.25 * ALPHA)
+    assert tail < WINO_CAP, "%s: the tail reaches %g units of 1/32" % (fam, tail)
+    return top / WINO_CAP
+
+
+def wino43_input(x, absolute=False):
+    """B^T d B of every mixed tile of x (pad 1; sides 7, 14 or 21) in float64, in the layout of q4.Wino43In: [121][C/4][T][4] --
+    frequency groups 0..35 the F(4)xF(4) tiles, 36..65 F(4) rows x F(3) columns, 66..95 F(3) x F(4), 96..120 F(3) x F(3), each
+    a * nb + b; T = (n, tile row, tile column) of the class, H/7 x W/7 tiles an image; channels zero padded to whole quads.
+    `absolute`: |B^T| in place of B^T (a bound on the transform of |x|)."""
+    n, c, h, w = x.shape
+    ar, ac, cq = h // 7, w // 7, -(-c // 4)
+    xp = np.zeros((n, cq * 4, h + 2, w + 2))
+    xp[:, :c, 1:1 + h, 1:1 + w] = x
+    rows, cols = SEGMENTS["wino43"](h), SEGMENTS["wino43"](w)
+    out = np.zeros((121, cq, n * ar * ac, 4))
+    fb = {(4, 4): 0, (4, 3): 36, (3, 4): 66, (3, 3): 96}
+    for (mr, mc), base in fb.items():
+        d, ro, co = _wino_tiles(xp, rows, cols, mr, mc)                              # (n, C, ar, ac, mr + 2, mc + 2)
+        btr, btc = _F[mr][0], _F[mc][0]
+        if absolute:
+            btr, btc = np.abs(btr), np.abs(btc)
+        v = np.einsum("ai,ncrsij,bj->abncrs", btr, d, btc)
+        v = v.reshape((mr + 2) * (mc + 2), n, cq, 4, ar * ac).transpose(0, 2, 1, 4, 3)
+        out[base:base + (mr + 2) * (mc + 2)] = v.reshape(-1, cq, n * ar * ac, 4)
+    return out

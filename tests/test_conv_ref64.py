@@ -2,6 +2,7 @@
 float32 oracle inside bound(LAMBDA["direct"]), each Winograd LAMBDA against a float32 emulation of its transforms, and
 mutations that the per-element check catches and the per-tensor assert_close (1e-4 of max|ref|) lets through."""
 import zlib
+from fractions import Fraction
 
 import numpy as np
 import pytest
@@ -190,3 +191,115 @@ def test_check_reports_the_worst_element_and_treats_signed_zeros_as_equal():
         R.check(y, ref, 0.0, "probe", "plan-x")
     with pytest.raises(AssertionError, match=r"probe \[plan-x\].*err/tol 2"):
         R.check(y, ref, np.full(ref.shape, 5e-4), "probe", "plan-x")
+
+
+# ---- operands on which the F(4,3) / F(3,3) Winograd pipelines are exact (tests/test_gpu_wino_exact.py) -----------------------------
+def _wino_exact_cases():
+    from tests.test_gpu_wino_exact import FAMILIES
+    return sorted(FAMILIES.items())
+
+
+@pytest.mark.parametrize("shape,fams", _wino_exact_cases(), ids=["x".join(map(str, s)) for s, _ in _wino_exact_cases()])
+def test_wino_exact_precondition_holds_on_every_gpu_shape(shape, fams):
+    """For every shape the GPU module runs and every family it runs it on: the filter transform as the kernels write it is the
+    exact integer U, the pipeline in absolute values stays below 2^24, the tail below 2^24 of its grain; and every input channel
+    is live in some output channel's filter for Cin <= 128 (no idle K chunk)."""
+    from tests.test_gpu_wino_exact import operands
+    ops = operands(shape)
+    x, K = ops[:2]
+    assert set(np.unique(np.abs(K)).tolist()) <= {0.0, R.WINO_TAP} and np.all(x == np.round(x))
+    for fam in sorted(fams):
+        frac = R.wino_exact_assert(fam, *ops)
+        assert 0.0 < frac < 1.0
+    if shape[1] <= 128:
+        assert (K != 0).any(axis=(0, 2, 3)).all(), "an input channel no filter reads"
+    assert len({tuple(np.flatnonzero((K[co] != 0).any(axis=(1, 2)))) for co in range(shape[4])}) > (1 if shape[1] > 12 and shape[4] > 1 else 0)
+
+
+def test_wino_exact_precondition_holds_on_the_phases_of_the_folded_convs():
+    from tests.test_gpu_wino_exact import FOLD_SIDES, fold_phases, operands
+    for side in FOLD_SIDES:
+        shape = (2, 16, side, side, 16)
+        _, K, _, sc, sh, _ = operands(shape)
+        phases = list(fold_phases(shape))
+        assert len(phases) == 4 and all(p.shape == (2, 16, -(-side // 2), -(-side // 2)) for p in phases)
+        assert sum(float(np.abs(p).sum()) for p in phases) == float(np.abs(operands(shape)[0]).sum())
+        for xph in phases:
+            R.wino_exact_assert("f4x4", xph, K, None, sc, sh, xph)
+
+
+def test_wino_exact_precondition_is_a_real_check():
+    rng = np.random.default_rng(9)
+    x, K, B, sc, sh, r = R.wino_exact_operands(rng, (1, 64, 8, 8), 4, True, True, True)
+    R.wino_exact_assert("f4x4", x, K, B, sc, sh, r)
+    dense = np.full((4, 64, 3, 3), R.WINO_TAP, np.float32)
+    with pytest.raises(AssertionError, match="pipeline"):             # every tap live: the Winograd-domain sums pass 2^24
+        R.wino_exact_assert("f4x4", np.full((1, 64, 8, 8), 3.0, np.float32), dense)
+    for tap in (100.0, 577.0, 1.0):                                    # taps that are no multiple of 576: G g G^T is rounded
+        Kbad = K.copy()
+        Kbad[Kbad != 0] = tap
+        with pytest.raises(AssertionError, match="filter transform"):
+            R.wino_exact_assert("f4x4", x, Kbad)
+    with pytest.raises(AssertionError, match="tail"):
+        R.wino_exact_assert("f4x4", x, K, None, np.full(4, 2.0 ** 10, np.float32), sh, None)
+
+
+def test_rounded_winograd_constants_times_multiples_of_24_are_exact():
+    """fl(c) * (24 m) is the integer 24 m c for c in {1/6, 1/12, 1/24, 1/3, 2/3}, |m| <= 4096: each constant is off by exactly
+    2^-25 of itself (one mantissa, 1.0101...b rounded up), less than half an ulp of the product."""
+    f = np.float32
+    m = np.arange(-4096, 4097)
+    v = (24 * m).astype(np.float32)
+    for num, den in ((1, 6), (1, 12), (1, 24), (1, 3), (2, 3)):
+        c = f(num) / f(den)
+        assert c.dtype == np.float32
+        rel = (Fraction(float(c)) - Fraction(num, den)) / Fraction(num, den)          # exact rational arithmetic
+        assert rel == Fraction(1, 2 ** 25), (num, den, rel)
+        got = v * c
+        assert got.dtype == np.float32
+        np.testing.assert_array_equal(got.astype(np.int64), 24 * m * num // den, err_msg="%d/%d" % (num, den))
+        assert np.all(got == np.round(got))
+
+
+@pytest.mark.parametrize("fam", ["f4x4", "w1d4", "wino43"])
+def test_float32_winograd_emulation_is_bit_exact_on_the_exact_operands(fam):
+    """The premise of tests/test_gpu_wino_exact.py: with U from wino_filter_f32 (the kernels' two-stage float32 transform), a running
+    channel sum and the integer B^T / A^T, all in float32, the pipeline gives the float64 conv in every bit, whatever the order of
+    the channel sum (ascending, descending and shuffled)."""
+    rng = np.random.default_rng(43)
+    shapes = [(2, 4, 8, 8), (2, 20, 8, 8), (1, 8, 13, 17), (2, 16, 9, 10), (1, 64, 7, 7)]
+    if fam == "wino43":
+        shapes = [(1, 64, 7, 7), (2, 16, 14, 7), (1, 8, 21, 14)]
+    for xs in shapes:
+        x, K, B, sc, sh, r = R.wino_exact_operands(rng, xs, 8, True, True, True)
+        R.wino_exact_assert(fam, x, K, B, sc, sh, r)
+        want = R.conv64(x, K, pads=[1, 1, 1, 1])
+        u = R.wino_filter_f32(K, fam)
+        for order in (range(xs[1]), range(xs[1] - 1, -1, -1), rng.permutation(xs[1])):
+            got, top = R.wino_pipeline(x, u, fam, np.float32, order=list(order))
+            assert got.dtype == np.float32 and top < R.WINO_CAP
+            np.testing.assert_array_equal(got.astype(np.float64), want, err_msg="%s %s" % (fam, xs))
+        # and ref64.wino_emulate, whose U comes from a float32 matmul with the rounded G, is NOT this check: not asserted exact
+
+
+@pytest.mark.parametrize("fam", ["f4x4", "w1d4", "wino43"])
+def test_wino_abs_top_is_the_maximum_of_wino_emulate_abs(fam):
+    """On maps of whole tiles the two agree; where tiles run past the map, wino_emulate_abs crops them and the cap counts them whole."""
+    rng = np.random.default_rng(8)
+    for xs, whole in [((2, 8, 14, 7), fam == "wino43"), ((1, 20, 8, 12), True), ((1, 8, 9, 10), False), ((2, 4, 5, 2), False)]:
+        if fam == "wino43" and (xs[2] % 7 or xs[3] % 7):
+            continue
+        x, K = R.wino_exact_operands(rng, xs, 6)[:2]
+        a = R.wino_emulate_abs(np.abs(x.astype(np.float64)), K.astype(np.float64), *R.wino_family(fam, xs[2], xs[3]))
+        top = R.wino_abs_top(fam, x, K)
+        assert top >= a.max() and (top == a.max() or not whole), (fam, xs, top, a.max())
+
+
+def test_mixed_tile_input_reference_agrees_with_the_f4x4_one_on_its_shared_tiles():
+    """wino43_input's F(4) x F(4) class on a 7 x 7 map is the first tile of wino4_input (same 6 x 6 patch, same B^T)."""
+    rng = np.random.default_rng(12)
+    x = rng.integers(-3, 4, (2, 6, 7, 7)).astype(np.float64)
+    v43, v4 = R.wino43_input(x), R.wino4_input(x)
+    assert v43.shape == (121, 2, 2, 4) and v4.shape == (36, 2, 8, 4)
+    np.testing.assert_array_equal(v43[:36], v4[:, :, [0, 4], :])
+    assert np.all(R.wino43_input(np.abs(x), True) >= np.abs(v43))

@@ -6,8 +6,9 @@ The 32-tile block (PLANER_HIP_EXPERIMENT=wf4_half=0) keeps the head and tail the
 bit, before this change or after it: the 32-tile block transforms patch rows 1-4 as c (d1 +- d2) + (d4 +- d3) (wf4_bt_row2), the
 16-tile block as c1 d1 + (c2 d2 + (c3 d3 + d4)) (wf4_transform_2rows and the woven item), which rounds differently.  So both
 forms are held to the oracle (util.conv_for + layer.BatchNorm / Add / ReLU / LeakyReLU) at the bound of tests/test_gpu_wf4.py,
-3e-5 of max|ref|, and that the 16-tile block computes bit for bit what it computed before rests on comparing dumps of the
-two builds (profiles/wf4_head_tail.md)."""
+3e-5 of max|ref|, on float data.  On operands where every sum is exact whatever its grouping, both forms -- and the phased and
+the plain-block ones -- must equal float64, and so each other, in every bit: tests/test_gpu_wino_exact.py
+(test_fused_kernel_every_form_and_tail) holds them to that on these shapes."""
 import numpy as np
 import pytest
 
