@@ -872,6 +872,51 @@ int pl_peaks_f32(pl_ctx *ctx, const float *x, int N, int K, int H, int W, double
 int pl_flow_instances_f32(pl_ctx *ctx, const float *x, int N, int H, int W, long long image_stride, long long pixel_stride,
                           long long off_dy, long long off_dx, long long off_prob, double level, double min_flow, int rounds,
                           int min_size, int max_instances, void *scratch, int *masks, int *num, int *instances, float *centres);
+/* ---- text as net output ----
+ * pl_ctc_greedy_f32: greedy CTC decoding of S = S_outer S_inner sequences of T frames over C classes.  Element (so, si, t, c) of
+ * the float32 x is at so st_outer + si st_inner + t st_time + c st_class, strides in elements; sequence s = so S_inner + si.  The
+ * layouts are stride sets: (T, N, C) is S_outer = N, S_inner = 1, st_outer = C, st_time = N C, st_class = 1; (N, T, C) is
+ * st_outer = T C, st_time = C; (N, C, H, W) with a line per (n, h) and time along W is S_outer = N, S_inner = H,
+ * st_outer = C H W, st_inner = W, st_time = 1, st_class = H W.
+ *   frame label       numpy's argmax over the C classes of frame (s, t): the first of equal maxima, the first NaN before any
+ *                     number, -0.0 ties with +0.0 (the rule of pl_labels_f32_u8).
+ *   frame confidence  with m the frame's maximum.  PL_TEXT_CONF_SOFTMAX: 1 / sum_c exp(x_c - m), NaN when m is not finite (the
+ *                     one result that is not exact: a float32 sum in the kernel's order).  PL_TEXT_CONF_VALUE: the bits of x at
+ *                     the argmax.  PL_TEXT_CONF_NONE: +0.0, and the exponentials are skipped.
+ *   valid length      len[s] = min(lengths[s], T), a negative lengths[s] counting as 0; T where lengths is null.  Frames at or
+ *                     past len do not exist: they are neither read nor decoded.
+ *   symbols           frame t < len starts a symbol iff label[t] != blank and (t == 0 or label[t] != label[t - 1] or
+ *                     merge_repeated == 0).  Its run ends at the first later frame whose label differs, or at len; with
+ *                     merge_repeated == 0 at t + 1.
+ *   length int32 (S): all symbols of the sequence; it may exceed max_len.
+ *   text   int32 (S, max_len): the labels of the first max_len symbols, -1 behind them.
+ *   conf   float32 (S, max_len): the confidence of each symbol's first frame, +0.0 behind.
+ *   spans  int32 (S, max_len, 2): [start, end) in frames, 0 behind.
+ * All four are written completely and nothing relies on zeroed memory.  Asynchronous on ctx's stream; two launches, a frame pass
+ * and a collapse pass (one where S T == 0), no global atomics, no host wait: capturable into a hipGraph.
+ * scratch: PL_TEXT_SCRATCH_BYTES(S, T) bytes of the caller's, 4-byte aligned, contents irrelevant: frame labels, then frame
+ * confidences.
+ * The frame pass has two forms.  st_class == 1: a frame is a row of C floats, read once in 16-byte words between a peeled head
+ * and tail, by one wave where C <= PL_TEXT_ROW_WAVE_MAX and by a workgroup above.  Otherwise a workgroup takes
+ * PL_TEXT_TIME_LANES consecutive frames of a sequence and splits the classes over its PL_TEXT_TIME_GROUPS lane groups.
+ * The collapse pass is one workgroup per sequence, PL_TEXT_CHUNK frames at a time.
+ * PL_EINVAL: a null pointer other than lengths, a negative dimension, C < 1, blank outside [0, C), max_len < 1, a confidence
+ * code outside PL_TEXT_CONF_*.  PL_EUNSUPPORTED: max_len > PL_TEXT_MAX_LEN, T > PL_TEXT_MAX_FRAMES (2^20: a collapse
+ * workgroup walks at most 4096 chunks), S T C >= 2^31.  S == 0: PL_OK, no launch; T == 0: length = 0 and the filler rows.  Every
+ * refusal comes before any launch and leaves the outputs untouched. */
+#define PL_TEXT_MAX_LEN 1024
+#define PL_TEXT_MAX_FRAMES 1048576
+#define PL_TEXT_CHUNK 256
+#define PL_TEXT_ROW_WAVE_MAX 1024
+#define PL_TEXT_TIME_LANES 32
+#define PL_TEXT_TIME_GROUPS 32
+#define PL_TEXT_CONF_NONE 0
+#define PL_TEXT_CONF_SOFTMAX 1
+#define PL_TEXT_CONF_VALUE 2
+#define PL_TEXT_SCRATCH_BYTES(S, T) ((size_t)(S) * (size_t)(T) * 8)
+int pl_ctc_greedy_f32(pl_ctx *ctx, const float *x, int S_outer, int S_inner, int T, int C, long long st_outer, long long st_inner,
+                      long long st_time, long long st_class, const int *lengths, int blank, int merge_repeated, int confidence,
+                      int max_len, void *scratch, int *text, int *length, float *conf, int *spans);
 /* split-K combine + epilogue (internal to conv, exported for tests) */
 int pl_splitk_reduce_f32(pl_ctx *ctx, const float *ws, int splits, float *y,
                          int N, int C, int inner, const float *bias,

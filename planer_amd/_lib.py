@@ -35,6 +35,13 @@ PEAKS_REFINE = {"none": 0, "quarter": 1}  # include/planer_hip.h PL_PEAKS_REFINE
 FLOW_SCAN_STEP = 1024               # include/planer_hip.h PL_FLOW_SCAN_STEP
 FLOW_MAX_ROUNDS = 30                # include/planer_hip.h PL_FLOW_MAX_ROUNDS
 FLOW_MAX_INSTANCES = 65536          # include/planer_hip.h PL_FLOW_MAX_INSTANCES
+TEXT_MAX_LEN = 1024                 # include/planer_hip.h PL_TEXT_MAX_LEN
+TEXT_MAX_FRAMES = 1 << 20           # include/planer_hip.h PL_TEXT_MAX_FRAMES
+TEXT_CHUNK = 256                    # include/planer_hip.h PL_TEXT_CHUNK
+TEXT_ROW_WAVE_MAX = 1024            # include/planer_hip.h PL_TEXT_ROW_WAVE_MAX
+TEXT_TIME_LANES = 32                # include/planer_hip.h PL_TEXT_TIME_LANES
+TEXT_TIME_GROUPS = 32               # include/planer_hip.h PL_TEXT_TIME_GROUPS
+TEXT_CONF = {"none": 0, "softmax": 1, "value": 2}   # include/planer_hip.h PL_TEXT_CONF_*
 ACT_NONE, ACT_RELU, ACT_LEAKY = 0, 1, 2
 ACT_RES_AFTER = 16
 UNIQUE_ID_BYTES = 128
@@ -213,6 +220,7 @@ SIGNATURES = {
     "pl_components_u8_i32": [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
     "pl_peaks_f32": [_P, _P, _I, _I, _I, _I, c_double, _I, _I, _I, c_double, c_double, _P, _P, _P],
     "pl_flow_instances_f32": [_P, _P, _I, _I, _I] + [c_longlong] * 5 + [c_double, c_double, _I, _I, _I, _P, _P, _P, _P, _P],
+    "pl_ctc_greedy_f32": [_P, _P, _I, _I, _I, _I] + [c_longlong] * 4 + [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P],
     "pl_tile_accumulate_f32": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I],
     "pl_tile_normalise_f32": [_P, _P, _P, _I, _I, _I],
     "pl_tile_windows_u8_nchw_f32": [_P, _P, _P, _I, _I, _I, _I, POINTER(c_int), _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P,

@@ -13,6 +13,7 @@
 #include "detect_kernel.h"
 #include "components_kernel.h"
 #include "flow_kernel.h"
+#include "text_kernel.h"
 #include "peaks_kernel.h"
 #include "tile_kernel.h"
 
@@ -1191,6 +1192,58 @@ int pl_peaks_f32(pl_ctx *ctx, const float *x, int N, int K, int H, int W, double
                                                                      counts);
     pk::merge_kernel<<<(unsigned)planes, pk::TPB, 0, ctx->stream>>>(x, keys, counts, g, max_peaks, refine == PL_PEAKS_REFINE_QUARTER, (float)sy,
                                                                    (float)sx, peaks, num);
+    PL_LAUNCH_CHECK();
+    return PL_OK;
+}
+
+// float32 sequence tensor -> greedy CTC text (text_kernel.h).  Every refusal comes before any launch.
+int pl_ctc_greedy_f32(pl_ctx *ctx, const float *x, int S_outer, int S_inner, int T, int C, long long st_outer, long long st_inner,
+                      long long st_time, long long st_class, const int *lengths, int blank, int merge_repeated, int confidence,
+                      int max_len, void *scratch, int *text, int *length, float *conf, int *spans) {
+    namespace tx = text;
+    PL_REQUIRE(ctx && x && scratch && text && length && conf && spans, PL_EINVAL, "pl_ctc_greedy_f32: null argument");
+    PL_REQUIRE(S_outer >= 0 && S_inner >= 0 && T >= 0 && C >= 1, PL_EINVAL, "pl_ctc_greedy_f32: bad shape: %d x %d sequences, %d frames, %d classes",
+               S_outer, S_inner, T, C);
+    PL_REQUIRE(blank >= 0 && blank < C, PL_EINVAL, "pl_ctc_greedy_f32: blank = %d is no class of %d", blank, C);
+    PL_REQUIRE(max_len >= 1, PL_EINVAL, "pl_ctc_greedy_f32: max_len = %d is below 1", max_len);
+    PL_REQUIRE(confidence == PL_TEXT_CONF_NONE || confidence == PL_TEXT_CONF_SOFTMAX || confidence == PL_TEXT_CONF_VALUE, PL_EINVAL,
+               "pl_ctc_greedy_f32: confidence is 0 (none), 1 (softmax) or 2 (value), got %d", confidence);
+    PL_REQUIRE(max_len <= PL_TEXT_MAX_LEN, PL_EUNSUPPORTED, "pl_ctc_greedy_f32: at most %d symbols per sequence, got max_len = %d",
+               PL_TEXT_MAX_LEN, max_len);
+    PL_REQUIRE(T <= PL_TEXT_MAX_FRAMES, PL_EUNSUPPORTED, "pl_ctc_greedy_f32: at most %d frames, got %d", PL_TEXT_MAX_FRAMES, T);
+    const size_t S = (size_t)S_outer * S_inner, frames = S * T;
+    PL_REQUIRE(S < (1ull << 31) && frames < (1ull << 31) && frames * C < (1ull << 31), PL_EUNSUPPORTED,
+               "pl_ctc_greedy_f32: 2^31 or more sequences, frames or elements");
+    if (S == 0) return PL_OK;
+    tx::Geo g;
+    g.S_inner = S_inner, g.T = T, g.C = C;
+    g.st_outer = st_outer, g.st_inner = st_inner, g.st_time = st_time, g.st_class = st_class;
+    int *labels = reinterpret_cast<int *>(scratch);
+    float *confs = reinterpret_cast<float *>(labels + frames);
+    const bool sum = confidence == PL_TEXT_CONF_SOFTMAX;
+    CtxGuard guard(ctx);
+    if (frames) {
+        if (st_class == 1 && C <= tx::ROW_WAVE_MAX) {
+            const unsigned grid = (unsigned)cdiv(frames, (size_t)tx::WAVES);
+            if (sum)
+                tx::rows_wave_kernel<true><<<grid, tx::TPB, 0, ctx->stream>>>(x, g, frames, lengths, confidence, labels, confs);
+            else
+                tx::rows_wave_kernel<false><<<grid, tx::TPB, 0, ctx->stream>>>(x, g, frames, lengths, confidence, labels, confs);
+        } else if (st_class == 1) {
+            if (sum)
+                tx::rows_block_kernel<true><<<(unsigned)frames, tx::TPB, 0, ctx->stream>>>(x, g, lengths, confidence, labels, confs);
+            else
+                tx::rows_block_kernel<false><<<(unsigned)frames, tx::TPB, 0, ctx->stream>>>(x, g, lengths, confidence, labels, confs);
+        } else {
+            const unsigned spans_t = (unsigned)cdiv(T, tx::TIME_LANES), grid = (unsigned)(S * spans_t);   // (below 2^31: no more than frames)
+            if (sum)
+                tx::time_kernel<true><<<grid, tx::TIME_TPB, 0, ctx->stream>>>(x, g, spans_t, lengths, confidence, labels, confs);
+            else
+                tx::time_kernel<false><<<grid, tx::TIME_TPB, 0, ctx->stream>>>(x, g, spans_t, lengths, confidence, labels, confs);
+        }
+    }
+    tx::collapse_kernel<<<(unsigned)S, tx::TPB, 0, ctx->stream>>>(labels, confs, T, lengths, blank, merge_repeated != 0, confidence, max_len, text,
+                                                                 length, conf, spans);
     PL_LAUNCH_CHECK();
     return PL_OK;
 }

@@ -1183,6 +1183,13 @@ def LSTM(X, W, R, B=0, sequence_lens=0, initial_h=0, initial_c=0, hidden_size=No
     for i, d in enumerate(dirs):
         gx = Dense(X2, W[i], None) if L else None                   # (L*N, 4H): every step's x_t W^T
         ht, ct = initial_h[i], initial_c[i]
+        if ht.ctx is not X.ctx:
+            # an initial state that is an init of a Net lives in the net's own context, and Dense launches where its first
+            # operand lives: seen from X's context the first step's h R^T is enqueued on X's stream like every other step (a
+            # throughput plan captures on a replica's stream, and a launch elsewhere is not part of its graph).  Reading the
+            # other context's memory from X's stream is ordered the way the reads of W, R and B are: an init was uploaded and
+            # synchronised when the net was loaded, long before any pass
+            ht = DeviceArray(ht.shape, ht.dtype, ctx=X.ctx, ptr=ht.ptr, base=ht)
         for t in list(range(L))[::d]:
             gh = Dense(ht, R[i], None)
             h_new, c_new = Y[t][i], empty((1, N, H), ctx=X.ctx)

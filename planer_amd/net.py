@@ -30,7 +30,7 @@ from . import q4 as _q4
 from .conv_layouts import DIRECT_Q4, IGEMM_NCHW, LAYOUTS, STEM_POOL, STEM_POOL_NCHW, WINO4_Q4, WINO43_Q4, experiment, suffix
 from .layer import layer_map, wrap
 from .plan import compile_front, fuse_upsample_concat, lower
-from .util import BlendGeometry, DetectionSpec, FlowSpec, ImageFeed, ImageOutSpec, ImageSpec, KeypointSpec, LabelSpec, ObjectSpec, WindowFeed, _Tiling
+from .util import BlendGeometry, DetectionSpec, FlowSpec, ImageFeed, ImageOutSpec, ImageSpec, KeypointSpec, LabelSpec, ObjectSpec, TextSpec, WindowFeed, _Tiling
 from .util import blend_windows as _blend_windows, resize as _resize
 
 STEM_WINO_DEFAULT = 1      # whether the stem + max-pool step takes the F(4,4) form where it applies
@@ -369,8 +369,8 @@ class Net:
         self._image_in = {}          # input key (None: the first input) -> util.ImageSpec: uint8 batches that input also takes
         self._image_out = {}         # output position -> util.ImageOutSpec / util.LabelSpec: that output comes back as uint8;
                                      # util.ObjectSpec: as labels, num, objects, centroids in its place; util.KeypointSpec: as
-                                     # peaks, num; util.FlowSpec: as masks, num, instances, centres (a spec's `places` says how
-                                     # many arrays it hands back)
+                                     # peaks, num; util.FlowSpec: as masks, num, instances, centres; util.TextSpec: as text,
+                                     # length, conf, spans (a spec's `places` says how many arrays it hands back)
         self._detect = None          # (util.DetectionSpec, positions of its heads or None: every output): they come back as det, num
 
     # ---- loading ----------------------------------------------------------------
@@ -487,6 +487,20 @@ class Net:
         self._image_out[self._unclaimed(index)] = spec
         return self
 
+    def text_output(self, layout="tnc", blank=0, merge_repeated=True, confidence="softmax", max_len=64, index=0):
+        """Output number `index`, a float32 sequence tensor -- `layout` "tnc" (T, N, C), "ntc" (N, T, C), or "nchw" (N, C, H, W)
+        with one sequence per (n, h) and time along W -- comes back as text by greedy CTC decoding, four arrays in its place,
+        `lead` being (N,) or for "nchw" (N, H): text int32 lead + (max_len,), the labels of the first `max_len` symbols and -1
+        behind them; length int32 lead, all symbols of the sequence, which may exceed max_len; conf float32 lead + (max_len,),
+        the confidence of each symbol's first frame; spans int32 lead + (max_len, 2), [start, end) in frames.  A frame's label
+        is numpy's argmax over the classes; a symbol starts where the label is not `blank` and, with `merge_repeated`, differs
+        from the frame in front.  `confidence` "softmax": 1 / sum exp(x - max); "value": x at the argmax; "none": +0.0
+        (util.TextSpec: pl_ctc_greedy_f32).  For a one-output net: text, length, conf, spans = net(x); util.text_strings makes
+        strings of the first two.  `Net.tiled` refuses a net with this declared.  See `image_output`."""
+        spec = TextSpec(layout, blank, merge_repeated, confidence, max_len)
+        self._image_out[self._unclaimed(index)] = spec
+        return self
+
     def float_output(self, index=0):
         """Output number `index` comes back as the float32 tensor again; if it is a head of a detection declaration, so do all
         of that declaration's heads."""
@@ -530,7 +544,7 @@ class Net:
         num (1,), objects (1, max_objects, 6) and centroids (1, max_objects, 2); with `flow_output` the instances of the blended flow and
         probability planes (the windows are blended as floats, then one chain follows the whole map), masks (OH, OW), num (1,),
         instances (1, max_instances, 5) and centres (1, max_instances, 2).  Host image in, host array out; device in, device out.
-        A declared `keypoint_output` raises ValueError: peaks of a blended scan are not built.
+        A declared `keypoint_output` raises ValueError: peaks of a blended scan are not built; so does a declared `text_output`.
         Every chunk runs the plan of ONE signature, (batch, Co, h, w): a short last chunk is padded with its last window.
         `progress(i, n)` is called after each chunk with the number of its last window (not at all for a single window).
         Where the working size differs from the image's (`sample`, or an image smaller than the window grown to `glob`), the
@@ -552,6 +566,9 @@ class Net:
             if spec is None:
                 raise ValueError("Net.tiled: a uint8 image needs `image_input` declared (its k, b and order are used)")
         out_spec = self._image_out.get(0)
+        if isinstance(out_spec, TextSpec):
+            raise ValueError("Net.tiled: a text output is declared, and a blended scan is no sequence tensor; "
+                             "`float_output` removes the declaration")
         if isinstance(out_spec, KeypointSpec):
             raise ValueError("Net.tiled: a keypoint output is declared, and the peaks of a blended scan are not built; "
                              "`float_output` removes the declaration, `util.heatmap_peaks` takes the blended heat maps")
@@ -637,7 +654,7 @@ class Net:
         return int(index)
 
     def _check_outputs(self, out):
-        """ValueError unless every declared output is a 4-d float32 device tensor its encoder takes.  Returns the positions of
+        """ValueError unless every declared output is a float32 device tensor of the shape its encoder takes.  Returns the positions of
         the detection heads (None: none declared)."""
         seq = out if isinstance(out, tuple) else (out,)
         for i, spec in self._image_out.items():

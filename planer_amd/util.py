@@ -724,6 +724,133 @@ def follow_flows(x, level=0.0, min_flow=0.0, rounds=10, min_size=15, max_instanc
     return (masks.reshape(masks.shape[1:]) if x.ndim == 3 else masks), num, instances, centres
 
 
+# ---- text as net output -------------------------------------------------------------------------------------------
+TEXT_LAYOUTS = ("tnc", "ntc", "nchw")
+
+
+def _text_scratch_bytes(s, t):
+    """include/planer_hip.h PL_TEXT_SCRATCH_BYTES"""
+    return s * t * 8
+
+
+def _text_arguments(what, layout, blank, merge_repeated, confidence, max_len):
+    if layout not in TEXT_LAYOUTS:
+        raise ValueError("%s: layout is 'tnc', 'ntc' or 'nchw', got %r" % (what, layout))
+    if not _is_int(blank, 0):
+        raise ValueError("%s: blank is a class number >= 0, got %r" % (what, blank))
+    if not isinstance(merge_repeated, (bool, numpy.bool_)):
+        raise ValueError("%s: merge_repeated is True or False, got %r" % (what, merge_repeated))
+    if confidence not in _lib.TEXT_CONF:
+        raise ValueError("%s: confidence is 'softmax', 'value' or 'none', got %r" % (what, confidence))
+    if not _is_int(max_len, 1, _lib.TEXT_MAX_LEN):
+        raise ValueError("%s: max_len is 1 to %d, got %r" % (what, _lib.TEXT_MAX_LEN, max_len))
+    return layout, int(blank), bool(merge_repeated), confidence, int(max_len)
+
+
+class TextSpec:
+    """A float32 sequence tensor as text by greedy CTC decoding.  `layout` says where sequences, frames and classes are: "tnc"
+    (T, N, C) and "ntc" (N, T, C) hold N sequences, "nchw" (N, C, H, W) one per (n, h) with time along W.  A frame's label is
+    numpy's argmax over its classes (the first of equal maxima, the first NaN before any number); a frame starts a symbol iff its
+    label is not `blank` and, with `merge_repeated`, differs from the label of the frame in front.  The first `max_len` (1 to
+    1024) symbols of a sequence come back with the confidence of their first frame -- `confidence` "softmax": 1 / sum exp(x - max)
+    over the frame's classes, NaN where the maximum is not finite; "value": the bits of x at the argmax, for nets that end in
+    their own softmax; "none": +0.0 -- and their [start, end) frames.  Everything but the softmax confidence is exact.  Host values
+    only."""
+
+    places = 4                                            # text, length, conf, spans
+
+    def __init__(self, layout="tnc", blank=0, merge_repeated=True, confidence="softmax", max_len=64):
+        self.layout, self.blank, self.merge_repeated, self.confidence, self.max_len = _text_arguments(
+            "text output", layout, blank, merge_repeated, confidence, max_len)
+
+    def geometry(self, shape):
+        """(lead, S_outer, S_inner, T, C, (st_outer, st_inner, st_time, st_class)) for a float32 result of `shape`, lead the
+        shape of the sequences, or a ValueError that names what does not fit."""
+        shape = tuple(int(v) for v in shape)
+        want = 4 if self.layout == "nchw" else 3
+        if len(shape) != want:
+            raise ValueError("text output: layout %r takes a %d-d tensor, got shape %s" % (self.layout, want, shape))
+        if self.layout == "tnc":
+            (t, n, c), inner = shape, 1
+            strides = (c, 0, n * c, 1)
+        elif self.layout == "ntc":
+            (n, t, c), inner = shape, 1
+            strides = (t * c, 0, c, 1)
+        else:
+            n, c, inner, t = shape
+            strides = (c * inner * t, t, 1, inner * t)
+        if c < 1:
+            raise ValueError("text output: a frame has at least one class, got shape %s" % (shape,))
+        if self.blank >= c:
+            raise ValueError("text output: blank = %d is no class of the %d in shape %s" % (self.blank, c, shape))
+        if t > _lib.TEXT_MAX_FRAMES:
+            raise ValueError("text output: %d frames are above %d" % (t, _lib.TEXT_MAX_FRAMES))
+        if n * inner * t * c >= 1 << 31 or n * inner >= 1 << 31:
+            raise ValueError("text output: shape %s is 2^31 or more elements or sequences" % (shape,))
+        return ((n, inner) if self.layout == "nchw" else (n,)), n, inner, t, c, strides
+
+    def _shape(self, x):
+        if not isinstance(x, DeviceArray):
+            raise TypeError("text output: expected a float32 DeviceArray, got %s" % type(x).__name__)
+        if x.dtype != numpy.float32:
+            raise ValueError("text output: expected a float32 tensor, got %s of shape %s" % (x.dtype, tuple(x.shape)))
+        return self.geometry(x.shape)
+
+    def check(self, x):
+        self._shape(x)
+
+    def encode(self, x, ctx=None, lengths=None):
+        """(text, length, conf, spans) of float32 `x`, fresh arrays with `lead` = (N,) or, for "nchw", (N, H): text int32
+        lead + (max_len,), the labels of the first max_len symbols and -1 behind them; length int32 lead, all symbols of the
+        sequence, which may exceed max_len; conf float32 lead + (max_len,), +0.0 behind; spans int32 lead + (max_len, 2),
+        [start, end) in frames, 0 behind.  `lengths`: valid frames per sequence, a host int array or a device int32 array of
+        `lead`'s size (values above T count as T, below 0 as 0); None: every frame.  pl_ctc_greedy_f32 with scratch from `ctx`'s
+        pool; asynchronous on `ctx`'s stream (default: x's), nothing waits for the host."""
+        lead, n, inner, t, c, strides = self._shape(x)
+        ctx = ctx or x.ctx
+        s, m = n * inner, self.max_len
+        if lengths is not None:
+            if not isinstance(lengths, DeviceArray):
+                host = numpy.asarray(lengths)
+                if host.dtype.kind not in "iu" or host.size != s:
+                    raise ValueError("text output: lengths is an integer array with one entry per sequence (%d), got %s of shape %s"
+                                     % (s, host.dtype, host.shape))
+                lengths = hip.asarray(numpy.clip(host, 0, t).astype(numpy.int32).reshape(-1), ctx=ctx)
+            elif lengths.dtype != numpy.int32 or lengths.size != s:
+                raise ValueError("text output: lengths is an int32 array with one entry per sequence (%d), got %s of shape %s"
+                                 % (s, lengths.dtype, tuple(lengths.shape)))
+        text, length = hip.empty(lead + (m,), numpy.int32, ctx=ctx), hip.empty(lead, numpy.int32, ctx=ctx)
+        conf, spans = hip.empty(lead + (m,), numpy.float32, ctx=ctx), hip.empty(lead + (m, 2), numpy.int32, ctx=ctx)
+        if s and not t:                                     # no frame: no symbol, and -1 is four 0xFF bytes
+            _lib.call("pl_memset", ctx.handle, text.ptr, 0xFF, text.nbytes)
+        _launch_or_zero(ctx, s, t, (length, conf, spans), _text_scratch_bytes(s, t), lambda scratch: _lib.call(
+            "pl_ctc_greedy_f32", ctx.handle, x.ptr, n, inner, t, c, strides[0], strides[1], strides[2], strides[3],
+            None if lengths is None else lengths.ptr, self.blank, int(self.merge_repeated), _lib.TEXT_CONF[self.confidence], m,
+            scratch, text.ptr, length.ptr, conf.ptr, spans.ptr))
+        return text, length, conf, spans
+
+
+def ctc_decode(x, layout="tnc", blank=0, merge_repeated=True, confidence="softmax", max_len=64, lengths=None):
+    """(text, length, conf, spans) of the float32 DeviceArray `x` by greedy CTC decoding: see `TextSpec` and `TextSpec.encode`.
+    Asynchronous on x's stream (pl_ctc_greedy_f32)."""
+    return TextSpec(layout, blank, merge_repeated, confidence, max_len).encode(x, lengths=lengths)
+
+
+def text_strings(text, length, alphabet):
+    """The decoded strings of host arrays `text` (..., max_len) and `length` (...) as `TextSpec.encode` hands them back (after
+    `.get()`): a list of str per sequence, nested like the leading axes, alphabet[label] the character of a label (the blank's
+    entry is never used).  Only the first min(length, max_len) labels of a sequence are used."""
+    text, length = numpy.asarray(text), numpy.asarray(length)
+    if text.ndim < 1 or text.shape[:-1] != length.shape:
+        raise ValueError("text strings: text is (..., max_len) and length (...), got %s and %s" % (text.shape, length.shape))
+    if text.ndim == 1:
+        labels = text[:min(int(length), text.shape[0])]
+        if labels.size and (labels.min() < 0 or labels.max() >= len(alphabet)):
+            raise ValueError("text strings: a label outside the alphabet of %d: %s" % (len(alphabet), labels.tolist()))
+        return "".join(alphabet[int(v)] for v in labels)
+    return [text_strings(t, n, alphabet) for t, n in zip(text, length)]
+
+
 # ---- tiled inference around a plan: windows cut and blended in one launch each (DESIGN 4.25) ----------------------------------
 def _window_origins(windows):
     """(r0, c0, h, w) of a list of (row slice, column slice) windows of one size: int32 origin arrays and the extent."""
