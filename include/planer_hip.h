@@ -621,6 +621,34 @@ int pl_topk_f32(pl_ctx *ctx, const float *x, int outer, int n, int inner, int k,
                 long long *indices);
 int pl_lstm_cell_f32(pl_ctx *ctx, const float *gates_x, const float *gates_h, const float *bias, const float *c_prev,
                      float *h, float *c, int N, int H);
+/* ---- a whole LSTM layer's recurrence ----
+ * pl_lstm_seq_f32: the recurrent part of util.lstm (util.py:102-119) for L steps of ndir directions, after the input GEMMs.
+ *   gates_x0, gates_x1  float32 (L N, 4H) per direction slot: row t N + n is x_t W^T of batch row n, gates in ONNX order
+ *                     i | o | f | c.  gates_x1 is the second slot's and is null exactly when ndir == 1.
+ *   R (ndir, 4H, H), bias (ndir, 8H) = Wb | Rb, h0 and c0 (ndir, N, H): the layer's operands as ONNX holds them.
+ *   Y (L, ndir, N, H)   every step's h.  c (ndir, N, H): the cell state, updated in place; on return the final cell states.
+ *                     c may be c0 itself; no other two operands may overlap.
+ *   sign0             +1: slot 0 runs forward, -1: it runs in reverse.  Slot 1 always runs in reverse ("bidirectional" is
+ *                     ndir = 2, sign0 = +1).
+ *   time              launch s = 0 .. L-1 handles t = s in a forward slot and t = L-1-s in a reverse slot, both slots in the
+ *                     same launch.  h_prev is Y[t-1][slot] (forward) or Y[t+1][slot] (reverse), and h0[slot] at s = 0; c_prev
+ *                     is c[slot], and c0[slot] at s = 0.  The final h of a slot is Y[L-1][slot] (forward) or Y[0][slot].
+ *   a step            gates = ((gates_x[t] + h_prev R^T) + bias[:4H]) + bias[4H:]; C = sigmoid(f) c_prev + sigmoid(i) tanh(c);
+ *                     h = sigmoid(o) tanh(C); sigmoid(v) = 1 / (exp(-v) + 1); every product and sum rounded on its own: the
+ *                     arithmetic of pl_lstm_cell_f32.  h_prev R^T is the 32 x 32 tile product of pl_gemm_f32's small-batch
+ *                     form (trans_b, M <= 64, K >= 64, K % 8 == 0, aligned operands): K split over four waves in runs of
+ *                     ceil((H / 8) / 4) 8-wide steps, 32x32x2 MFMAs, the partial tiles summed in the order 0, 1, 2, 3.  Where
+ *                     pl_gemm_f32 takes that form the results are, bit for bit, those of pl_gemm_f32 + pl_lstm_cell_f32 per
+ *                     step; everywhere they depend on the operands alone, never on a measured algorithm pick.
+ * Asynchronous on ctx's stream: L launches of one kernel, grid (H / 8, ceil(N / 32), ndir), 256 threads; no host wait, no
+ * allocation, no atomics, no synchronisation but the workgroup barrier and the kernel boundary: capturable into a hipGraph.
+ * Rows at or past N are neither read nor written, and nothing but Y and c is written.
+ * PL_EINVAL: a null pointer (other than gates_x1 at ndir == 1), gates_x1 given at ndir == 1, ndir outside {1, 2}, sign0 outside
+ * {+1, -1}, L < 1, N < 0, H < 1, an operand that is not 16-byte aligned.  PL_EUNSUPPORTED: H % 8 != 0; N 4H >= 2^29 or
+ * 4H H >= 2^29 (byte offsets of the buffer descriptors); N > 2097120 (65535 row blocks).  N == 0: PL_OK, no launch.  Every refusal comes before any launch and
+ * leaves Y and c untouched. */
+int pl_lstm_seq_f32(pl_ctx *ctx, const float *gates_x0, const float *gates_x1, const float *R, const float *bias,
+                    const float *h0, const float *c0, float *Y, float *c, int L, int N, int H, int ndir, int sign0);
 /* ---- tiled large-image inference: the device side of util.tile (util.py:291-348) ----
  * pl_resize_hwc_f32: util.resize (util.py:253-269) on an H x W x C image; ra/rs (OH entries) and
  * ca/cs (OW entries) are the integer sample rows/columns and their fractions, device arrays

@@ -211,6 +211,7 @@ SIGNATURES = {
     "pl_nonzero_write": [_P, _P, _Z, _I, _P, _P, _I, _P, c_longlong],
     "pl_topk_f32": [_P, _P, _I, _I, _I, _I, _I, _P, _P],
     "pl_lstm_cell_f32": [_P, _P, _P, _P, _P, _P, _P, _I, _I],
+    "pl_lstm_seq_f32": [_P] + [_P] * 8 + [_I] * 5,
     "pl_resize_hwc_f32": [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P],
     "pl_image_u8_nchw_f32": [_P, _P, _P, _I, _I, _I, _I, _I, _I, POINTER(c_int), _I, _I, _P, _P, _P, _P, POINTER(c_float), POINTER(c_float)],
     "pl_image_f32_u8": [_P, _P, _P, _I, _I, _I, _I, _I, POINTER(c_int), _I, POINTER(c_float), POINTER(c_float), _I],

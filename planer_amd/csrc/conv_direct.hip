@@ -30,6 +30,7 @@
 //    columns) use split-K over gridDim.y with a second pass that sums the
 //    slabs and applies the fused tail.
 #include "conv_shared.h"
+#include "dense_tile.h"
 
 namespace {
 
@@ -1459,7 +1460,7 @@ int pair_launch(pl_ctx *ctx, const float *x, int N, int Cin, int H, int W, const
 // 16 ways and adds a reduce kernel -- 13.6 us for ResNet-18's 33 MFLOP classifier.  Here a workgroup owns 32 output
 // features x 32 batch rows; its four waves take a quarter of K each, reading both operands straight from global
 // memory as float4s of 4 consecutive k (nothing is shared between waves, so nothing goes through LDS but the final
-// sum of the four partial tiles).  32x32x2 MFMAs: lanes 0-31 carry k, lanes 32-63 carry k + 4.
+// sum of the four partial tiles).  32x32x2 MFMAs: lanes 0-31 carry k, lanes 32-63 carry k + 4.  (dense_tile.h)
 __global__ void __launch_bounds__(256) dense_small_kernel(const float *x, const float *w, const float *bias, float *y,
                                                           int M, int K, int N, unsigned x_bytes, unsigned w_bytes) {
     __shared__ float part[3][32 * 32];
@@ -1468,47 +1469,19 @@ __global__ void __launch_bounds__(256) dense_small_kernel(const float *x, const 
     const int n0 = blockIdx.x * 32, m0 = blockIdx.y * 32;
     const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(x), 0, x_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(w), 0, w_bytes, 0x00020000);
-    constexpr int OOB = (int)0x80000000;
-    const int kq = K / 4;                                  // K % 8 == 0 (host check): pairs of float4
-    const int steps = kq / 2, per_wave = (steps + 3) / 4;
-    const int s0 = wave * per_wave, s1 = min(steps, s0 + per_wave);
-    const int xo = m0 + l31 < M ? ((m0 + l31) * K + 4 * lhi) << 2 : OOB;
-    const int wo = n0 + l31 < N ? ((n0 + l31) * K + 4 * lhi) << 2 : OOB;
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    for (int s = s0; s < s1; s += 4) {                     // four load pairs in flight per lane
-        float4 a[4], b[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const bool ok = s + u < s1;
-            a[u] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(xr, ok ? xo : OOB, (s + u) * 32, 0));
-            b[u] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(wr, ok ? wo : OOB, (s + u) * 32, 0));
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u].x, b[u].x, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u].y, b[u].y, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u].z, b[u].z, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u].w, b[u].w, acc, 0, 0, 0);
-        }
-    }
+    const int xo = m0 + l31 < M ? ((m0 + l31) * K + 4 * lhi) << 2 : DENSE_TILE_OOB;
+    const int wo = n0 + l31 < N ? ((n0 + l31) * K + 4 * lhi) << 2 : DENSE_TILE_OOB;
+    // the K loop and the four-wave sum are dense_tile.h's, shared with the fused LSTM step (lstm_kernel.h)
+    f32x16 acc = dense_tile_kloop(xr, wr, xo, wo, K, wave);
+    dense_tile_sum(acc, part, wave, lane);
     // C layout: column = lane & 31 (output feature), rows (batch) 8*(r>>2) + 4*(lane>>5) + (r&3)
-    if (wave > 0) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) part[wave - 1][(8 * (r >> 2) + 4 * lhi + (r & 3)) * 32 + l31] = acc[r];
-    }
-    __syncthreads();
     if (wave == 0) {
         const int n = n0 + l31;
         const float bv = (bias && n < N) ? bias[n] : 0.f;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int row = 8 * (r >> 2) + 4 * lhi + (r & 3);
+            const int row = dense_tile_row(r, lane);
             float v = acc[r];
-            v = __fadd_rn(v, part[0][row * 32 + l31]);        // fixed order: waves 0, 1, 2, 3
-            v = __fadd_rn(v, part[1][row * 32 + l31]);
-            v = __fadd_rn(v, part[2][row * 32 + l31]);
             if (bias) v = __fadd_rn(v, bv);
             if (m0 + row < M && n < N) y[(size_t)(m0 + row) * N + n] = v;
         }

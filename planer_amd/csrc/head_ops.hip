@@ -5,6 +5,7 @@
 // (instance norm, the NonZero scan) are wave64 shuffle trees, TopK sorts a row in LDS.
 #include "common.h"
 #include "device_utils.h"
+#include "lstm_kernel.h"
 
 namespace {
 
@@ -292,26 +293,24 @@ __global__ void __launch_bounds__(TPB) topk_select_kernel(const float *x, float 
         }
 }
 
-// One step of util.lstm (util.py:109-118) after the two GEMMs: gates = ((x_t W^T + h R^T) + b[:4H]) + b[4H:],
-// split i, o, f, c (ONNX order); sigmoid(i), sigmoid(f), tanh(c); C = f*c_prev + i*c; h = sigmoid(o) * tanh(C).
-// Products and sums are rounded one at a time, as numpy does them.
-__device__ __forceinline__ float ref_sigmoid(float v) { return __fdiv_rn(1.f, __fadd_rn(expf(-v), 1.f)); }
+// One step of util.lstm (util.py:109-118) after the two GEMMs; the cell itself is lstm_kernel.h's lstm_cell, shared with the
+// fused step kernel of pl_lstm_seq_f32.
 __global__ void __launch_bounds__(TPB) lstm_cell_kernel(const float *gx, const float *gh, const float *b, const float *c_prev,
                                                         float *h, float *c, int N, int H) {
     // unsigned: total < 2^31 (host check) and the stride is at most 2^20, so i + stride stays below 2^32 (a signed i overflowed)
     const unsigned total = (unsigned)N * (unsigned)H, stride = gridDim.x * TPB;
     for (unsigned i = blockIdx.x * TPB + threadIdx.x; i < total; i += stride) {
         const int n = (int)(i / (unsigned)H), j = (int)(i - (unsigned)n * (unsigned)H);
-        float g[4];
+        float gxv[4], ghv[4], hv, C;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int col = q * H + j;
-            g[q] = __fadd_rn(__fadd_rn(__fadd_rn(gx[(size_t)n * 4 * H + col], gh[(size_t)n * 4 * H + col]), b[col]), b[4 * H + col]);
+            gxv[q] = gx[(size_t)n * 4 * H + col];
+            ghv[q] = gh[(size_t)n * 4 * H + col];
         }
-        const float ig = ref_sigmoid(g[0]), fg = ref_sigmoid(g[2]), cg = tanhf(g[3]);
-        const float C = __fadd_rn(__fmul_rn(fg, c_prev[i]), __fmul_rn(ig, cg));
+        lstm_cell(gxv, ghv, b, H, j, c_prev[i], hv, C);
         c[i] = C;
-        h[i] = __fmul_rn(ref_sigmoid(g[1]), tanhf(C));
+        h[i] = hv;
     }
 }
 
@@ -460,6 +459,34 @@ int pl_lstm_cell_f32(pl_ctx *ctx, const float *gates_x, const float *gates_h, co
     CtxGuard g(ctx);
     lstm_cell_kernel<<<stream_grid(ctx, (size_t)N * H), TPB, 0, ctx->stream>>>(gates_x, gates_h, bias, c_prev, h, c, N, H);
     PL_LAUNCH_CHECK();
+    return PL_OK;
+}
+
+int pl_lstm_seq_f32(pl_ctx *ctx, const float *gates_x0, const float *gates_x1, const float *R, const float *bias, const float *h0,
+                    const float *c0, float *Y, float *c, int L, int N, int H, int ndir, int sign0) {
+    PL_REQUIRE(ctx && gates_x0 && R && bias && h0 && c0 && Y && c, PL_EINVAL, "pl_lstm_seq_f32: null argument");
+    PL_REQUIRE(ndir == 1 || ndir == 2, PL_EINVAL, "pl_lstm_seq_f32: ndir = %d, one or two directions", ndir);
+    PL_REQUIRE((ndir == 2) == (gates_x1 != nullptr), PL_EINVAL, "pl_lstm_seq_f32: gates_x1 is given exactly when ndir == 2");
+    PL_REQUIRE(sign0 == 1 || sign0 == -1, PL_EINVAL, "pl_lstm_seq_f32: sign0 = %d, +1 (forward) or -1 (reverse)", sign0);
+    PL_REQUIRE(L >= 1, PL_EINVAL, "pl_lstm_seq_f32: L = %d, at least one step", L);
+    PL_REQUIRE(N >= 0 && H >= 1, PL_EINVAL, "pl_lstm_seq_f32: bad shape");
+    PL_REQUIRE(H % 8 == 0, PL_EUNSUPPORTED, "pl_lstm_seq_f32: H = %d is not a multiple of 8", H);
+    PL_REQUIRE(((reinterpret_cast<uintptr_t>(gates_x0) | reinterpret_cast<uintptr_t>(gates_x1) | reinterpret_cast<uintptr_t>(R) |
+                 reinterpret_cast<uintptr_t>(bias) | reinterpret_cast<uintptr_t>(h0) | reinterpret_cast<uintptr_t>(c0) |
+                 reinterpret_cast<uintptr_t>(Y) | reinterpret_cast<uintptr_t>(c)) & 15u) == 0,
+               PL_EINVAL, "pl_lstm_seq_f32: operands must be 16-byte aligned");
+    // the buffer-descriptor range of the dense tile (pl_gemm_f32's small-batch form): byte offsets stay below 2^31
+    PL_REQUIRE((size_t)N * 4 * H < (1ull << 29) && (size_t)4 * H * H < (1ull << 29), PL_EUNSUPPORTED,
+               "pl_lstm_seq_f32: N 4H or 4H H is 2^29 or more");
+    PL_REQUIRE((N + 31) / 32 <= 65535, PL_EUNSUPPORTED, "pl_lstm_seq_f32: N above 2097120");
+    if (!N) return PL_OK;
+    CtxGuard g(ctx);
+    LstmSeqArgs a = {{gates_x0, gates_x1}, R, bias, h0, c0, Y, c, L, N, H, 0, sign0};
+    const dim3 grid((unsigned)(H / 8), (unsigned)((N + 31) / 32), (unsigned)ndir);
+    for (a.step = 0; a.step < L; ++a.step) {
+        lstm_step_fused_kernel<<<grid, 256, 0, ctx->stream>>>(a);
+        PL_LAUNCH_CHECK();
+    }
     return PL_OK;
 }
 

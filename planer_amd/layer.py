@@ -14,6 +14,8 @@ kind raises KeyError in Net like the reference (net.py:15), and inputs a kernel
 does not cover raise NotImplementedError instead of silently running on the CPU.
 """
 
+import os
+
 import numpy
 
 from . import _lib
@@ -1162,11 +1164,39 @@ def TopK(x, k, axis=-1, largest=1, sorted=1):
     return vals, idx
 
 
+def lstm_fused_enabled():
+    """PLANER_HIP_LSTM_FUSED, read at call time: "0" gives the per-step program (a GEMM and a cell launch per step and
+    direction) everywhere; anything else, or nothing, the fused step launches of pl_lstm_seq_f32."""
+    return os.environ.get("PLANER_HIP_LSTM_FUSED", "1") != "0"
+
+
+def lstm_fused_eligible(L, N, H, ndir, aligned=True):
+    """What pl_lstm_seq_f32 accepts (head_ops.hip, the rule in include/planer_hip.h): at least one step, one or two directions,
+    a hidden size that is a positive multiple of 8, 16-byte aligned operands, N 4H and 4H H below 2^29, at most 65535 blocks
+    of 32 batch rows.  Where it says no, layer.LSTM runs the per-step program."""
+    return bool(L >= 1 and ndir in (1, 2) and N >= 0 and H >= 8 and H % 8 == 0 and aligned
+                and N * 4 * H < 1 << 29 and 4 * H * H < 1 << 29 and (N + 31) // 32 <= 65535)
+
+
+def _lstm_takes_fused(L, N, H, gx, operands, Y):
+    """Whether this call of layer.LSTM goes to pl_lstm_seq_f32: the switch, then lstm_fused_eligible on the shapes and on the
+    pointers the call would pass.  gx holds None per direction when L == 0."""
+    if not lstm_fused_enabled() or not L or not N:
+        return False                                     # (nothing to align at L == 0: there is no gates_x)
+    nd = len(gx)
+    if any(t.shape[0] < nd for t in operands):
+        return False
+    aligned = all(t.ptr % 16 == 0 for t in tuple(gx) + tuple(operands) + (Y,))
+    return lstm_fused_eligible(L, N, H, nd, aligned=aligned)
+
+
 def LSTM(X, W, R, B=0, sequence_lens=0, initial_h=0, initial_c=0, hidden_size=None, direction="forward"):
     """layer.LSTM (layer.py:36-42) over util.lstm (util.py:102-119): X (L, N, D), W (dirs, 4H, D), R (dirs, 4H, H),
     B (dirs, 8H), initial_h / initial_c (dirs, N, H); gates in ONNX order i, o, f, c; sequence_lens is ignored
-    there too.  x_t W^T for every step is ONE MFMA GEMM per direction; a step is then h R^T (GEMM) + the cell
-    kernel.  Returns (Y (L, dirs, N, H), H, C) with the reference's shapes: H (N, H) and C (1, N, H) of the
+    there too.  x_t W^T for every step is ONE MFMA GEMM per direction; the recurrence is then pl_lstm_seq_f32: one
+    launch per step that does h R^T, the gate sum and the cell for every direction.  Where
+    lstm_fused_eligible says no, or with PLANER_HIP_LSTM_FUSED=0, a step is h R^T (GEMM) + the cell kernel per
+    direction.  Returns (Y (L, dirs, N, H), H, C) with the reference's shapes: H (N, H) and C (1, N, H) of the
     LAST direction only."""
     dirs = {"forward": [1], "reverse": [-1], "bidirectional": [1, -1]}[direction]
     _f32(X, W, R)
@@ -1179,9 +1209,28 @@ def LSTM(X, W, R, B=0, sequence_lens=0, initial_h=0, initial_c=0, hidden_size=No
     from .hip import zeros
     Y = zeros((L, len(dirs), N, H), ctx=X.ctx)
     X2 = X.reshape(L * N, D)
+    nd = len(dirs)
+    gx = [Dense(X2, W[i], None) if L else None for i in range(nd)]   # (L*N, 4H) per direction: every step's x_t W^T
+    if not _lstm_takes_fused(L, N, H, gx, (R, B, initial_h, initial_c), Y):
+        return _lstm_steps(X, gx, R, B, initial_h, initial_c, Y, dirs)
+    # raw pointers on X's context: an operand that is an init of a Net lives in the net's own context, and every launch of the
+    # recurrence still goes to X's stream (a throughput plan captures on a replica's stream, and a launch elsewhere is not part
+    # of its graph).  Reading the other context's memory from X's stream is ordered the way the reads of W are: an init was
+    # uploaded and synchronised when the net was loaded, long before any pass
+    Cs = empty((nd, N, H), ctx=X.ctx)
+    _lib.call("pl_lstm_seq_f32", X.ctx.handle, gx[0].ptr, gx[1].ptr if nd == 2 else None, R.ptr, B.ptr, initial_h.ptr,
+              initial_c.ptr, Y.ptr, Cs.ptr, L, N, H, nd, dirs[0])
+    ht = Y[L - 1 if dirs[-1] > 0 else 0][nd - 1]
+    # the last direction's cell state as a block of its own, like the per-step program's (a net's result must be one)
+    ct = Cs.reshape(1, N, H) if nd == 1 else Cs[nd - 1].reshape(1, N, H).copy()
+    return Y, ht.copy(), ct
+
+
+def _lstm_steps(X, gx, R, B, initial_h, initial_c, Y, dirs):
+    """The per-step program: per direction and step, h R^T through Dense and the cell kernel."""
+    L, _, N, H = Y.shape
     ht = ct = None
     for i, d in enumerate(dirs):
-        gx = Dense(X2, W[i], None) if L else None                   # (L*N, 4H): every step's x_t W^T
         ht, ct = initial_h[i], initial_c[i]
         if ht.ctx is not X.ctx:
             # an initial state that is an init of a Net lives in the net's own context, and Dense launches where its first
@@ -1193,7 +1242,7 @@ def LSTM(X, W, R, B=0, sequence_lens=0, initial_h=0, initial_c=0, hidden_size=No
         for t in list(range(L))[::d]:
             gh = Dense(ht, R[i], None)
             h_new, c_new = Y[t][i], empty((1, N, H), ctx=X.ctx)
-            _lib.call("pl_lstm_cell_f32", X.ctx.handle, gx.rows(t * N, (t + 1) * N).ptr, gh.ptr, B[i].ptr, ct.ptr, h_new.ptr,
+            _lib.call("pl_lstm_cell_f32", X.ctx.handle, gx[i].rows(t * N, (t + 1) * N).ptr, gh.ptr, B[i].ptr, ct.ptr, h_new.ptr,
                       c_new.ptr, N, H)
             ht, ct = h_new, c_new
     return Y, ht.copy(), ct

@@ -9,9 +9,12 @@ tuning cache.  Then the chain alone (one more process): HIP events around --laun
 and (80, 32, 6625) "tnc" and on (32, 6625, 1, 80) "nchw", beside a one-frame call (the launch floor).  With --trace that process
 runs once more under rocprofv3 --kernel-trace and the median device time of each launch is reported per input, the frame pass also
 as bytes read per second and as a share of 8 TB/s; and one CRNN forward (37 classes) runs under a kernel trace of its own, from
-which the share of the LSTM steps -- every lstm_cell_kernel and the h R^T GEMM in front of it -- in the kernels of one pass is read.
+which the share of the LSTM steps -- every lstm_step_fused_kernel, or every lstm_cell_kernel and the h R^T GEMM in
+front of it -- in the kernels of one pass is read.  --lstm per-step runs the CRNN arms and the traced forward with
+PLANER_HIP_LSTM_FUSED=0 (the per-step program), --lstm both runs every arm in both programs, alternating inside each round; the
+per-step lines and summary keys carry "@per-step".
 One JSON line per step as it ends, then one summary line.  The tool stops at the first step that fails.
-    python tools/text_bench.py [--rounds 2] [--passes 40] [--arms ...] [--no-kernels] [--trace [all|chain|lstm]]
+    python tools/text_bench.py [--rounds 2] [--passes 40] [--arms ...] [--no-kernels] [--trace [all|chain|lstm]] [--lstm fused|per-step|both]
 The parent process never opens the GPU."""
 import argparse
 import collections
@@ -31,6 +34,8 @@ CLASSES = (37, 6625)
 ARMS = ["crnn-%d-%s" % (c, how) for c in CLASSES for how in ("text", "float", "float-host")]
 BATCH, SIZE, FRAMES, MAX_LEN = 32, (32, 320), 80, 64
 HBM_BYTES_S = 8e12
+PER_STEP = "@per-step"          # suffix of an arm run with PLANER_HIP_LSTM_FUSED=0
+FUSED_ENV = {"fused": "1", "per-step": "0"}
 
 
 def host_decode(logits):
@@ -65,7 +70,7 @@ def arm_child(args):
     planer_amd, net, crnn = crnn_net(int(classes))
     if how == "text":
         net.text_output("tnc", max_len=MAX_LEN)
-    line = {"arm": args.arm, "round": args.round}
+    line = {"arm": args.arm + ("" if planer_amd.layer.lstm_fused_enabled() else PER_STEP), "round": args.round}
     batches = [crnn.make_input(BATCH, seed=s, size=SIZE, channels=3) for s in (1, 2)]
     window, pend = 6, collections.deque()
 
@@ -173,7 +178,8 @@ def forward_child(args):
     ctx.synchronize()
     if ctx.tune_cache:
         ctx.save_tune_cache()
-    print(json.dumps({"forward": "crnn-37", "captured": bool(net.use_graph), "tune_source": net.tune_source()}), flush=True)
+    print(json.dumps({"forward": "crnn-37", "captured": bool(net.use_graph), "tune_source": net.tune_source(),
+                      "lstm_fused": planer_amd.layer.lstm_fused_enabled()}), flush=True)
 
 
 def read_trace(directory):
@@ -216,12 +222,36 @@ def chain_digest(directory, launches):
     return out
 
 
+def lstm_fused_digest(rows):
+    """The fused program: a step of a whole LSTM op (both directions) is one lstm_step_fused_kernel, 2 x 80 of them a pass."""
+    steps = [i for i, r in enumerate(rows) if "lstm_step_fused_kernel" in r[0]]
+    per_pass = 2 * FRAMES
+    if len(steps) < 2 * per_pass:
+        return {"error": "%d fused step kernels in the trace, fewer than two passes" % len(steps)}
+    k = steps[-1] - steps[-1 - per_pass]
+    last = rows[len(rows) - k:]
+    mine = [i for i, r in enumerate(last) if "lstm_step_fused_kernel" in r[0]]
+    if len(mine) != per_pass:
+        return {"error": "%d fused step kernels in the last %d kernels, expected %d" % (len(mine), k, per_pass)}
+    busy = sum(t1 - t0 for _, t0, t1 in last)
+    inside = sum(last[i][2] - last[i][1] for i in mine)
+    spans = [last[mine[(op + 1) * FRAMES - 1]][2] - last[mine[op * FRAMES]][1] for op in range(2)]
+    wall = last[-1][2] - last[0][1]
+    return {"kernels_per_pass": k, "fused_step_kernels_per_pass": len(mine), "lstm_step_launches": len(mine),
+            "pass_wall_us": round(wall / 1e3, 1), "pass_busy_us": round(busy / 1e3, 1),
+            "lstm_steps_busy_us": round(inside / 1e3, 1), "lstm_steps_share_of_busy": round(inside / busy, 3),
+            "lstm_step_us": round(inside / len(mine) / 1e3, 2),
+            "lstm_ops_wall_us": round(sum(spans) / 1e3, 1), "lstm_ops_share_of_wall": round(sum(spans) / wall, 3)}
+
+
 def lstm_digest(directory):
     """The last pass of the forward child: its kernels are the last K of the trace, K the distance between two cell kernels
     that are one pass (2 LSTMs x 2 directions x 80 steps) apart.  A step is a cell kernel and the h R^T GEMM in front of it:
     every kernel since the cell of the step before (however many launches the GEMM takes), and for a direction's first step the
     one kernel in front.  `step_gemm_kernels` names what was counted as such a GEMM."""
     rows = read_trace(directory)
+    if any("lstm_step_fused_kernel" in r[0] for r in rows):
+        return lstm_fused_digest(rows)
     cells = [i for i, r in enumerate(rows) if "lstm_cell_kernel" in r[0]]
     per_pass = 2 * 2 * FRAMES
     if len(cells) < 2 * per_pass:
@@ -262,6 +292,8 @@ def main():
     ap.add_argument("--no-kernels", action="store_true")
     ap.add_argument("--trace", nargs="?", const="all", default=None, choices=["all", "chain", "lstm"],
                     help="under rocprofv3 --kernel-trace: the kernels step once more (chain), one CRNN forward (lstm), or both")
+    ap.add_argument("--lstm", default="fused", choices=["fused", "per-step", "both"],
+                    help="the LSTM program of the CRNN arms and of the traced forward (PLANER_HIP_LSTM_FUSED); both: alternating")
     ap.add_argument("--cache", default=None, help="tuning cache file every process loads and saves")
     ap.add_argument("--timeout", type=int, default=300, help="seconds one child process may take")
     ap.add_argument("--child", choices=["arm", "kernels", "forward"])
@@ -276,9 +308,12 @@ def main():
     env = dict(os.environ, PLANER_HIP_TUNE_CACHE=os.path.abspath(args.cache))
     common = ["--passes", str(args.passes), "--calls", str(args.calls), "--launches", str(args.launches)]
 
-    def step(extra, wrap=()):
+    modes = ["fused", "per-step"] if args.lstm == "both" else [args.lstm]
+
+    def step(extra, wrap=(), mode=None):
+        """mode: the LSTM program of a child that runs the CRNN (arm, forward); the chain children run no LSTM and get none"""
         cmd = ["timeout", "-k", "10", str(args.timeout)] + list(wrap) + [sys.executable, os.path.abspath(__file__)] + extra + common
-        r = subprocess.run(cmd, capture_output=True, text=True, env=env)
+        r = subprocess.run(cmd, capture_output=True, text=True, env=dict(env, PLANER_HIP_LSTM_FUSED=FUSED_ENV[mode]) if mode else env)
         if r.returncode != 0:                          # the first failing step ends the run: nothing more is started
             sys.exit("step %s failed (exit %d):\n%s\n%s" % (" ".join(extra), r.returncode, r.stdout[-2000:], r.stderr[-3000:]))
         lines = [json.loads(ln) for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -289,7 +324,8 @@ def main():
     runs = []
     for rnd in range(args.rounds):
         for arm in arms:
-            runs += step(["--child", "arm", "--arm", arm, "--round", str(rnd)])
+            for mode in modes:
+                runs += step(["--child", "arm", "--arm", arm, "--round", str(rnd)], mode=mode)
     kernels = [] if args.no_kernels else step(["--child", "kernels"])
     out = {"dtype": "fp32", "rounds": args.rounds, "passes": args.passes, "batch": BATCH, "size": list(SIZE), "arms": {}, "kernels": kernels}
     if args.trace in ("all", "chain"):
@@ -298,13 +334,20 @@ def main():
         out["trace"] = chain_digest(d, args.launches)
         print(json.dumps({"trace": out["trace"]}), flush=True)
     if args.trace in ("all", "lstm"):
-        d = os.path.join(tmp.name, "forward")
-        step(["--child", "forward"])                   # untraced first: the conv picks are measured here, not under the tracer
-        step(["--child", "forward"], wrap=["rocprofv3", "--kernel-trace", "-d", d, "-o", "crnn", "--output-format", "csv", "--"])
-        out["lstm"] = lstm_digest(d)
-        print(json.dumps({"lstm": out["lstm"]}), flush=True)
+        digests = {}
+        for rnd in range(args.rounds if len(modes) > 1 else 1):
+            for mode in modes:
+                d = os.path.join(tmp.name, "forward-%s-%d" % (mode, rnd))
+                step(["--child", "forward"], mode=mode)    # untraced first: the conv picks are measured here, not under the tracer
+                step(["--child", "forward"], wrap=["rocprofv3", "--kernel-trace", "-d", d, "-o", "crnn", "--output-format", "csv", "--"],
+                     mode=mode)
+                digest = lstm_digest(d)
+                digests.setdefault(mode, []).append(digest)
+                print(json.dumps({"lstm": digest, "program": mode, "round": rnd}), flush=True)
+        # one program: the digest itself, as before; --lstm both: {program: [a digest per round]}
+        out["lstm"] = digests if len(modes) > 1 else digests[modes[0]][0]
     med = lambda v: sorted(v)[len(v) // 2] if v else None        # noqa: E731
-    for arm in arms:
+    for arm in [a + ("" if m == "fused" else PER_STEP) for a in arms for m in modes]:
         mine = [r for r in runs if r["arm"] == arm]
         keys = [k for k, v in mine[0].items() if isinstance(v, (int, float)) and not isinstance(v, bool) and k != "round"]
         out["arms"][arm] = {"median_" + k: med([r[k] for r in mine]) for k in keys}
