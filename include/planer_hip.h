@@ -619,6 +619,27 @@ int pl_nonzero_write(pl_ctx *ctx, const void *x, size_t n, int elem_type, const 
                      const long long *shape, int ndim, long long *out, long long total);
 int pl_topk_f32(pl_ctx *ctx, const float *x, int outer, int n, int inner, int k, int largest, float *values,
                 long long *indices);
+/* ---- top-k by exact radix selection ----
+ * pl_topk_select_f32: what pl_topk_f32(..., largest = 1, ...) computes, with the same bits in both outputs, without sorting the
+ *   row.  x is viewed (outer, n, inner); for each (outer, inner) row indices[j] is element n - 1 - j of the stable ascending
+ *   sort (NaN last, +0 == -0, equal values by ascending index) -- read from its end: descending value, NaN first, equal values
+ *   by descending index -- and values[j] is x there with its original bits.  values / indices are (outer, k, inner).
+ *   A row is cut into chunks of PL_TOPK_SELECT_CHUNK elements, one workgroup each: three histogram passes over 11, 11 and 10
+ *   bits of an order-preserving 32-bit key find the k-th greatest key exactly, a gather pass collects the keys above it, and one
+ *   workgroup per row sorts those (fewer than k) and fills up with the elements equal to the threshold by descending index.  Six
+ *   launches whatever the data, nothing waits for the host: it runs under graph capture.
+ *   scratch: PL_TOPK_SELECT_SCRATCH_BYTES(outer inner, n, k) bytes of the caller's, 8-byte aligned, contents irrelevant: every
+ *   word the kernels read is written by a kernel of the same call.
+ *   PL_EINVAL (before any launch, outputs untouched): a null pointer, n < 1, k < 1, k > n, a negative dimension, scratch not
+ *   8-byte aligned.  PL_EUNSUPPORTED: k > PL_TOPK_SELECT_MAX_K, 2^31 or more rows or elements.  No rows: PL_OK, no launch.
+ *   largest = 0 is pl_topk_f32's. */
+#define PL_TOPK_SELECT_CHUNK 1024
+#define PL_TOPK_SELECT_MAX_K 4096
+#define PL_TOPK_SELECT_HIST_WORDS 5120
+#define PL_TOPK_SELECT_SCRATCH_BYTES(rows, n, k) \
+    ((size_t)(rows) * ((size_t)(k) * 8 + PL_TOPK_SELECT_HIST_WORDS * 4 + 4 + (((size_t)(n) + PL_TOPK_SELECT_CHUNK - 1) / PL_TOPK_SELECT_CHUNK) * 4))
+int pl_topk_select_f32(pl_ctx *ctx, const float *x, int outer, int n, int inner, int k, void *scratch, float *values,
+                       long long *indices);
 int pl_lstm_cell_f32(pl_ctx *ctx, const float *gates_x, const float *gates_h, const float *bias, const float *c_prev,
                      float *h, float *c, int N, int H);
 /* ---- a whole LSTM layer's recurrence ----

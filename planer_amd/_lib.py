@@ -41,6 +41,9 @@ TEXT_CHUNK = 256                    # include/planer_hip.h PL_TEXT_CHUNK
 TEXT_ROW_WAVE_MAX = 1024            # include/planer_hip.h PL_TEXT_ROW_WAVE_MAX
 TEXT_TIME_LANES = 32                # include/planer_hip.h PL_TEXT_TIME_LANES
 TEXT_TIME_GROUPS = 32               # include/planer_hip.h PL_TEXT_TIME_GROUPS
+TOPK_SELECT_CHUNK = 1024            # include/planer_hip.h PL_TOPK_SELECT_CHUNK
+TOPK_SELECT_MAX_K = 4096            # include/planer_hip.h PL_TOPK_SELECT_MAX_K
+TOPK_SELECT_HIST_WORDS = 5120       # include/planer_hip.h PL_TOPK_SELECT_HIST_WORDS
 TEXT_CONF = {"none": 0, "softmax": 1, "value": 2}   # include/planer_hip.h PL_TEXT_CONF_*
 ACT_NONE, ACT_RELU, ACT_LEAKY = 0, 1, 2
 ACT_RES_AFTER = 16
@@ -210,6 +213,7 @@ SIGNATURES = {
     "pl_nonzero_count": [_P, _P, _Z, _I, _P, _P],
     "pl_nonzero_write": [_P, _P, _Z, _I, _P, _P, _I, _P, c_longlong],
     "pl_topk_f32": [_P, _P, _I, _I, _I, _I, _I, _P, _P],
+    "pl_topk_select_f32": [_P, _P, _I, _I, _I, _I, _P, _P, _P],
     "pl_lstm_cell_f32": [_P, _P, _P, _P, _P, _P, _P, _I, _I],
     "pl_lstm_seq_f32": [_P] + [_P] * 8 + [_I] * 5,
     "pl_resize_hwc_f32": [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P],

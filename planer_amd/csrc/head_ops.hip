@@ -2,10 +2,12 @@
 // trunk (reference layer.py:36-42, 155-157, 202-239, 253-258): comparisons, Where, Cast, Gather, Erf (the
 // reference's 1025-entry lookup table), InstanceNormalization, ScatterND, NonZero, TopK and the LSTM cell.
 // All HBM-bound: one pass over the operands, grid-stride loops capped near 8 blocks per CU; the reductions
-// (instance norm, the NonZero scan) are wave64 shuffle trees, TopK sorts a row in LDS.
+// (instance norm, the NonZero scan) are wave64 shuffle trees, TopK sorts a row in LDS or, as pl_topk_select_f32, selects its k
+// greatest by radix histograms over one workgroup per chunk of the row (topk_select_kernel.h).
 #include "common.h"
 #include "device_utils.h"
 #include "lstm_kernel.h"
+#include "topk_select_kernel.h"
 
 namespace {
 
@@ -447,6 +449,45 @@ int pl_topk_f32(pl_ctx *ctx, const float *x, int outer, int n, int inner, int k,
     } else {
         topk_select_kernel<<<(unsigned)rows, TPB, 0, ctx->stream>>>(x, values, indices, n, inner, k, largest);
     }
+    PL_LAUNCH_CHECK();
+    return PL_OK;
+}
+
+int pl_topk_select_f32(pl_ctx *ctx, const float *x, int outer, int n, int inner, int k, void *scratch, float *values,
+                       long long *indices) {
+    namespace ts = topk_select;
+    PL_REQUIRE(ctx && x && scratch && values && indices, PL_EINVAL, "pl_topk_select_f32: null argument");
+    PL_REQUIRE(outer >= 0 && inner >= 0 && n >= 1 && k >= 1, PL_EINVAL, "pl_topk_select_f32: bad shape: (%d, %d, %d), k = %d", outer, n,
+               inner, k);
+    PL_REQUIRE(k <= n, PL_EINVAL, "pl_topk_select_f32: k = %d exceeds the axis length %d", k, n);
+    PL_REQUIRE((reinterpret_cast<uintptr_t>(scratch) & 7u) == 0, PL_EINVAL, "pl_topk_select_f32: scratch must be 8-byte aligned");
+    PL_REQUIRE(k <= PL_TOPK_SELECT_MAX_K, PL_EUNSUPPORTED, "pl_topk_select_f32: k = %d is above %d", k, PL_TOPK_SELECT_MAX_K);
+    const size_t rows = (size_t)outer * inner;
+    PL_REQUIRE(rows < (1ull << 31) && rows * (size_t)n < (1ull << 31), PL_EUNSUPPORTED, "pl_topk_select_f32: 2^31 or more rows or elements");
+    if (!rows) return PL_OK;
+    CtxGuard g(ctx);
+    const size_t chunks = ((size_t)n + ts::CHUNK - 1) / ts::CHUNK;         // rows * chunks <= rows * n < 2^31: a grid's x extent
+    ts::Args a;
+    a.x = x;
+    a.n = (unsigned)n, a.inner = (unsigned)inner, a.k = (unsigned)k, a.chunks = (unsigned)chunks;
+    a.cand = reinterpret_cast<unsigned long long *>(scratch);
+    a.hist = reinterpret_cast<unsigned *>(a.cand + rows * (size_t)k);
+    a.counter = a.hist + rows * ts::HIST_WORDS;
+    a.ties = a.counter + rows;
+    a.values = values, a.indices = indices;
+    const size_t clear = rows * (ts::HIST_WORDS + 1);                      // histograms and counters, adjacent
+    const unsigned grid = (unsigned)(rows * chunks);
+    ts::clear_kernel<<<stream_grid(ctx, clear), TPB, 0, ctx->stream>>>(a.hist, clear);
+    PL_LAUNCH_CHECK();
+    ts::hist_kernel<1><<<grid, TPB, 0, ctx->stream>>>(a);
+    PL_LAUNCH_CHECK();
+    ts::hist_kernel<2><<<grid, TPB, 0, ctx->stream>>>(a);
+    PL_LAUNCH_CHECK();
+    ts::hist_kernel<3><<<grid, TPB, 0, ctx->stream>>>(a);
+    PL_LAUNCH_CHECK();
+    ts::gather_kernel<<<grid, TPB, 0, ctx->stream>>>(a);
+    PL_LAUNCH_CHECK();
+    ts::finish_kernel<<<(unsigned)rows, TPB, 0, ctx->stream>>>(a);
     PL_LAUNCH_CHECK();
     return PL_OK;
 }

@@ -1142,9 +1142,12 @@ def NonZero(x):
 def TopK(x, k, axis=-1, largest=1, sorted=1):
     """layer.TopK (layer.py:234-239): (values, int64 indices) of take(argsort(x, axis), arange(k) * -largest -
     (largest > 0), axis).  largest = 1: the k greatest, descending.  largest = 0: the reference's index list
-    is k zeros, i.e. k copies of the smallest element -- reproduced.  One workgroup sorts a row in LDS (up to
-    16384 elements; longer rows take k selection rounds).  Equal values: numpy's sort leaves their order
-    unspecified, here the lower index sorts first."""
+    is k zeros, i.e. k copies of the smallest element -- reproduced.  Where topk_select_eligible says so (by
+    default rows of 4096 elements and more with k <= 4096, largest = 1) the k greatest are SELECTED by
+    pl_topk_select_f32: radix histograms over one workgroup per 1024 elements, six launches whatever the data
+    (DESIGN.md 4.31).  Otherwise pl_topk_f32: one workgroup sorts a row in LDS (up to 16384 elements; longer
+    rows take k selection rounds in that one workgroup).  The two give the same bits.  Equal values: numpy's
+    sort leaves their order unspecified, here the lower index sorts first."""
     _f32(x)
     kk = int(numpy.asarray(_host_values(k)).reshape(-1)[0])
     if largest not in (0, 1):
@@ -1160,8 +1163,50 @@ def TopK(x, k, axis=-1, largest=1, sorted=1):
     shape = x.shape[:axis] + (kk,) + x.shape[axis + 1:]
     vals, idx = empty(shape, ctx=x.ctx), empty(shape, numpy.int64, ctx=x.ctx)
     if vals.size:
-        _lib.call("pl_topk_f32", x.ctx.handle, x.ptr, outer, n, inner, kk, int(largest), vals.ptr, idx.ptr)
+        _topk_launch(x.ctx, x.ptr, outer, n, inner, kk, int(largest), vals, idx)
     return vals, idx
+
+
+TOPK_SORT_MAX = 16384           # head_ops.hip TOPK_LDS_MAX: pl_topk_f32 sorts rows up to this length in LDS
+TOPK_SELECT_MIN_N = 4096        # the shortest row that goes to pl_topk_select_f32 by default
+
+
+def topk_select_enabled():
+    """PLANER_HIP_TOPK_SELECT, read at call time: "0" gives pl_topk_f32 everywhere; anything else, or nothing, lets
+    topk_select_eligible route to pl_topk_select_f32."""
+    return os.environ.get("PLANER_HIP_TOPK_SELECT", "1") != "0"
+
+
+def topk_select_eligible(rows, n, inner, k, largest):
+    """Whether a top-k of `rows` = outer * inner rows of length n goes to pl_topk_select_f32.  The entry serves largest = 1,
+    1 <= k <= min(n, 4096) and fewer than 2^31 rows and elements (include/planer_hip.h).  PLANER_HIP_TOPK_SELECT=force takes it
+    wherever it serves; =0 never.  By default it is taken for rows of 4096 elements and more -- where it was measured 1.5 to 17
+    times faster than the LDS sort at every k (profiles/topk_select.md; below that both cost about 30 us and the sort is one
+    launch) -- except k = 1 above 16384, where pl_topk_f32's selection is one pass over the row too."""
+    if not topk_select_enabled():
+        return False
+    served = bool(largest == 1 and rows >= 1 and inner >= 1 and 1 <= k <= min(n, _lib.TOPK_SELECT_MAX_K)
+                  and rows < 1 << 31 and rows * n < 1 << 31)
+    if os.environ.get("PLANER_HIP_TOPK_SELECT") == "force":
+        return served
+    return served and n >= TOPK_SELECT_MIN_N and (k >= 2 or n <= TOPK_SORT_MAX)
+
+
+def _topk_select_scratch_bytes(rows, n, k):
+    """include/planer_hip.h PL_TOPK_SELECT_SCRATCH_BYTES"""
+    return rows * (k * 8 + _lib.TOPK_SELECT_HIST_WORDS * 4 + 4 + (n + _lib.TOPK_SELECT_CHUNK - 1) // _lib.TOPK_SELECT_CHUNK * 4)
+
+
+def _topk_launch(ctx, x_ptr, outer, n, inner, k, largest, vals, idx):
+    """The top-k of x (outer, n, inner) at `x_ptr` into vals / idx (outer, k, inner) on `ctx`'s stream: pl_topk_select_f32 with
+    scratch from `ctx`'s pool where topk_select_eligible says so, pl_topk_f32 otherwise.  layer.TopK, util.nms and the
+    detection chain all come through here."""
+    if topk_select_eligible(outer * inner, n, inner, k, largest):
+        nbytes = _topk_select_scratch_bytes(outer * inner, n, k)
+        scratch = empty(((nbytes + 7) // 8,), numpy.int64, ctx=ctx)     # (held until the launches are enqueued)
+        _lib.call("pl_topk_select_f32", ctx.handle, x_ptr, outer, n, inner, k, scratch.ptr, vals.ptr, idx.ptr)
+    else:
+        _lib.call("pl_topk_f32", ctx.handle, x_ptr, outer, n, inner, k, largest, vals.ptr, idx.ptr)
 
 
 def lstm_fused_enabled():

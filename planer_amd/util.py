@@ -22,7 +22,8 @@ import numpy
 from . import _lib
 from . import hip
 from .hip import DeviceArray
-from .layer import _strided_map, _contig_strides, _f32
+from .layer import _strided_map, _contig_strides, _f32, _topk_launch
+from .layer import _topk_select_scratch_bytes              # noqa: F401  (include/planer_hip.h PL_TOPK_SELECT_SCRATCH_BYTES)
 
 
 def _is_int(v, lo, hi=None):
@@ -326,10 +327,11 @@ def _f32v(v):
 
 
 def _nms_sorted(boxes, classes, scores, n, r, k, floor, iou, class_aware, max_det, ctx):
-    """top-k of scores (N, R) and pl_nms_f32 on the k first of each image: (det (N, max_det, 6), num (N,)), fresh arrays."""
+    """top-k of scores (N, R) and pl_nms_f32 on the k first of each image: (det (N, max_det, 6), num (N,)), fresh arrays.  The
+    top-k is pl_topk_f32 or, where layer.topk_select_eligible says so, pl_topk_select_f32: the same bits."""
     vals, idx = hip.empty((n, k), ctx=ctx), hip.empty((n, k), numpy.int64, ctx=ctx)
     if n and k:
-        _lib.call("pl_topk_f32", ctx.handle, scores.ptr, n, r, 1, k, 1, vals.ptr, idx.ptr)
+        _topk_launch(ctx, scores.ptr, n, r, 1, k, 1, vals, idx)
     det, num = hip.empty((n, max_det, 6), ctx=ctx), hip.empty((n,), numpy.int32, ctx=ctx)
     _lib.call("pl_nms_f32", ctx.handle, boxes.ptr, classes.ptr if classes is not None else None, vals.ptr, idx.ptr, n, r, k,
               floor, iou, int(bool(class_aware)), max_det, det.ptr, num.ptr)
@@ -406,8 +408,9 @@ class DetectionSpec:
     def encode(self, xs, ctx=None):
         """(det, num) of the head tensors `xs`: det float32 (N, max_det, 6), rows [x1, y1, x2, y2, score, class] by descending
         score and +0.0 behind them, num int32 (N,); fresh arrays (max_det is at most the number of anchors).  One
-        pl_yolo_decode_f32 per head, pl_topk_f32, pl_nms_f32, asynchronous on `ctx`'s stream (default: the first head's);
-        scores, classes, boxes and the top-k results are scratch from that context's pool."""
+        pl_yolo_decode_f32 per head, pl_topk_f32 (rows of 4096 anchors and more: pl_topk_select_f32), pl_nms_f32, asynchronous on
+        `ctx`'s stream (default: the first head's); scores, classes, boxes and the top-k results are scratch from that context's
+        pool."""
         n, rows, total, k, max_det = self.geometry([_f32_nchw("detection output", x) for x in xs])
         ctx = ctx or xs[0].ctx
         scores, boxes = hip.empty((n, total), ctx=ctx), hip.empty((n, total, 4), ctx=ctx)
