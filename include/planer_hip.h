@@ -807,6 +807,50 @@ int pl_yolo_decode_f32(pl_ctx *ctx, const float *x, int N, int A, int C, int Gh,
                        double sy, double conf, int row, int offset, float *scores, int *classes, float *boxes);
 int pl_nms_f32(pl_ctx *ctx, const float *boxes, const int *classes, const float *sorted_scores, const long long *order, int N,
                int R, int K, double floor, double iou, int class_aware, int max_det, float *det, int *num);
+/* ---- anchor-free heads and prototype masks ----
+ * Heads of the form float32 (N, 4 R + C + Md, Gh, Gw): channels [0, 4 R) the R bins of the left, top, right and bottom side
+ * ("DFL"), then C class logits (no objectness plane), then Md mask coefficients (0: none); one prototype tensor
+ * (N, Md, Ph, Pw).  The chain: pl_dfl_decode_f32 once per head, pl_topk_f32 over the scores, pl_nms_rows_f32,
+ * pl_dfl_coefficients_f32 once per head, pl_proto_masks_f32.  Asynchronous on ctx's stream; nothing is allocated or uploaded,
+ * nothing synchronises, no atomics.
+ *
+ * pl_dfl_decode_f32: row, offset, the back-to-front storage and the outputs are pl_yolo_decode_f32's; cell (gy, gx) has anchor
+ * index offset + gy Gw + gx.  class = argmax of the C logits with pl_labels_f32_u8's rule, score = s(logit[class]) with
+ * pl_sigmoid_f32's s; a candidate iff score > (float)conf.  Per side with bins t_j: m = fmax_j t_j, e_j = expf(t_j - m),
+ * d = fl(sum_j fl(j e_j)) / fl(sum_j e_j), sums in ascending j;
+ *   x1 = fl(fl(fl(gx + 0.5) - d_l) (float)sx), y1 likewise (gy, d_t, sy), x2 = fl(fl(fl(gx + 0.5) + d_r) (float)sx), y2
+ * likewise; every operation rounded on its own, not clipped.  A non-candidate writes score -1 and leaves class and box untouched.
+ * One lane per cell; every cell reads the C class planes, only a candidate the 4 R bin planes.
+ *
+ * pl_nms_rows_f32: pl_nms_f32 (the same kernel, the same det and num) with one more output, rows (N, max_det) int32: the
+ * `order` value of every kept entry, -1 in the rows behind them; written completely.
+ *
+ * pl_dfl_coefficients_f32: x is one head (shape arguments as for the decode); for every det row d < num[n] whose anchor index
+ * row - 1 - rows[n, d] lies in [offset, offset + Gh Gw) the cell's Md coefficient values go to coef (N, max_det, Md).  The call
+ * with offset == 0 writes +0.0 into the rows at or behind num[n]: after one call per head coef is written completely.
+ *
+ * pl_proto_masks_f32: masks (N, max_det, Ph, Pw) uint8, masks[n, d, y, x] = 1 iff d < num[n], and
+ * fl(x1 kx) <= x < fl(x2 kx) and fl(y1 ky) <= y < fl(y2 ky) for det row d's box (det (N, max_det, 6), pl_nms_f32's), with
+ * kx = (float)((double)Pw / W), ky = (float)((double)Ph / H) and x, y the pixel indices as floats, and
+ * sum_k coef[n, d, k] protos[n, k, y, x] > 0 (v_mfma_f32_16x16x4_f32, k ascending in steps of four); else 0.  Every byte is
+ * written.  One workgroup per 256 pixels of an image's prototype plane; 10 KB + 512 Md' bytes of LDS, Md' the power of two >= Md.
+ *
+ * PL_EINVAL: a null pointer, a negative dimension, R < 1, C < 1, H < 1, W < 1, offset < 0 or offset + Gh Gw > row, Md of the
+ * masks entry below 4 or no multiple of 4 (and pl_nms_f32's).  PL_EUNSUPPORTED: R > PL_DFL_MAX_REG, Md > PL_MASK_MAX_COEF,
+ * max_det > PL_MASK_MAX_DET, 2^31 or more elements in a tensor (and pl_nms_f32's).  Nothing to do (N == 0, no cells, max_det == 0,
+ * Md == 0 for the coefficients, no pixels): PL_OK, no launch.  Every refusal comes before any launch and leaves the outputs
+ * untouched. */
+#define PL_DFL_MAX_REG 32
+#define PL_MASK_MAX_DET 128
+#define PL_MASK_MAX_COEF 64
+int pl_dfl_decode_f32(pl_ctx *ctx, const float *x, int N, int R, int C, int Md, int Gh, int Gw, double sx, double sy, double conf,
+                      int row, int offset, float *scores, int *classes, float *boxes);
+int pl_nms_rows_f32(pl_ctx *ctx, const float *boxes, const int *classes, const float *sorted_scores, const long long *order, int N,
+                    int R, int K, double floor, double iou, int class_aware, int max_det, float *det, int *num, int *rows);
+int pl_dfl_coefficients_f32(pl_ctx *ctx, const float *x, int N, int R, int C, int Md, int Gh, int Gw, const int *rows, const int *num,
+                            int row, int offset, int max_det, float *coef);
+int pl_proto_masks_f32(pl_ctx *ctx, const float *det, const int *num, const float *coef, const float *protos, int N, int max_det,
+                       int Md, int Ph, int Pw, int H, int W, unsigned char *masks);
 /* ---- objects as net output ----
  * pl_components_u8_i32: connected components of the uint8 class map m (N, H, W) -- pl_labels_f32_u8's output, or any label map --
  * and the region table of each image's first max_objects objects.  An object is a maximal set of pixels of one image with equal

@@ -22,7 +22,10 @@ IMAGE_OUT_TILE_PIXELS = 1024        # include/planer_hip.h PL_IMAGE_OUT_TILE_PIX
 IMAGE_OUT_LANE_PIXELS = 4           # include/planer_hip.h PL_IMAGE_OUT_LANE_PIXELS
 YOLO_MAX_ANCHORS = 8                # include/planer_hip.h PL_YOLO_MAX_ANCHORS
 NMS_MAX_CANDIDATES = 4096           # include/planer_hip.h PL_NMS_MAX_CANDIDATES
-CC_TILE_H, CC_TILE_W = 32, 64      # include/planer_hip.h PL_CC_TILE_H, PL_CC_TILE_W
+DFL_MAX_REG = 32                    # include/planer_hip.h PL_DFL_MAX_REG
+MASK_MAX_DET = 128                  # include/planer_hip.h PL_MASK_MAX_DET
+MASK_MAX_COEF = 64                  # include/planer_hip.h PL_MASK_MAX_COEF
+CC_TILE_H, CC_TILE_W = 32, 64     # include/planer_hip.h PL_CC_TILE_H, PL_CC_TILE_W
 CC_BLOCK = 2048                     # include/planer_hip.h PL_CC_BLOCK
 CC_SCAN_STEP = 1024                 # include/planer_hip.h PL_CC_SCAN_STEP
 CC_MAX_OBJECTS = 65536              # include/planer_hip.h PL_CC_MAX_OBJECTS
@@ -222,6 +225,10 @@ SIGNATURES = {
     "pl_labels_f32_u8": [_P, _P, _P, _I, _I, _I, _I, c_double],
     "pl_yolo_decode_f32": [_P, _P, _I, _I, _I, _I, _I, POINTER(c_float), c_double, c_double, c_double, _I, _I, _P, _P, _P],
     "pl_nms_f32": [_P, _P, _P, _P, _P, _I, _I, _I, c_double, c_double, _I, _I, _P, _P],
+    "pl_dfl_decode_f32": [_P, _P, _I, _I, _I, _I, _I, _I, c_double, c_double, c_double, _I, _I, _P, _P, _P],
+    "pl_nms_rows_f32": [_P, _P, _P, _P, _P, _I, _I, _I, c_double, c_double, _I, _I, _P, _P, _P],
+    "pl_dfl_coefficients_f32": [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _I, _I, _P],
+    "pl_proto_masks_f32": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "pl_components_u8_i32": [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
     "pl_peaks_f32": [_P, _P, _I, _I, _I, _I, c_double, _I, _I, _I, c_double, c_double, _P, _P, _P],
     "pl_flow_instances_f32": [_P, _P, _I, _I, _I] + [c_longlong] * 5 + [c_double, c_double, _I, _I, _I, _P, _P, _P, _P, _P],

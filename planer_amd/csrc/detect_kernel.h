@@ -22,7 +22,8 @@
 // in float32, every operation rounded on its own, no division: a zero union or a NaN suppresses nothing.  One barrier per KEPT
 // box.  A slower wave that still searches while a faster one already clears bits finds the same entry: only bits behind it
 // change.  The kept entries are a second bit mask; at the end every lane writes the rows of the kept entries it owns (row =
-// number of kept bits in front), the other rows as +0.0, and lane 0 the count: det and num are written completely.
+// number of kept bits in front), the other rows as +0.0, and lane 0 the count: det and num are written completely.  With `rows`
+// (pl_nms_rows_f32; null for pl_nms_f32) the kept entries' `order` values go to rows (N, max_det) int32 too, -1 behind them.
 #pragma once
 #include "common.h"
 #include "device_utils.h"
@@ -122,7 +123,7 @@ __device__ __forceinline__ int first_alive(const unsigned long long *mask, int w
 // grid = N.  boxes (N, R, 4), classes (N, R) or null, sorted (N, K) descending scores, order (N, K) their rows in [0, R).
 __global__ void __launch_bounds__(TPB) nms_kernel(const float *boxes, const int *classes, const float *sorted,
                                                   const long long *order, int R, int K, float low, float iou, bool class_aware,
-                                                  int max_det, float *det, int *num) {
+                                                  int max_det, float *det, int *num, int *rows) {
     extern __shared__ __attribute__((aligned(16))) unsigned char nms_smem[];
     float *x1 = reinterpret_cast<float *>(nms_smem), *y1 = x1 + K, *x2 = y1 + K, *y2 = x2 + K, *area = y2 + K;
     int *cls = reinterpret_cast<int *>(area + K);
@@ -190,9 +191,12 @@ __global__ void __launch_bounds__(TPB) nms_kernel(const float *boxes, const int 
             for (int q = 0; q < w; ++q) rowi += __popcll(keep[q]);
             float *o = d + (size_t)rowi * 6;
             o[0] = x1[j], o[1] = y1[j], o[2] = x2[j], o[3] = y2[j], o[4] = sc[j], o[5] = (float)cls[j];
+            if (rows) rows[n * (size_t)max_det + (size_t)rowi] = (int)ord[j];
         }
     }
     for (int e = kept * 6 + t; e < max_det * 6; e += TPB) d[e] = 0.f;
+    if (rows)
+        for (int e = kept + t; e < max_det; e += TPB) rows[n * (size_t)max_det + (size_t)e] = -1;
     if (t == 0) num[n] = kept;
 }
 

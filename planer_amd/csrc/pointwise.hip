@@ -11,6 +11,7 @@
 #include "image_input_kernel.h"
 #include "image_output_kernel.h"
 #include "detect_kernel.h"
+#include "dfl_kernel.h"
 #include "components_kernel.h"
 #include "flow_kernel.h"
 #include "text_kernel.h"
@@ -1014,23 +1015,110 @@ int pl_yolo_decode_f32(pl_ctx *ctx, const float *x, int N, int A, int C, int Gh,
     return PL_OK;
 }
 
-int pl_nms_f32(pl_ctx *ctx, const float *boxes, const int *classes, const float *sorted_scores, const long long *order, int N, int R,
-               int K, double floor, double iou, int class_aware, int max_det, float *det, int *num) {
+namespace {
+// pl_nms_f32 (rows null) and pl_nms_rows_f32: the same checks, the same kernel
+int nms_entry(const char *who, pl_ctx *ctx, const float *boxes, const int *classes, const float *sorted_scores, const long long *order,
+              int N, int R, int K, double floor, double iou, int class_aware, int max_det, float *det, int *num, int *rows) {
     namespace dt = detect;
-    PL_REQUIRE(ctx && boxes && sorted_scores && order && det && num, PL_EINVAL, "pl_nms_f32: null argument");
-    PL_REQUIRE(N >= 0 && R >= 0 && K >= 0 && max_det >= 0, PL_EINVAL, "pl_nms_f32: bad shape N = %d, R = %d, K = %d, max_det = %d", N, R, K,
+    PL_REQUIRE(ctx && boxes && sorted_scores && order && det && num, PL_EINVAL, "%s: null argument", who);
+    PL_REQUIRE(N >= 0 && R >= 0 && K >= 0 && max_det >= 0, PL_EINVAL, "%s: bad shape N = %d, R = %d, K = %d, max_det = %d", who, N, R, K,
                max_det);
-    PL_REQUIRE(K <= R, PL_EINVAL, "pl_nms_f32: K = %d entries of %d rows", K, R);
-    PL_REQUIRE(K <= dt::NMS_MAX_K, PL_EUNSUPPORTED, "pl_nms_f32: at most %d entries per image, got K = %d", dt::NMS_MAX_K, K);
-    PL_REQUIRE(max_det <= K, PL_EUNSUPPORTED, "pl_nms_f32: max_det = %d exceeds K = %d", max_det, K);
-    PL_REQUIRE(below_2_31(N, 4, R) && below_2_31(N, 6, max_det), PL_EUNSUPPORTED, "pl_nms_f32: 2^31 or more floats in a tensor");
+    PL_REQUIRE(K <= R, PL_EINVAL, "%s: K = %d entries of %d rows", who, K, R);
+    PL_REQUIRE(K <= dt::NMS_MAX_K, PL_EUNSUPPORTED, "%s: at most %d entries per image, got K = %d", who, dt::NMS_MAX_K, K);
+    PL_REQUIRE(max_det <= K, PL_EUNSUPPORTED, "%s: max_det = %d exceeds K = %d", who, max_det, K);
+    PL_REQUIRE(below_2_31(N, 4, R) && below_2_31(N, 6, max_det), PL_EUNSUPPORTED, "%s: 2^31 or more floats in a tensor", who);
     if (N == 0) return PL_OK;
     CtxGuard g(ctx);
     const size_t lds = dt::nms_lds_bytes(K);
     if (lds > 48 * 1024)
         PL_HIP(hipFuncSetAttribute((const void *)dt::nms_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     dt::nms_kernel<<<(unsigned)N, dt::TPB, lds, ctx->stream>>>(boxes, classes, sorted_scores, order, R, K, (float)floor, (float)iou,
-                                                               class_aware != 0, max_det, det, num);
+                                                               class_aware != 0, max_det, det, num, rows);
+    PL_LAUNCH_CHECK();
+    return PL_OK;
+}
+}  // namespace
+
+int pl_nms_f32(pl_ctx *ctx, const float *boxes, const int *classes, const float *sorted_scores, const long long *order, int N, int R,
+               int K, double floor, double iou, int class_aware, int max_det, float *det, int *num) {
+    return nms_entry("pl_nms_f32", ctx, boxes, classes, sorted_scores, order, N, R, K, floor, iou, class_aware, max_det, det, num, nullptr);
+}
+
+int pl_nms_rows_f32(pl_ctx *ctx, const float *boxes, const int *classes, const float *sorted_scores, const long long *order, int N,
+                    int R, int K, double floor, double iou, int class_aware, int max_det, float *det, int *num, int *rows) {
+    PL_REQUIRE(rows, PL_EINVAL, "pl_nms_rows_f32: null argument");
+    return nms_entry("pl_nms_rows_f32", ctx, boxes, classes, sorted_scores, order, N, R, K, floor, iou, class_aware, max_det, det, num, rows);
+}
+
+// Anchor-free heads and prototype masks (dfl_kernel.h).  Every refusal comes before any launch.
+int pl_dfl_decode_f32(pl_ctx *ctx, const float *x, int N, int R, int C, int Md, int Gh, int Gw, double sx, double sy, double conf,
+                      int row, int offset, float *scores, int *classes, float *boxes) {
+    PL_REQUIRE(ctx && x && scores && classes && boxes, PL_EINVAL, "pl_dfl_decode_f32: null argument");
+    PL_REQUIRE(N >= 0 && Md >= 0 && Gh >= 0 && Gw >= 0 && row >= 0, PL_EINVAL,
+               "pl_dfl_decode_f32: bad shape (%d, 4 x %d + %d + %d, %d, %d), row %d", N, R, C, Md, Gh, Gw, row);
+    PL_REQUIRE(R >= 1 && C >= 1, PL_EINVAL, "pl_dfl_decode_f32: at least one bin and one class, got R = %d, C = %d", R, C);
+    const size_t HW = (size_t)Gh * Gw;
+    PL_REQUIRE(offset >= 0 && HW < (1ull << 31) && HW <= (size_t)row && (size_t)offset <= (size_t)row - HW, PL_EINVAL,
+               "pl_dfl_decode_f32: %d x %d cells at offset %d do not fit a row of %d", Gh, Gw, offset, row);
+    PL_REQUIRE(R <= dfl::MAX_REG, PL_EUNSUPPORTED, "pl_dfl_decode_f32: at most %d bins per side, got R = %d", dfl::MAX_REG, R);
+    const size_t CH = 4 * (size_t)R + (size_t)C + (size_t)Md;
+    PL_REQUIRE(below_2_31(N, CH, HW) && below_2_31(N, 4, row), PL_EUNSUPPORTED, "pl_dfl_decode_f32: 2^31 or more floats in a tensor");
+    if (N == 0 || HW == 0) return PL_OK;
+    CtxGuard g(ctx);
+    const unsigned tiles = cdiv(HW, dfl::TPB);
+    dfl::decode_kernel<<<(unsigned)N * tiles, dfl::TPB, 0, ctx->stream>>>(x, scores, classes, boxes, R, C, CH, Gw, HW, tiles, (float)sx,
+                                                                          (float)sy, (float)conf, (size_t)row, (size_t)offset);
+    PL_LAUNCH_CHECK();
+    return PL_OK;
+}
+
+int pl_dfl_coefficients_f32(pl_ctx *ctx, const float *x, int N, int R, int C, int Md, int Gh, int Gw, const int *rows, const int *num,
+                            int row, int offset, int max_det, float *coef) {
+    PL_REQUIRE(ctx && x && rows && num && coef, PL_EINVAL, "pl_dfl_coefficients_f32: null argument");
+    PL_REQUIRE(N >= 0 && R >= 1 && C >= 1 && Md >= 0 && Gh >= 0 && Gw >= 0 && row >= 0 && max_det >= 0, PL_EINVAL,
+               "pl_dfl_coefficients_f32: bad shape (%d, 4 x %d + %d + %d, %d, %d), row %d, max_det %d", N, R, C, Md, Gh, Gw, row, max_det);
+    const size_t HW = (size_t)Gh * Gw;
+    PL_REQUIRE(offset >= 0 && HW < (1ull << 31) && HW <= (size_t)row && (size_t)offset <= (size_t)row - HW, PL_EINVAL,
+               "pl_dfl_coefficients_f32: %d x %d cells at offset %d do not fit a row of %d", Gh, Gw, offset, row);
+    const size_t CH = 4 * (size_t)R + (size_t)C + (size_t)Md;
+    PL_REQUIRE(below_2_31(N, CH, HW) && below_2_31(N, max_det, Md), PL_EUNSUPPORTED,
+               "pl_dfl_coefficients_f32: 2^31 or more floats in a tensor");
+    const size_t total = (size_t)N * max_det * Md;
+    if (total == 0) return PL_OK;
+    CtxGuard g(ctx);
+    dfl::coefficients_kernel<<<cdiv(total, dfl::TPB), dfl::TPB, 0, ctx->stream>>>(x, rows, num, coef, total, max_det, Md, CH,
+                                                                                 4 * (size_t)R + (size_t)C, HW, (long long)row,
+                                                                                 (long long)offset);
+    PL_LAUNCH_CHECK();
+    return PL_OK;
+}
+
+int pl_proto_masks_f32(pl_ctx *ctx, const float *det, const int *num, const float *coef, const float *protos, int N, int max_det,
+                       int Md, int Ph, int Pw, int H, int W, unsigned char *masks) {
+    PL_REQUIRE(ctx && det && num && coef && protos && masks, PL_EINVAL, "pl_proto_masks_f32: null argument");
+    PL_REQUIRE(N >= 0 && max_det >= 0 && Ph >= 0 && Pw >= 0 && H >= 1 && W >= 1, PL_EINVAL,
+               "pl_proto_masks_f32: bad shape N = %d, max_det = %d, protos (%d, %d), input (%d, %d)", N, max_det, Ph, Pw, H, W);
+    PL_REQUIRE(Md >= 4 && Md % 4 == 0, PL_EINVAL, "pl_proto_masks_f32: Md is a multiple of 4 from 4 up, got %d", Md);
+    PL_REQUIRE(Md <= dfl::MASK_MAX_COEF, PL_EUNSUPPORTED, "pl_proto_masks_f32: at most %d coefficients, got Md = %d", dfl::MASK_MAX_COEF, Md);
+    PL_REQUIRE(max_det <= dfl::MASK_MAX_DET, PL_EUNSUPPORTED, "pl_proto_masks_f32: at most %d rows per image, got max_det = %d",
+               dfl::MASK_MAX_DET, max_det);
+    const size_t P = (size_t)Ph * Pw;
+    PL_REQUIRE(P < (1ull << 31) && below_2_31(N, Md, P) && below_2_31(N, max_det, P), PL_EUNSUPPORTED,
+               "pl_proto_masks_f32: 2^31 or more prototype floats or mask bytes");
+    if (N == 0 || max_det == 0 || P == 0) return PL_OK;
+    CtxGuard g(ctx);
+    const unsigned tiles = cdiv(P, dfl::TILE_PX), grid = (unsigned)N * tiles;
+    const float kx = (float)((double)Pw / (double)W), ky = (float)((double)Ph / (double)H);
+    const bool vin = aligned16(protos) && P % 4 == 0, vout = aligned16(masks) && P % 16 == 0;
+#define PL_MASKS_LAUNCH(KS)                                                                                                       \
+    dfl::proto_masks_kernel<KS><<<grid, dfl::TPB, 0, ctx->stream>>>(det, num, coef, protos, max_det, Md, (unsigned)Pw, (unsigned)P, \
+                                                                    tiles, kx, ky, vin, vout, masks)
+    if (Md <= 4) PL_MASKS_LAUNCH(1);
+    else if (Md <= 8) PL_MASKS_LAUNCH(2);
+    else if (Md <= 16) PL_MASKS_LAUNCH(4);
+    else if (Md <= 32) PL_MASKS_LAUNCH(8);
+    else PL_MASKS_LAUNCH(16);
+#undef PL_MASKS_LAUNCH
     PL_LAUNCH_CHECK();
     return PL_OK;
 }

@@ -506,25 +506,34 @@ class Net:
         of that declaration's heads."""
         index = self._out_index(index)
         self._image_out.pop(index, None)
-        if self._detect is not None and (self._detect[1] is None or index in self._detect[1]):
+        if self._detect is not None and (self._detect[1] is None or index in self._detect[1] or index == self._detect[0].protos):
             self._detect = None
         return self
 
     def detection_output(self, heads, classes, conf=0.25, iou=0.45, max_det=100, max_candidates=1024, class_aware=True, size=None,
-                         indices=None):
+                         indices=None, protos=None):
         """The outputs at positions `indices` (in head order; default: every output, in order) are YOLO-style heads, float32
         (N, A (5 + classes), Gh, Gw), head h with anchors and stride heads[h] = (anchors, stride or None).  In their place the
         net returns det, float32 (N, max_det, 6) rows [x1, y1, x2, y2, score, class] in input pixels by descending score (+0.0
         in unused rows), and num, int32 (N,), inserted where the lowest of those positions was; the other outputs keep their
         order.  Decode, top-k and NMS run behind the pass on the stream that owns the outputs (util.DetectionSpec): plans are
-        not touched.  Declaring again replaces the declaration; `float_output` on one of the positions removes it."""
-        spec = DetectionSpec(heads, classes, conf, iou, max_det, max_candidates, class_aware, size)
+        not touched.  Declaring again replaces the declaration; `float_output` on one of the positions removes it.
+        Anchor-free heads are declared as heads[h] = ("dfl", stride or None[, reg_max = 16]), float32
+        (N, 4 reg_max + classes + Md, Gh, Gw): the bins of the left, top, right and bottom side, the class logits (no
+        objectness), Md mask coefficients.  With `protos`, the position of the float32 prototype tensor (N, Md, Ph, Pw) among
+        the outputs (then `size` is needed and max_det is at most 128), masks, uint8 (N, max_det, Ph, Pw), follows num: 1 where
+        the row's coefficients times the prototypes are positive inside its box at prototype scale; the prototype tensor is
+        not handed back, and without `indices` the heads are every other output."""
+        if protos is not None:
+            protos = self._out_index(protos)
+        spec = DetectionSpec(heads, classes, conf, iou, max_det, max_candidates, class_aware, size, protos)
         if indices is not None:
             indices = tuple(self._out_index(i) for i in indices)
-            if len(indices) != len(spec.heads) or len(set(indices)) != len(indices):
+            if len(indices) != len(spec.heads) or len(set(indices)) != len(indices) or protos in indices:
                 raise ValueError("detection output: indices names one distinct output position per head (%d), got %r"
                                  % (len(spec.heads), indices))
-        taken = sorted(self._image_out if indices is None else set(indices) & set(self._image_out))
+        claimed = None if indices is None else set(indices) | ({protos} if protos is not None else set())
+        taken = sorted(self._image_out if claimed is None else claimed & set(self._image_out))
         if taken:
             raise ValueError("detection output: output %d is already declared an image or label output" % taken[0])
         self._detect = (spec, indices)
@@ -643,7 +652,7 @@ class Net:
 
     def _unclaimed(self, index):
         index = self._out_index(index)
-        if self._detect is not None and (self._detect[1] is None or index in self._detect[1]):
+        if self._detect is not None and (self._detect[1] is None or index in self._detect[1] or index == self._detect[0].protos):
             raise ValueError("output %d is a head of the declared detection output" % index)
         return index
 
@@ -667,15 +676,15 @@ class Net:
             return None
         spec, idx = self._detect
         if idx is None:
-            idx = tuple(range(len(seq)))
+            idx = tuple(i for i in range(len(seq)) if i != spec.protos)
             if len(idx) != len(spec.heads):
                 raise ValueError("detection output: %d heads declared, the net returns %d output(s)" % (len(spec.heads), len(seq)))
-        for i in idx:
+        for i in idx + (() if spec.protos is None else (spec.protos,)):
             if i >= len(seq):
                 raise ValueError("output %d is declared a detection head, the net returns %d output(s)" % (i, len(seq)))
             if not isinstance(seq[i], DeviceArray):
                 raise ValueError("output %d is declared a detection head and is no device tensor: %s" % (i, type(seq[i]).__name__))
-        spec.check([seq[i] for i in idx])
+        spec.check([seq[i] for i in idx], None if spec.protos is None else seq[spec.protos])
         return idx
 
     def _hand_back(self, out, private):
@@ -685,8 +694,10 @@ class Net:
             return out
         heads = self._check_outputs(out)
         seq = out if isinstance(out, tuple) else (out,)
+        protos = self._detect[0].protos if heads is not None else None
         rst = [self._image_out[i].encode(o) if i in self._image_out else
-               o.copy() if private and isinstance(o, DeviceArray) and not (heads and i in heads) else o for i, o in enumerate(seq)]
+               o.copy() if private and isinstance(o, DeviceArray) and not (heads and (i in heads or i == protos)) else o
+               for i, o in enumerate(seq)]
         # a spec says how many places its arrays take: an object output's four, a keypoint output's two
         places = [tuple(r) if i in self._image_out and self._image_out[i].places > 1 else (r,) for i, r in enumerate(rst)]
         if heads is None:
@@ -694,8 +705,9 @@ class Net:
             return flat if isinstance(out, tuple) or len(flat) > 1 else flat[0]
         # det, num where the lowest head was; the heads themselves are not handed back (nor copied)
         first = min(heads)
-        det_num = self._detect[0].encode([seq[i] for i in heads])
-        return tuple(r for i, p in enumerate(places) for r in (det_num if i == first else () if i in heads else p))
+        xs = [seq[i] for i in heads]
+        det_num = self._detect[0].encode(xs) if protos is None else self._detect[0].encode(xs, protos=seq[protos])
+        return tuple(r for i, p in enumerate(places) for r in (det_num if i == first else () if i in heads or i == protos else p))
 
     def _image_spec(self, pos):
         name = self.input[pos] if pos < len(self.input) else None

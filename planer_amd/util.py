@@ -326,15 +326,20 @@ def _f32v(v):
     return float(numpy.float32(v))
 
 
-def _nms_sorted(boxes, classes, scores, n, r, k, floor, iou, class_aware, max_det, ctx):
+def _nms_sorted(boxes, classes, scores, n, r, k, floor, iou, class_aware, max_det, ctx, kept=None):
     """top-k of scores (N, R) and pl_nms_f32 on the k first of each image: (det (N, max_det, 6), num (N,)), fresh arrays.  The
-    top-k is pl_topk_f32 or, where layer.topk_select_eligible says so, pl_topk_select_f32: the same bits."""
+    top-k is pl_topk_f32 or, where layer.topk_select_eligible says so, pl_topk_select_f32: the same bits.  With `kept`, int32
+    (N, max_det), pl_nms_rows_f32 writes the kept entries' rows there too."""
     vals, idx = hip.empty((n, k), ctx=ctx), hip.empty((n, k), numpy.int64, ctx=ctx)
     if n and k:
         _topk_launch(ctx, scores.ptr, n, r, 1, k, 1, vals, idx)
     det, num = hip.empty((n, max_det, 6), ctx=ctx), hip.empty((n,), numpy.int32, ctx=ctx)
-    _lib.call("pl_nms_f32", ctx.handle, boxes.ptr, classes.ptr if classes is not None else None, vals.ptr, idx.ptr, n, r, k,
-              floor, iou, int(bool(class_aware)), max_det, det.ptr, num.ptr)
+    args = (ctx.handle, boxes.ptr, classes.ptr if classes is not None else None, vals.ptr, idx.ptr, n, r, k,
+            floor, iou, int(bool(class_aware)), max_det, det.ptr, num.ptr)
+    if kept is None:
+        _lib.call("pl_nms_f32", *args)
+    else:
+        _lib.call("pl_nms_rows_f32", *args, kept.ptr)
     return det, num
 
 
@@ -347,9 +352,35 @@ class DetectionSpec:
     box, class_aware: of the same class), which stops after max_det.  conf, iou, anchors and strides are rounded to float32, the
     numbers the kernels compute with.  Host values only."""
 
-    def __init__(self, heads, classes, conf=0.25, iou=0.45, max_det=100, max_candidates=1024, class_aware=True, size=None):
+    def __init__(self, heads, classes, conf=0.25, iou=0.45, max_det=100, max_candidates=1024, class_aware=True, size=None, protos=None):
+        heads = list(heads)
+        dfl = [isinstance(head, (tuple, list)) and len(head) > 0 and isinstance(head[0], str) for head in heads]
+        self.dfl = any(dfl)
+        if self.dfl and not all(dfl):
+            raise ValueError("detection output: all heads are of one form, (anchors, stride) or (\"dfl\", stride[, reg_max]), got a mix")
+        self.protos = protos
+        if protos is not None:
+            if not self.dfl:
+                raise ValueError("detection output: protos go with \"dfl\" heads only")
+            if not _is_int(max_det, 1, _lib.MASK_MAX_DET):
+                raise ValueError("detection output: with protos max_det is 1 to %d, got %r" % (_lib.MASK_MAX_DET, max_det))
+            if size is None:
+                raise ValueError("detection output: protos need size, the input's (H, W), to scale the boxes by")
         self.heads = []
         for h, head in enumerate(heads):
+            if self.dfl:
+                if head[0] != "dfl" or len(head) not in (2, 3):
+                    raise ValueError("detection output: head %d is (\"dfl\", stride or None[, reg_max]), got %r" % (h, head))
+                stride, reg_max = head[1], head[2] if len(head) == 3 else 16
+                if not _is_int(reg_max, 1, _lib.DFL_MAX_REG):
+                    raise ValueError("detection output: head %d has reg_max %r, 1 to %d fit" % (h, reg_max, _lib.DFL_MAX_REG))
+                if stride is not None:
+                    try:
+                        stride = tuple(_f32v(s) for s in numpy.broadcast_to(numpy.asarray(stride, numpy.float64), (2,)))
+                    except (TypeError, ValueError):
+                        raise ValueError("detection output: head %d is (\"dfl\", stride or None[, reg_max]), got %r" % (h, head))
+                self.heads.append((int(reg_max), stride))
+                continue
             try:
                 anchors, stride = head
                 anchors = numpy.asarray(anchors, numpy.float64).reshape(-1, 2)
@@ -374,21 +405,41 @@ class DetectionSpec:
                 raise ValueError("detection output: size is the input's (H, W), got %r" % (size,))
         self.classes, self.max_det, self.max_candidates = int(classes), int(max_det), int(max_candidates)
         self.conf, self.iou, self.class_aware, self.size = _f32v(conf), _f32v(iou), bool(class_aware), size
-        self._anchors = [(_lib.c_float * a.size)(*a.ravel().tolist()) for a, _ in self.heads]       # kept alive here
+        self._anchors = [] if self.dfl else [(_lib.c_float * a.size)(*a.ravel().tolist()) for a, _ in self.heads]     # kept alive here
 
-    def geometry(self, shapes):
+    def _proto_geometry(self, n, shape):
+        """(Md, Ph, Pw) of the prototype tensor's `shape` beside heads of batch size n, or a ValueError."""
+        if shape is None or len(tuple(shape)) != 4:
+            raise ValueError("detection output: protos is a float32 tensor (N, Md, Ph, Pw), got shape %s" % (shape,))
+        pn, md, ph, pw = tuple(shape)
+        if n is not None and pn != n:
+            raise ValueError("detection output: protos has batch size %d, head 0 has %d" % (pn, n))
+        if md % 4 or not 4 <= md <= _lib.MASK_MAX_COEF:
+            raise ValueError("detection output: protos has %d planes, a multiple of 4 from 4 to %d fits" % (md, _lib.MASK_MAX_COEF))
+        return md, ph, pw
+
+    def geometry(self, shapes, protos=None):
         """(N, [(A, C, Gh, Gw, sx, sy, offset) per head], A_total, k, max_det) for head tensors of `shapes`, k the entries NMS
-        sees and max_det the rows of det (min(self.max_det, k)), or a ValueError that names what does not fit."""
+        sees and max_det the rows of det (min(self.max_det, k)), or a ValueError that names what does not fit.  For "dfl" heads
+        A is reg_max and a head has Gh Gw anchors; declared with protos, `protos` is the prototype tensor's shape and
+        (Md, Ph, Pw) follows max_det."""
         shapes = [tuple(s) for s in shapes]
         if len(shapes) != len(self.heads):
             raise ValueError("detection output: %d heads declared, %d tensors given" % (len(self.heads), len(shapes)))
+        md = None
+        if self.protos is not None:
+            md = self._proto_geometry(shapes[0][0] if len(shapes[0]) == 4 else None, protos)
         rows, off = [], 0
         for h, (shape, (anchors, stride)) in enumerate(zip(shapes, self.heads)):
             if len(shape) != 4:
-                raise ValueError("detection output: head %d is (N, A (5 + C), Gh, Gw), got shape %s" % (h, shape))
+                raise ValueError("detection output: head %d is (N, %s, Gh, Gw), got shape %s"
+                                 % (h, "4 R + C + Md" if self.dfl else "A (5 + C)", shape))
             n, ch, gh, gw = shape
-            a = len(anchors)
-            if ch != a * (5 + self.classes):
+            a = anchors if self.dfl else len(anchors)
+            if self.dfl and ch != 4 * a + self.classes + (md[0] if md else 0):
+                raise ValueError("detection output: head %d has %d channels, 4 x %d bins + %d classes + %d coefficients is %d"
+                                 % (h, ch, a, self.classes, md[0] if md else 0, 4 * a + self.classes + (md[0] if md else 0)))
+            if not self.dfl and ch != a * (5 + self.classes):
                 raise ValueError("detection output: head %d has %d channels, %d anchors x (5 + %d classes) is %d"
                                  % (h, ch, a, self.classes, a * (5 + self.classes)))
             if n != shapes[0][0]:
@@ -398,32 +449,63 @@ class DetectionSpec:
                     raise ValueError("detection output: head %d has no stride and there is no input size to derive it from" % h)
                 stride = _f32v(self.size[1] / gw), _f32v(self.size[0] / gh)
             rows.append((a, self.classes, gh, gw, stride[0], stride[1], off))
-            off += a * gh * gw
+            off += gh * gw if self.dfl else a * gh * gw
         k = min(self.max_candidates, off)
-        return shapes[0][0], rows, off, k, min(self.max_det, k)
+        geo = shapes[0][0], rows, off, k, min(self.max_det, k)
+        return geo if md is None else geo + (md,)
 
-    def check(self, xs):
-        self.geometry([_f32_nchw("detection output", x) for x in xs])
+    def check(self, xs, protos=None):
+        self.geometry([_f32_nchw("detection output", x) for x in xs],
+                      None if self.protos is None else _f32_nchw("detection output: protos", protos))
 
-    def encode(self, xs, ctx=None):
+    def encode(self, xs, ctx=None, protos=None):
         """(det, num) of the head tensors `xs`: det float32 (N, max_det, 6), rows [x1, y1, x2, y2, score, class] by descending
         score and +0.0 behind them, num int32 (N,); fresh arrays (max_det is at most the number of anchors).  One
         pl_yolo_decode_f32 per head, pl_topk_f32 (rows of 4096 anchors and more: pl_topk_select_f32), pl_nms_f32, asynchronous on
         `ctx`'s stream (default: the first head's); scores, classes, boxes and the top-k results are scratch from that context's
-        pool."""
-        n, rows, total, k, max_det = self.geometry([_f32_nchw("detection output", x) for x in xs])
+        pool.  "dfl" heads: pl_dfl_decode_f32 per head; declared with protos, `protos` (default: the declared tensor) is the
+        float32 (N, Md, Ph, Pw) prototype tensor and the result is (det, num, masks), masks uint8 (N, max_det, Ph, Pw):
+        pl_nms_rows_f32, pl_dfl_coefficients_f32 per head and pl_proto_masks_f32 follow."""
+        if not self.dfl:
+            n, rows, total, k, max_det = self.geometry([_f32_nchw("detection output", x) for x in xs])
+            ctx = ctx or xs[0].ctx
+            scores, boxes = hip.empty((n, total), ctx=ctx), hip.empty((n, total, 4), ctx=ctx)
+            classes = hip.empty((n, total), numpy.int32, ctx=ctx)
+            for x, anchors, (a, c, gh, gw, sx, sy, off) in zip(xs, self._anchors, rows):
+                _lib.call("pl_yolo_decode_f32", ctx.handle, x.ptr, n, a, c, gh, gw, anchors, sx, sy, self.conf, total, off,
+                          scores.ptr, classes.ptr, boxes.ptr)
+            return _nms_sorted(boxes, classes, scores, n, total, k, self.conf, self.iou, self.class_aware, max_det, ctx)
+        if self.protos is not None and protos is None:
+            protos = self.protos
+        shapes = [_f32_nchw("detection output", x) for x in xs]
+        if self.protos is None:
+            (n, rows, total, k, max_det), md = self.geometry(shapes), 0
+        else:
+            n, rows, total, k, max_det, (md, ph, pw) = self.geometry(shapes, _f32_nchw("detection output: protos", protos))
         ctx = ctx or xs[0].ctx
         scores, boxes = hip.empty((n, total), ctx=ctx), hip.empty((n, total, 4), ctx=ctx)
         classes = hip.empty((n, total), numpy.int32, ctx=ctx)
-        for x, anchors, (a, c, gh, gw, sx, sy, off) in zip(xs, self._anchors, rows):
-            _lib.call("pl_yolo_decode_f32", ctx.handle, x.ptr, n, a, c, gh, gw, anchors, sx, sy, self.conf, total, off,
+        for x, (r, c, gh, gw, sx, sy, off) in zip(xs, rows):
+            _lib.call("pl_dfl_decode_f32", ctx.handle, x.ptr, n, r, c, md, gh, gw, sx, sy, self.conf, total, off,
                       scores.ptr, classes.ptr, boxes.ptr)
-        return _nms_sorted(boxes, classes, scores, n, total, k, self.conf, self.iou, self.class_aware, max_det, ctx)
+        if not md:
+            return _nms_sorted(boxes, classes, scores, n, total, k, self.conf, self.iou, self.class_aware, max_det, ctx)
+        kept = hip.empty((n, max_det), numpy.int32, ctx=ctx)
+        det, num = _nms_sorted(boxes, classes, scores, n, total, k, self.conf, self.iou, self.class_aware, max_det, ctx, kept)
+        coef = hip.empty((n, max_det, md), ctx=ctx)
+        for x, (r, c, gh, gw, sx, sy, off) in zip(xs, rows):
+            _lib.call("pl_dfl_coefficients_f32", ctx.handle, x.ptr, n, r, c, md, gh, gw, kept.ptr, num.ptr, total, off, max_det, coef.ptr)
+        masks = hip.empty((n, max_det, ph, pw), numpy.uint8, ctx=ctx)
+        _lib.call("pl_proto_masks_f32", ctx.handle, det.ptr, num.ptr, coef.ptr, protos.ptr, n, max_det, md, ph, pw,
+                  self.size[0], self.size[1], masks.ptr)
+        return det, num, masks
 
 
-def decode_detections(xs, heads, classes, conf=0.25, iou=0.45, max_det=100, max_candidates=1024, class_aware=True, size=None):
-    """(det, num) of YOLO-style head tensors `xs` (float32 DeviceArrays): `DetectionSpec(heads, classes, ...).encode(xs)`."""
-    return DetectionSpec(heads, classes, conf, iou, max_det, max_candidates, class_aware, size).encode(list(xs))
+def decode_detections(xs, heads, classes, conf=0.25, iou=0.45, max_det=100, max_candidates=1024, class_aware=True, size=None,
+                      protos=None):
+    """(det, num) of YOLO-style head tensors `xs` (float32 DeviceArrays): `DetectionSpec(heads, classes, ...).encode(xs)`; with
+    "dfl" heads and `protos`, the prototype tensor, (det, num, masks)."""
+    return DetectionSpec(heads, classes, conf, iou, max_det, max_candidates, class_aware, size, protos).encode(list(xs))
 
 
 def nms(boxes, scores, classes=None, iou=0.45, max_det=100, floor=-math.inf):

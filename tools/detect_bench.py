@@ -252,6 +252,79 @@ def kernels_child(args):
             print(json.dumps(line), flush=True)
 
 
+def dfl_child(args):
+    """--head dfl: the anchor-free chain with masks on synthetic heads of YOLOv8-seg's geometry at 640 x 640: cells
+    80^2 + 40^2 + 20^2, 80 classes, reg_max 16, 32 coefficients, prototypes (32, 160, 160).  Every launch alone (HIP events
+    around --launches launches, best of 5), the whole chain through DetectionSpec.encode, and what a caller without it does
+    instead: download the heads and prototypes, then the numpy box decode of the candidates and `coef @ protos > 0`."""
+    sys.path.insert(0, HERE)
+    import planer_amd
+    from planer_amd import _lib, hip, layer
+    ctx = hip.context()
+    rng = np.random.default_rng(0)
+    R, C, MD, P, size = 16, 80, 32, 160, 640
+
+    def timed(fn):
+        for _ in range(5):
+            fn()
+        best = None
+        for _ in range(5):
+            e0 = hip.Event(ctx).record()
+            for _ in range(args.launches):
+                fn()
+            e1 = hip.Event(ctx).record()
+            t = e0.elapsed_ms(e1) / args.launches * 1e3
+            best = t if best is None else min(best, t)
+        return round(best, 2)
+    for n in (1, 8):
+        host = [(rng.standard_normal((n, 4 * R + C + MD, g, g)) * 1.5).astype(np.float32) for g in (80, 40, 20)]
+        for h in host:
+            h[:, 4 * R:4 * R + C] -= 5.5                                   # about a hundred candidates per image at conf 0.25
+        protos_host = rng.standard_normal((n, MD, P, P)).astype(np.float32)
+        heads, protos = [hip.asarray(h) for h in host], hip.asarray(protos_host)
+        spec = planer_amd.util.DetectionSpec([("dfl", None, R)] * 3, C, conf=0.25, iou=IOU, max_det=MAX_DET, max_candidates=MAX_CANDIDATES,
+                                             size=(size, size), protos=protos)
+        _, rows, total, k, md, _ = spec.geometry([h.shape for h in heads], protos.shape)
+        scores, boxes, classes = hip.empty((n, total)), hip.empty((n, total, 4)), hip.empty((n, total), np.int32)
+        vals, idx = hip.empty((n, k)), hip.empty((n, k), np.int64)
+        det, num, kept = hip.empty((n, md, 6)), hip.empty((n,), np.int32), hip.empty((n, md), np.int32)
+        coef, masks = hip.empty((n, md, MD)), hip.empty((n, md, P, P), np.uint8)
+        line = {"head": "dfl", "batch": n, "anchors": total, "k": k, "max_det": md, "launches": args.launches}
+
+        def per_head(name, i, *tail):
+            r, c, gh, gw, sx, sy, off = rows[i]
+            mid = (sx, sy, spec.conf, total, off) if name == "pl_dfl_decode_f32" else (kept.ptr, num.ptr, total, off, md)
+            return lambda: _lib.call(name, ctx.handle, heads[i].ptr, n, r, c, MD, gh, gw, *mid, *tail)
+        for i, grid in enumerate((80, 40, 20)):
+            line["decode%d_us" % grid] = timed(per_head("pl_dfl_decode_f32", i, scores.ptr, classes.ptr, boxes.ptr))
+        line["topk_us"] = timed(lambda: layer._topk_launch(ctx, scores.ptr, n, total, 1, k, 1, vals, idx))
+        nms = (ctx.handle, boxes.ptr, classes.ptr, vals.ptr, idx.ptr, n, total, k, spec.conf, spec.iou, 1, md, det.ptr, num.ptr)
+        line["nms_us"] = timed(lambda: _lib.call("pl_nms_f32", *nms))
+        line["nms_rows_us"] = timed(lambda: _lib.call("pl_nms_rows_f32", *nms, kept.ptr))
+        for i, grid in enumerate((80, 40, 20)):
+            line["coef%d_us" % grid] = timed(per_head("pl_dfl_coefficients_f32", i, coef.ptr))
+        line["masks_us"] = timed(lambda: _lib.call("pl_proto_masks_f32", ctx.handle, det.ptr, num.ptr, coef.ptr, protos.ptr, n, md, MD, P, P,
+                                                   size, size, masks.ptr))
+        line["masks_bytes"] = int(masks.nbytes + protos.nbytes)
+        line["chain_us"] = timed(lambda: spec.encode(heads))
+        line["kept_per_image"] = float(num.get().mean())
+        line["candidates_per_image"] = float((scores.get() > 0).sum(1).mean())
+        # the caller's host step on the same data: downloads, then numpy
+        t0 = time.perf_counter()
+        got = [h.get() for h in heads] + [protos.get()]
+        line["download_ms"] = round((time.perf_counter() - t0) * 1e3, 2)
+        c_host, d_host = coef.get(), det.get()
+        t0 = time.perf_counter()
+        for i in range(n):
+            m = (c_host[i] @ got[3][i].reshape(MD, -1)).reshape(md, P, P) > 0
+            x1, y1, x2, y2 = (d_host[i, :, j, None, None] * 0.25 for j in range(4))
+            ys, xs = np.arange(P, dtype=np.float32)[None, :, None], np.arange(P, dtype=np.float32)[None, None, :]
+            m &= (x1 <= xs) & (xs < x2) & (y1 <= ys) & (ys < y2)
+        line["host_masks_ms_per_image"] = round((time.perf_counter() - t0) * 1e3 / n, 2)
+        line["masks_equal_host"] = bool(n == 0 or (m == (masks.get()[n - 1] > 0)).mean() > 0.9999)
+        print(json.dumps(line), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=3)
@@ -267,13 +340,14 @@ def main():
     ap.add_argument("--timeout", type=int, default=300, help="seconds one child process may take")
     ap.add_argument("--launches", type=int, default=50, help="launches between the two events of a kernel timing")
     ap.add_argument("--no-kernels", action="store_true")
-    ap.add_argument("--child", choices=["arm", "kernels"])
+    ap.add_argument("--head", choices=["yolo", "dfl"], default="yolo", help="dfl: only the anchor-free chain with masks, on synthetic heads")
+    ap.add_argument("--child", choices=["arm", "kernels", "dfl"])
     ap.add_argument("--arm")
     ap.add_argument("--root")
     ap.add_argument("--round", type=int, default=0)
     args = ap.parse_args()
     if args.child:
-        return arm_child(args) if args.child == "arm" else kernels_child(args)
+        return {"arm": arm_child, "kernels": kernels_child, "dfl": dfl_child}[args.child](args)
     tmp = None
     if args.cache is None:
         tmp = tempfile.TemporaryDirectory()
@@ -293,6 +367,9 @@ def main():
                 print(json.dumps(ln), flush=True)
                 f.write(json.dumps(ln) + "\n")
         return lines
+    if args.head == "dfl":
+        step(["--child", "dfl"])
+        return
     arms = [a for a in args.arms.split(",") if a]
     if args.parent_tree:
         arms = [p for a in arms for p in (["p" + a[1:], a] if a[0] == "a" else [a])]
