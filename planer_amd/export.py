@@ -17,6 +17,8 @@ import numpy
 
 from . import _lib, hip
 from .hip import DeviceArray
+from .plan import _IN_PLACE
+from .util import ImageFeed
 
 _ALIGN = 256
 _DTYPES = {"float32": 0, "int32": 1, "int64": 2, "uint8": 3, "bool": 3}
@@ -128,31 +130,60 @@ def _place(events, pinned):
     return offsets, top
 
 
+def _owners(a, spans):
+    return {k for k, (lo, hi) in spans.items() if lo <= a.ptr < hi}
+
+
+def _warm(net, prog, xs):
+    """One eager pass of `prog` on copies of `xs`, the declared output heads behind it (tuning, lazy uploads, pool sizes).
+    -> the graph inputs the recorded pass must get as copies: those a step rewrote in place -- a kind of `plan._IN_PLACE`, the
+    table of record for what rewrites srcs[0], whose first operand points into an input's block: the input itself or any view
+    of it, read off the pointer whatever kinds made the view -- and those a result of the pass is a view of.  A replay would
+    otherwise rewrite, or hand out, the plan's input block."""
+    work = [a.copy() for a in xs]
+    spans = {k: (a.ptr, a.ptr + max(a.nbytes, 1)) for k, a in zip(net.input, work)}
+    hit = set()
+
+    def probe(obj, args):
+        if obj.name in _IN_PLACE and args and isinstance(args[0], DeviceArray):
+            hit.update(_owners(args[0], spans))
+    out = net._interpret(prog, list(work), probe=probe)
+    for o in (out if isinstance(out, tuple) else (out,)):
+        if isinstance(o, DeviceArray):
+            hit |= _owners(o, spans)
+    net._hand_back(out, False)
+    return hit
+
+
 def export_plan(net, *xs, path=None, mode="latency"):
     """-> bytes of the plan file for `net` on inputs shaped like `xs` (host arrays or DeviceArrays).  `mode="throughput"`: the conv
     algorithms a pipelined host (several plan instances on several streams) should run -- the pipeline-judged picks first."""
     ctx = net.ctx
     xs = [hip.asarray(numpy.asarray(a) if not isinstance(a, DeviceArray) else a, ctx=ctx) for a in xs]
-    shapes = {k: a.shape for k, a in zip(net.input, xs)}
+    # a uint8 batch of an input declared with Net.image_input is the plan's input as it is: the decode kernel is the file's
+    # first call, and the pass runs on the float32 tensor it writes (what Net._compile builds its plan for)
+    feeds = net._image_feeds(xs)
+    floats = [a.materialise() if isinstance(a, ImageFeed) else a for a in feeds]
+    shapes = {k: a.shape for k, a in zip(net.input, floats)}
     shapes.update({k: w.shape for k, w in zip(net.inits, net.weights)})
-    net._interpret(net._program, [a.copy() for a in xs], shapes=shapes)          # validates the graph, records every shape
+    net._interpret(net._program, [a.copy() for a in floats], shapes=shapes)      # validates the graph, records every shape
     with net.picking(mode):
         prog, _ = net._fuse(shapes, net.use_fusion)
-    net._interpret(prog, [a.copy() for a in xs])                                 # warm: tuning, lazy uploads, pool sizes
+    inplace = _warm(net, prog, floats)
+    del floats
     ctx.synchronize()
-    kinds = {name: obj.name for name, obj in prog.objs.items()}
-    inplace = set()
-    for src, names, dst in prog.flow:
-        if kinds.get(names[0] if isinstance(names, list) else names) in ("relu", "relu_q4", "flatten", "identity", "return"):
-            inplace.update(src if isinstance(src, list) else [src])
     rec = _Recorder(ctx)
     _lib._recorder, hip._free_hook = rec.on_call, rec.on_free
     try:
         statics = [DeviceArray(a.shape, a.dtype, ctx) for a in xs]               # recorded allocations: the plan's inputs
         in_ids = [rec.live[s.ptr][0] for s in statics]
-        work = [s.copy() if k in inplace else s for k, s in zip(net.input, statics)]
+        work = [f.spec.bind(s).materialise() if isinstance(f, ImageFeed) else s.copy() if k in inplace else s
+                for k, s, f in zip(net.input, statics, feeds)]
         out = net._interpret(prog, work)
         del work
+        # the declared outputs (image, label, object, keypoint, flow, text, detection): their encoders are device calls with
+        # tables of a declared size, recorded like the pass; an undeclared output is handed on as it is
+        out = net._hand_back(out, False)
         outs = list(out) if isinstance(out, tuple) else [out]
         out_recs = []
         for o in outs:

@@ -745,11 +745,12 @@ class Net:
         return obj.shape if hasattr(obj, "shape") else obj
 
     # ---- eager interpreter ---------------------------------------------------------
-    def _interpret(self, prog, xs, debug=False, shapes=None, profile=False, record=None, repeat=1):
+    def _interpret(self, prog, xs, debug=False, shapes=None, profile=False, record=None, repeat=1, probe=None):
         """net.py:37-72: one kernel launch (or view) per layer, in flow order.  `record` (a list)
         receives one dict per convolution / dense step: which kernel family and launch plan ran.  `profile` brackets the
         steps with stream markers; with `repeat` = R > 1 every step is launched R times between its markers (the time per
-        launch is what gets recorded: a marker costs about as much as a small kernel, R launches dilute it)."""
+        launch is what gets recorded: a marker costs about as much as a small kernel, R launches dilute it).  `probe(obj, args)`
+        is called in front of every step with the layer object and the operands it is about to get."""
         env = {"None": None}
         env.update(zip(self.inits, self.weights))
         env.update(self._extra)
@@ -769,6 +770,8 @@ class Net:
                 t0 = time.time()
                 if profile and not events:
                     events.append((None, None, hip.Event(self.ctx).record()))
+                if probe is not None:
+                    probe(obj, args)
                 val = obj(*args)
                 for _ in range(repeat - 1 if profile else 0):
                     val = obj(*args)

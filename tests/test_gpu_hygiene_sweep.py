@@ -450,19 +450,36 @@ def test_real_scale_random_nets_audited(pa, seed, monkeypatch, _plan_switches):
 
 
 # ---- plan files: pl_plan_build's eager pass on a zeroed and on a poisoned arena --------------------------------------------
-@pytest.mark.parametrize("name", ["resnet18", "yolov3", "customnet"])
-def test_plan_files_do_not_rely_on_the_zeroed_arena(name):
+def _plan_file_nets():
+    """The three nets at their own sizes, then every net tests/test_gpu_plan_file_kinds.py replays (all of them export), at
+    64 px and batch 2: "<name>@64"."""
+    from tests import plan_programs as PP
+    return ["resnet18", "yolov3", "customnet"] + [n + "@64" for n in list(PP.NETS) + ["crnn", "crnn_h12", "cellnet", "posenet"]]
+
+
+@pytest.mark.parametrize("name", _plan_file_nets())
+def test_plan_files_do_not_rely_on_the_zeroed_arena(name, monkeypatch):
     """pl_plan_build + pl_plan_run (ctypes only, tests/test_gpu_plan_file._run_plan) with the mode off -- the arena cleared to
-    zero, as shipped -- and under each poison: guards clean, outputs bit-identical in all three."""
+    zero, as shipped -- and under each poison: guards clean, outputs bit-identical in all three.  (The "@64" nets: with the
+    launch-plan tuner off in the three contexts that replay the file, which tune each for itself otherwise.)"""
     import planer_amd
     from planer_amd import hip
     from planer_amd.export import export_plan
     from planer_amd.irgen import customnet, resnet18, yolov3
     from tests import test_gpu_plan_file as PF
-    mod, x = {"resnet18": (resnet18, resnet18.make_input(2)), "yolov3": (yolov3, yolov3.make_input(1, size=160)),
-              "customnet": (customnet, customnet.make_input(2))}[name]
-    g, b = mod.build()
+    if name.endswith("@64"):
+        from tests.test_gpu_plan_file_kinds import load
+        monkeypatch.setenv("PLANER_HIP_AUTOTUNE", "0")
+        g, b, x = load(name[:-3])
+    else:
+        mod, x = {"resnet18": (resnet18, resnet18.make_input(2)), "yolov3": (yolov3, yolov3.make_input(1, size=160)),
+                  "customnet": (customnet, customnet.make_input(2))}[name]
+        g, b = mod.build()
     net = planer_amd.from_graph(g, b)
+    if name.endswith("@64"):
+        from tests.test_gpu_plan_file_kinds import install
+        # nothing timed: the last candidate that runs; the first for yolov3, whose file under the last holds a gigabyte of constants
+        install(net, "first" if name.startswith("yolov3") else "last")
     blob = export_plan(net, x)
     del net
     lib = PF._bind()

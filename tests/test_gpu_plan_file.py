@@ -43,9 +43,18 @@ def _ok(lib, rc):
     assert rc == 0, lib.pl_last_error().decode()
 
 
-def _run_plan(lib, blob, inputs, through_pointers=False, hygiene=None):
-    """ctypes only: -> list of output arrays.  hygiene = (guard bytes, poison byte): the context's pool in hygiene mode from the
-    start (pl_plan_build then poisons the arena instead of clearing it), and every guard clean at the end."""
+DTYPES = {0: np.dtype(np.float32), 1: np.dtype(np.int32), 2: np.dtype(np.int64), 3: np.dtype(np.uint8)}      # a tensor record's code
+DTYPE_CODES = {v: k for k, v in DTYPES.items()}
+
+
+def _run_plan(lib, blob, inputs, through_pointers=False, hygiene=None, then=None, stats=None, write_once=False):
+    """ctypes only: -> list of output arrays, each of the dtype its tensor record names.  hygiene = (guard bytes, poison byte):
+    the context's pool in hygiene mode from the start (pl_plan_build then poisons the arena instead of clearing it), and every
+    guard clean at the end.  An input is any array of the dtype its record names.  `then`: further input batches, each run once
+    on the SAME built plan behind the three replays of `inputs` -> (outputs, [outputs of each of them]).  `stats`: a dict that
+    receives the plan's `calls`, `arena` and `consts` (pl_plan_info).  `write_once`: the plan's own input buffers are written
+    before the first replay only, and the second and third run on what the runs before them left there -- which must be the
+    bytes that were written: a pass never rewrites an input of the plan."""
     ctx = ctypes.c_void_p()
     _ok(lib, lib.pl_ctx_create(0, ctypes.byref(ctx)))
     if hygiene is not None:
@@ -57,49 +66,64 @@ def _run_plan(lib, blob, inputs, through_pointers=False, hygiene=None):
     arena, consts = ctypes.c_size_t(), ctypes.c_size_t()
     _ok(lib, lib.pl_plan_info(plan, ctypes.byref(n_in), ctypes.byref(n_out), ctypes.byref(arena), ctypes.byref(consts), ctypes.byref(ncalls)))
     assert n_in.value == len(inputs) and ncalls.value > 0
-    outs = []
-    for rep in range(3):                                    # replays must be stable
+    if stats is not None:
+        stats.update(calls=ncalls.value, arena=arena.value, consts=consts.value)
+
+    def once(xs, upload=True):
         in_ptrs = (ctypes.c_void_p * n_in.value)()
         held = []
-        for i, x in enumerate(inputs):
+        for i, x in enumerate(xs):
             ptr, nbytes = ctypes.c_void_p(), ctypes.c_size_t()
             dims = (ctypes.c_int * 8)()
             nd, dt = ctypes.c_int(), ctypes.c_int()
             _ok(lib, lib.pl_plan_tensor(plan, 0, i, ctypes.byref(ptr), ctypes.byref(nbytes), ctypes.byref(dt), ctypes.byref(nd), dims))
-            assert nbytes.value == x.nbytes and tuple(dims[:nd.value]) == x.shape and dt.value == 0
+            assert nbytes.value == x.nbytes and tuple(dims[:nd.value]) == x.shape and dt.value == DTYPE_CODES[x.dtype]
             if through_pointers:                            # the caller's own device buffer, copied in by pl_plan_run
                 mine = ctypes.c_void_p()
                 _ok(lib, lib.pl_alloc(ctx, x.nbytes, ctypes.byref(mine)))
                 _ok(lib, lib.pl_h2d(ctx, mine, x.ctypes.data, x.nbytes))
                 in_ptrs[i] = mine.value
                 held.append(mine)
-            else:
+            elif upload:
                 _ok(lib, lib.pl_h2d(ctx, ptr, x.ctypes.data, x.nbytes))
         _ok(lib, lib.pl_plan_run(plan, in_ptrs if through_pointers else None, None))
         _ok(lib, lib.pl_sync(ctx))
+        for i, x in enumerate(xs if write_once else ()):      # the run left the plan's input buffer as it was written
+            ptr, back = ctypes.c_void_p(), np.empty_like(x)
+            _ok(lib, lib.pl_plan_tensor(plan, 0, i, ctypes.byref(ptr), None, None, None, None))
+            _ok(lib, lib.pl_d2h(ctx, back.ctypes.data, ptr, x.nbytes))
+            np.testing.assert_array_equal(back.view(np.uint8), x.view(np.uint8), "a run rewrote input %d of the plan" % i)
         got = []
         for i in range(n_out.value):
             ptr, nbytes = ctypes.c_void_p(), ctypes.c_size_t()
             dims = (ctypes.c_int * 8)()
             nd, dt = ctypes.c_int(), ctypes.c_int()
             _ok(lib, lib.pl_plan_tensor(plan, 1, i, ctypes.byref(ptr), ctypes.byref(nbytes), ctypes.byref(dt), ctypes.byref(nd), dims))
-            y = np.empty(tuple(dims[:nd.value]), np.float32)
+            y = np.empty(tuple(dims[:nd.value]), DTYPES[dt.value])
             assert y.nbytes == nbytes.value
             _ok(lib, lib.pl_d2h(ctx, y.ctypes.data, ptr, y.nbytes))
             got.append(y)
-        for m in held:
+        for m, x in zip(held, xs):                          # a run reads the caller's buffers and never writes them
+            back = np.empty_like(x)
+            _ok(lib, lib.pl_d2h(ctx, back.ctypes.data, m, x.nbytes))
+            np.testing.assert_array_equal(back.view(np.uint8), x.view(np.uint8))
             lib.pl_free(ctx, m)
-        outs.append(got)
+        return got
+
+    inputs = [np.ascontiguousarray(x) for x in inputs]
+    assert not (write_once and through_pointers)
+    outs = [once(inputs, upload=not (write_once and rep)) for rep in range(3)]      # replays must be stable
     for other in outs[1:]:
         for a, c in zip(outs[0], other):
             np.testing.assert_array_equal(a, c)
+    later = [once([np.ascontiguousarray(x) for x in xs]) for xs in then or ()]
     _ok(lib, lib.pl_plan_destroy(plan))
     if hygiene is not None:
         dirty, report = ctypes.c_int(), ctypes.create_string_buffer(4096)
         _ok(lib, lib.pl_pool_debug_check(ctx, ctypes.byref(dirty), report, 4096))
         assert dirty.value == 0, report.value.decode()
     _ok(lib, lib.pl_ctx_destroy(ctx))
-    return outs[0]
+    return outs[0] if then is None else (outs[0], later)
 
 
 def test_resnet18_batch2_from_a_plan_file_with_ctypes_only(tmp_path):
