@@ -703,6 +703,31 @@ int pl_tile_normalise_f32(pl_ctx *ctx, float *buf, const float *count, int OH, i
 int pl_image_u8_nchw_f32(pl_ctx *ctx, const unsigned char *x, float *y, int N, int H, int W, int C, int nhwc,
                          int Co, const int *order, int OH, int OW, const int *ra, const float *rs, const int *ca,
                          const float *cs, const float *k, const float *b);
+/* ---- uint16 image batches, and per-image percentile scaling, as net input ----
+ * pl_image_u16_nchw_f32: pl_image_u8_nchw_f32 for 16-bit samples, argument for argument and rounding for rounding (r is the
+ *   sample widened to float); x is 2-byte aligned (else PL_EINVAL) and may start at any even address.  Limit: fewer than 2^31
+ *   source samples and output floats.  One launch.
+ * pl_image_norm_nchw_f32: the same decode of a batch of `bits` = 8 or 16 bit samples (else PL_EUNSUPPORTED) with the affine of
+ *   output channel c of image n taken from the percentiles lo <= hi (in [0, 100], else PL_EINVAL) of source plane
+ *   P = (n, order[c]), M = H W samples sorted ascending s_0 .. s_{M-1}, BEFORE any resize.  For q in {lo, hi}, on the host in
+ *   float64: v = q / 100 * (M - 1), j = floor(v), g = v - j, j1 = min(j + 1, M - 1); on the device in float64, every operation
+ *   rounded on its own: p = s_j + (s_j1 - s_j) * g; d = p_hi - p_lo, 1 unless d > 0; K = k[c] / d; B = b[c] - p_lo * K; then
+ *   y = fl(fl(r * fl32(K)) + fl32(B)) in float32.  k = 1, b = 0, lo = 1, hi = 99 is Cellpose's normalize99.
+ *   The order statistics are selected exactly by two 256-bin radix levels (integer atomics: reproducible); five launches
+ *   whatever the data, nothing waits for the host, nothing is uploaded: it runs under graph capture.
+ *   scratch: PL_IMAGE_NORM_SCRATCH_BYTES(N, C) bytes of the caller's (pl_image_norm_scratch_bytes says the same), 8-byte
+ *   aligned (else PL_EINVAL), contents irrelevant: every word the kernels read is written by a kernel of the same call.
+ *   A workgroup of the histogram passes takes PL_IMAGE_NORM_CHUNK_PIXELS consecutive pixels of one image. */
+#define PL_IMAGE_NORM_CHUNK_PIXELS 4096
+#define PL_IMAGE_NORM_PLANE_WORDS 1280
+#define PL_IMAGE_NORM_SCRATCH_BYTES(N, C) ((size_t)(N) * (size_t)(C) * PL_IMAGE_NORM_PLANE_WORDS * 4 + (size_t)(N) * 32)
+int pl_image_u16_nchw_f32(pl_ctx *ctx, const unsigned short *x, float *y, int N, int H, int W, int C, int nhwc,
+                          int Co, const int *order, int OH, int OW, const int *ra, const float *rs, const int *ca,
+                          const float *cs, const float *k, const float *b);
+int pl_image_norm_nchw_f32(pl_ctx *ctx, const void *x, int bits, float *y, int N, int H, int W, int C, int nhwc,
+                           int Co, const int *order, int OH, int OW, const int *ra, const float *rs, const int *ca,
+                           const float *cs, const float *k, const float *b, double lo, double hi, void *scratch);
+int pl_image_norm_scratch_bytes(int N, int C, size_t *bytes);
 /* ---- uint8 images and label maps as net output ----
  * Both read x, the float32 (N, C, H, W) tensor a net wrote (any 4-byte boundary), and write uint8 y, which may start at any
  * byte; call them behind pl_plan_run, on the plan's context.  Asynchronous on ctx's stream; nothing is allocated or uploaded.

@@ -221,6 +221,10 @@ SIGNATURES = {
     "pl_lstm_seq_f32": [_P] + [_P] * 8 + [_I] * 5,
     "pl_resize_hwc_f32": [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P],
     "pl_image_u8_nchw_f32": [_P, _P, _P, _I, _I, _I, _I, _I, _I, POINTER(c_int), _I, _I, _P, _P, _P, _P, POINTER(c_float), POINTER(c_float)],
+    "pl_image_u16_nchw_f32": [_P, _P, _P, _I, _I, _I, _I, _I, _I, POINTER(c_int), _I, _I, _P, _P, _P, _P, POINTER(c_float), POINTER(c_float)],
+    "pl_image_norm_nchw_f32": [_P, _P, _I, _P, _I, _I, _I, _I, _I, _I, POINTER(c_int), _I, _I, _P, _P, _P, _P, POINTER(c_float), POINTER(c_float),
+                               c_double, c_double, _P],
+    "pl_image_norm_scratch_bytes": [_I, _I, POINTER(c_size_t)],
     "pl_image_f32_u8": [_P, _P, _P, _I, _I, _I, _I, _I, POINTER(c_int), _I, POINTER(c_float), POINTER(c_float), _I],
     "pl_labels_f32_u8": [_P, _P, _P, _I, _I, _I, _I, c_double],
     "pl_yolo_decode_f32": [_P, _P, _I, _I, _I, _I, _I, POINTER(c_float), c_double, c_double, c_double, _I, _I, _P, _P, _P],

@@ -9,6 +9,7 @@
 #include "groupnorm_q4_kernel.h"
 #include "pixel_shuffle_q4_kernel.h"
 #include "image_input_kernel.h"
+#include "image_input16_kernel.h"
 #include "image_output_kernel.h"
 #include "detect_kernel.h"
 #include "dfl_kernel.h"
@@ -933,6 +934,112 @@ int pl_image_u8_nchw_f32(pl_ctx *ctx, const unsigned char *x, float *y, int N, i
         else ii::image_u8_flat_kernel<false><<<(unsigned)N * Co * tiles, TPB, 0, ctx->stream>>>(x, y, HWo, C, Co, tiles, af, vec);
     }
     PL_LAUNCH_CHECK();
+    return PL_OK;
+}
+
+}  // extern "C"
+
+// uint16 batches and per-image percentile scaling (image_input16_kernel.h).  Every refusal comes before any launch.
+namespace {
+// pct: null, or {lo, hi} and then `scratch` holds PL_IMAGE_NORM_SCRATCH_BYTES(N, C) bytes
+template <typename T>
+int image16_decode(pl_ctx *ctx, const char *name, const T *x, float *y, int N, int H, int W, int C, int nhwc, int Co, const int *order,
+                   int OH, int OW, const int *ra, const float *rs, const int *ca, const float *cs, const float *k, const float *b,
+                   const double *pct, void *scratch) {
+    namespace ii = image_input16;
+    PL_REQUIRE(ctx && k && b, PL_EINVAL, "%s: null argument", name);
+    PL_REQUIRE(N >= 0 && H > 0 && W > 0 && OH > 0 && OW > 0, PL_EINVAL, "%s: bad shape", name);
+    PL_REQUIRE(C >= 1 && C <= ii::MAX_C && Co >= 1 && Co <= ii::MAX_C, PL_EUNSUPPORTED, "%s: 1 to 4 channels, got C = %d, Co = %d",
+               name, C, Co);
+    PL_REQUIRE(order || Co == C, PL_EINVAL, "%s: no channel order given and Co != C", name);
+    ii::Affine af;
+    for (int c = 0; c < ii::MAX_C; ++c) {
+        af.k[c] = c < Co ? k[c] : 0.f;
+        af.b[c] = c < Co ? b[c] : 0.f;
+        af.order[c] = c < Co ? (order ? order[c] : c) : 0;
+        PL_REQUIRE(af.order[c] >= 0 && af.order[c] < C, PL_EINVAL, "%s: order[%d] = %d is no source channel", name, c, af.order[c]);
+    }
+    const bool tables = ra || rs || ca || cs;
+    PL_REQUIRE(!tables || (ra && rs && ca && cs), PL_EINVAL, "%s: all four sampling tables or none", name);
+    PL_REQUIRE(tables || (OH == H && OW == W), PL_EINVAL, "%s: OH x OW != H x W needs sampling tables", name);
+    PL_REQUIRE(!tables || nhwc, PL_EUNSUPPORTED, "%s: resize takes the (N, H, W, C) layout only", name);
+    PL_REQUIRE(!tables || (H >= 2 && W >= 2), PL_EINVAL, "%s: resize needs H, W >= 2", name);
+    const size_t HW = (size_t)H * W, HWo = (size_t)OH * OW;
+    PL_REQUIRE((size_t)N * HW * C < (1ull << 31) && (size_t)N * Co * HWo < (1ull << 31), PL_EUNSUPPORTED,
+               "%s: 2^31 or more source samples or output floats", name);
+    PL_REQUIRE(reinterpret_cast<uintptr_t>(x) % sizeof(T) == 0, PL_EINVAL, "%s: x is not aligned to its %d-byte samples", name,
+               (int)sizeof(T));
+    ii::Ranks rk = {};
+    if (pct) {
+        PL_REQUIRE(pct[0] >= 0.0 && pct[0] <= pct[1] && pct[1] <= 100.0, PL_EINVAL, "%s: percentiles 0 <= lo <= hi <= 100, got %g, %g",
+                   name, pct[0], pct[1]);
+        PL_REQUIRE(scratch && reinterpret_cast<uintptr_t>(scratch) % 8 == 0, PL_EINVAL, "%s: scratch is null or not 8-byte aligned", name);
+        for (int q = 0; q < 2; ++q) {                      // (HW < 2^31: the ranks fit the 32-bit counters)
+            const double v = pct[q] / 100.0 * (double)(HW - 1);
+            const double j = floor(v);
+            rk.j[2 * q] = (unsigned)j;
+            rk.j[2 * q + 1] = (unsigned)std::min((size_t)j + 1, HW - 1);
+            rk.g[q] = v - j;
+        }
+    }
+    if (N == 0) return PL_OK;
+    PL_REQUIRE(x && y, PL_EINVAL, "%s: null argument", name);
+    CtxGuard g(ctx);
+    const float2 *kb = nullptr;
+    if (pct) {
+        // a planar source is N C images of one channel; image n owns planes n C .. n C + C - 1 either way
+        const size_t images = nhwc ? (size_t)N : (size_t)N * C, words = (size_t)N * C * ii::PLANE_WORDS;
+        const int ch = nhwc ? C : 1;
+        const size_t chunk_px = ii::chunk_pixels(images, HW);          // (chunk_px * ch <= max(HW ch, 4 CHUNK_PX) < 2^31: an int)
+        const unsigned chunks = cdiv(HW, chunk_px);
+        unsigned *hist = static_cast<unsigned *>(scratch);
+        float2 *table = reinterpret_cast<float2 *>(hist + words);
+        ii::clear_kernel<<<stream_grid(ctx, words), TPB, 0, ctx->stream>>>(hist, words);
+        ii::hist_hi_kernel<T><<<(unsigned)images * chunks, TPB, 0, ctx->stream>>>(x, hist, HW, ch, chunks, chunk_px);
+        ii::hist_lo_kernel<T><<<(unsigned)images * chunks, TPB, 0, ctx->stream>>>(x, hist, HW, ch, chunks, chunk_px, rk);
+        ii::affine_kernel<<<(unsigned)N, TPB, 0, ctx->stream>>>(hist, table, C, Co, af, rk, 16 - 8 * (int)sizeof(T));
+        kb = table;
+    }
+    if (tables) {
+        const int groups = (OW + ii::LANE_PX - 1) / ii::LANE_PX;
+        const size_t total = (size_t)N * OH * groups;
+        ii::image_resize_kernel<T><<<stream_grid(ctx, total), TPB, 0, ctx->stream>>>(x, y, total, H, W, C, Co, OH, OW, groups, ra, rs, ca,
+                                                                                  cs, af, kb, aligned16(y) && OW % 4 == 0);
+    } else {
+        const unsigned tiles = cdiv(HWo, ii::TILE_PX);
+        const bool vec = aligned16(y) && HWo % 4 == 0;
+        if (nhwc) ii::image_flat_kernel<T, true><<<(unsigned)N * tiles, TPB, 0, ctx->stream>>>(x, y, HWo, C, Co, tiles, af, kb, vec);
+        else ii::image_flat_kernel<T, false><<<(unsigned)N * Co * tiles, TPB, 0, ctx->stream>>>(x, y, HWo, C, Co, tiles, af, kb, vec);
+    }
+    PL_LAUNCH_CHECK();
+    return PL_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int pl_image_u16_nchw_f32(pl_ctx *ctx, const unsigned short *x, float *y, int N, int H, int W, int C, int nhwc, int Co,
+                          const int *order, int OH, int OW, const int *ra, const float *rs, const int *ca, const float *cs,
+                          const float *k, const float *b) {
+    return image16_decode(ctx, "pl_image_u16_nchw_f32", x, y, N, H, W, C, nhwc, Co, order, OH, OW, ra, rs, ca, cs, k, b, nullptr,
+                          nullptr);
+}
+
+int pl_image_norm_nchw_f32(pl_ctx *ctx, const void *x, int bits, float *y, int N, int H, int W, int C, int nhwc, int Co,
+                           const int *order, int OH, int OW, const int *ra, const float *rs, const int *ca, const float *cs,
+                           const float *k, const float *b, double lo, double hi, void *scratch) {
+    PL_REQUIRE(bits == 8 || bits == 16, PL_EUNSUPPORTED, "pl_image_norm_nchw_f32: 8 or 16 bit samples, got %d", bits);
+    const double pct[2] = {lo, hi};
+    if (bits == 8)
+        return image16_decode(ctx, "pl_image_norm_nchw_f32", static_cast<const unsigned char *>(x), y, N, H, W, C, nhwc, Co, order, OH,
+                              OW, ra, rs, ca, cs, k, b, pct, scratch);
+    return image16_decode(ctx, "pl_image_norm_nchw_f32", static_cast<const unsigned short *>(x), y, N, H, W, C, nhwc, Co, order, OH, OW,
+                          ra, rs, ca, cs, k, b, pct, scratch);
+}
+
+int pl_image_norm_scratch_bytes(int N, int C, size_t *bytes) {
+    PL_REQUIRE(bytes && N >= 0 && C >= 1, PL_EINVAL, "pl_image_norm_scratch_bytes: null argument or a bad shape");
+    *bytes = PL_IMAGE_NORM_SCRATCH_BYTES(N, C);
     return PL_OK;
 }
 

@@ -159,10 +159,17 @@ def export_plan(net, *xs, path=None, mode="latency"):
     """-> bytes of the plan file for `net` on inputs shaped like `xs` (host arrays or DeviceArrays).  `mode="throughput"`: the conv
     algorithms a pipelined host (several plan instances on several streams) should run -- the pipeline-judged picks first."""
     ctx = net.ctx
+    for a in xs:                                          # (before anything is uploaded, recorded or written)
+        if getattr(a, "dtype", None) == numpy.uint16:
+            raise NotImplementedError("export_plan: a uint16 batch, and the plan file has no dtype code for uint16 (%s); "
+                                      "export for the float32 batch it decodes to" % sorted(_DTYPES))
     xs = [hip.asarray(numpy.asarray(a) if not isinstance(a, DeviceArray) else a, ctx=ctx) for a in xs]
     # a uint8 batch of an input declared with Net.image_input is the plan's input as it is: the decode kernel is the file's
     # first call, and the pass runs on the float32 tensor it writes (what Net._compile builds its plan for)
     feeds = net._image_feeds(xs)
+    if any(isinstance(a, ImageFeed) and a.spec.normalise is not None for a in feeds):
+        raise NotImplementedError("export_plan: an image input declared with normalise=, and its percentile passes are not "
+                                  "recorded into plan files; export for the float32 batch it decodes to")
     floats = [a.materialise() if isinstance(a, ImageFeed) else a for a in feeds]
     shapes = {k: a.shape for k, a in zip(net.input, floats)}
     shapes.update({k: w.shape for k, w in zip(net.inits, net.weights)})

@@ -30,7 +30,7 @@ from . import q4 as _q4
 from .conv_layouts import DIRECT_Q4, IGEMM_NCHW, LAYOUTS, STEM_POOL, STEM_POOL_NCHW, WINO4_Q4, WINO43_Q4, experiment, suffix
 from .layer import layer_map, wrap
 from .plan import compile_front, fuse_upsample_concat, lower
-from .util import BlendGeometry, DetectionSpec, FlowSpec, ImageFeed, ImageOutSpec, ImageSpec, KeypointSpec, LabelSpec, ObjectSpec, TextSpec, WindowFeed, _Tiling
+from .util import IMAGE_DTYPES, BlendGeometry, DetectionSpec, FlowSpec, ImageFeed, ImageOutSpec, ImageSpec, KeypointSpec, LabelSpec, ObjectSpec, TextSpec, WindowFeed, _Tiling
 from .util import blend_windows as _blend_windows, resize as _resize
 
 STEM_WINO_DEFAULT = 1      # whether the stem + max-pool step takes the F(4,4) form where it applies
@@ -421,15 +421,18 @@ class Net:
         self._host[:] = self._blob.get()
         self._plans, self._extra = {}, {}
 
-    def image_input(self, k, b, layout="nhwc", size=None, order=None, key=None):
-        """Input `key` (default: the first) also takes uint8 image batches, host ndarray or DeviceArray, (N, H, W, C) for
-        layout "nhwc" or (N, C, H, W) for "nchw": the net then reads fl(fl(x * k[c]) + b[c]) as float32 NCHW (k, b per channel
-        from util.image_affine), channel c taken from source channel order[c], resized to `size` by util.resize's rule where
-        the batch's H x W differs.  The decode is one kernel (pl_image_u8_nchw_f32) in front of the pass; a uint8 batch runs the
-        plan of the float32 tensor it decodes to.  float32 inputs are taken as before.  Calling it again replaces the
-        declaration."""
-        self._image_in[key] = ImageSpec(k, b, layout, size, order)
-        u8 = lambda sig: any(dt == "uint8" for _, dt in sig)        # noqa: E731
+    def image_input(self, k, b, layout="nhwc", size=None, order=None, key=None, normalise=None):
+        """Input `key` (default: the first) also takes uint8 and uint16 image batches, host ndarray or DeviceArray, (N, H, W, C)
+        for layout "nhwc" or (N, C, H, W) for "nchw": the net then reads fl(fl(x * k[c]) + b[c]) as float32 NCHW (k, b per channel
+        from util.image_affine; scale=65535 for 16-bit samples), channel c taken from source channel order[c], resized to `size`
+        by util.resize's rule where the batch's H x W differs.  The decode is one kernel (pl_image_u8_nchw_f32,
+        pl_image_u16_nchw_f32) in front of the pass; an image batch runs the plan of the float32 tensor it decodes to.
+        normalise=("percentile", lo, hi) scales every image by the percentiles of each of its source planes first
+        (util.ImageSpec; k = 1, b = 0, (1, 99) is Cellpose's normalize99): five launches in front of the pass
+        (pl_image_norm_nchw_f32), nothing computed on or uploaded from the host.  float32 inputs are taken as before.  Calling it
+        again replaces the declaration."""
+        self._image_in[key] = ImageSpec(k, b, layout, size, order, normalise)
+        u8 = lambda sig: any(dt in ("uint8", "uint16") for _, dt in sig)        # noqa: E731
         self._plans = {s: p for s, p in self._plans.items() if not u8(s[1:])}
         self._eager_prog = {s: p for s, p in self._eager_prog.items() if not u8(s)}
         return self
@@ -565,6 +568,9 @@ class Net:
         if self._detect is not None:
             raise ValueError("Net.tiled: detections of windows cannot be blended; `float_output` removes the declaration")
         host_in = isinstance(image, numpy.ndarray)
+        if isinstance(image, (numpy.ndarray, DeviceArray)) and image.dtype == numpy.uint16:
+            raise NotImplementedError("Net.tiled: a uint16 image is not taken: its percentiles would be those of the whole scan, and "
+                                      "the window gather has no 16-bit form; scale it to float32 (or uint8) first")
         if host_in and image.dtype != numpy.uint8:
             image = numpy.ascontiguousarray(image, dtype=numpy.float32)
         if not isinstance(image, (numpy.ndarray, DeviceArray)) or image.ndim not in (2, 3) or image.dtype not in (numpy.uint8, numpy.float32):
@@ -574,6 +580,9 @@ class Net:
             spec = self._image_spec(0)
             if spec is None:
                 raise ValueError("Net.tiled: a uint8 image needs `image_input` declared (its k, b and order are used)")
+            if spec.normalise is not None:
+                raise NotImplementedError("Net.tiled: `image_input` is declared with normalise=%r, and the percentiles of a whole "
+                                          "scan are not built (the window gather scales by k and b alone)" % (spec.normalise,))
         out_spec = self._image_out.get(0)
         if isinstance(out_spec, TextSpec):
             raise ValueError("Net.tiled: a text output is declared, and a blended scan is no sequence tensor; "
@@ -714,11 +723,12 @@ class Net:
         return self._image_in.get(name, self._image_in.get(None) if pos == 0 else None)
 
     def _image_feeds(self, xs):
-        """uint8 batches of inputs declared with `image_input` (host arrays are uploaded as they are) -> ImageFeeds."""
+        """uint8 and uint16 batches of inputs declared with `image_input` (host arrays are uploaded as they are) -> ImageFeeds.
+        (An int16 batch goes to ImageFeed too: it says why it is refused.)"""
         xs = list(xs)
         for i, a in enumerate(xs if self._image_in else ()):
             spec = self._image_spec(i)
-            if spec is not None and isinstance(a, (DeviceArray, numpy.ndarray)) and a.dtype == numpy.uint8:
+            if spec is not None and isinstance(a, (DeviceArray, numpy.ndarray)) and (a.dtype in IMAGE_DTYPES or a.dtype == numpy.int16):
                 xs[i] = spec.bind(hip.asarray(a, ctx=self.ctx))
         return xs
 
@@ -727,7 +737,7 @@ class Net:
         sig = []
         for i, a in enumerate(xs):
             spec = self._image_spec(i) if self._image_in else None
-            if spec is not None and not isinstance(a, ImageFeed) and a.dtype == numpy.uint8:
+            if spec is not None and not isinstance(a, ImageFeed) and a.dtype in IMAGE_DTYPES:
                 sig.append((spec.geometry(a.shape)[1], "float32"))
             else:
                 sig.append((tuple(a.shape), str(a.dtype)))

@@ -84,7 +84,10 @@ def resize(img, size):
     return y
 
 
-# ---- uint8 image batches as net input ----------------------------------------------------------------------
+# ---- uint8 and uint16 image batches as net input -----------------------------------------------------
+IMAGE_DTYPES = (numpy.dtype(numpy.uint8), numpy.dtype(numpy.uint16))
+
+
 def image_affine(mean, std, scale=255.0):
     """(k, b) with x / scale, - mean, / std folded into one multiply and one add per element: k = 1 / (scale * std),
     b = -mean / std, evaluated in float64 and rounded once to float32.  mean and std: one value per output channel."""
@@ -109,10 +112,13 @@ def _sampling_tables(ctx, h, w, oh, ow):
 
 
 class ImageSpec:
-    """How a uint8 image batch becomes a net's float32 NCHW input: y[:, c] = fl(fl(r * k[c]) + b[c]) with r the byte of source
-    channel order[c], or util.resize's sample of those bytes where `size` differs from the batch's H x W.  Host values only."""
+    """How a uint8 or uint16 image batch becomes a net's float32 NCHW input: y[:, c] = fl(fl(r * k[c]) + b[c]) with r the sample
+    of source channel order[c], or util.resize's sample of those where `size` differs from the batch's H x W.  With
+    normalise=("percentile", lo, hi), k[c] and b[c] are first divided and shifted by the percentiles of each image's source
+    plane, before any resize: K = k[c] / (p_hi - p_lo), B = b[c] - p_lo K in float64 (a difference that is not > 0 counts as 1),
+    numpy's linear percentiles; k = 1, b = 0, (1, 99) is Cellpose's normalize99.  Host values only."""
 
-    def __init__(self, k, b, layout="nhwc", size=None, order=None):
+    def __init__(self, k, b, layout="nhwc", size=None, order=None, normalise=None):
         k, b = numpy.atleast_1d(numpy.asarray(k)), numpy.atleast_1d(numpy.asarray(b))
         if layout not in ("nhwc", "nchw"):
             raise ValueError("image input: layout is 'nhwc' or 'nchw', got %r" % (layout,))
@@ -128,6 +134,12 @@ class ImageSpec:
             size = (int(size[0]), int(size[1]))
             if layout == "nchw":
                 raise NotImplementedError("image input: resizing takes the 'nhwc' layout only")
+        if normalise is not None:
+            if (not isinstance(normalise, (tuple, list)) or len(normalise) != 3 or normalise[0] != "percentile"
+                    or not all(_is_number(q) for q in normalise[1:]) or not 0 <= normalise[1] <= normalise[2] <= 100):
+                raise ValueError('image input: normalise is ("percentile", lo, hi) with 0 <= lo <= hi <= 100, got %r' % (normalise,))
+            normalise = ("percentile", float(normalise[1]), float(normalise[2]))
+        self.normalise = normalise
         self.k, self.b = k.astype(numpy.float32), b.astype(numpy.float32)
         self.layout, self.size, self.order, self.channels = layout, size, order, int(k.size)
         self._k = (_lib.c_float * self.channels)(*self.k.tolist())
@@ -135,10 +147,13 @@ class ImageSpec:
         self._order = (_lib.c_int * self.channels)(*order) if order is not None else None
 
     def geometry(self, shape):
-        """(N, H, W, C) of a uint8 batch of `shape` in this layout and the (N, Co, OH, OW) it decodes to."""
+        """(N, H, W, C) of an image batch of `shape` in this layout and the (N, Co, OH, OW) it decodes to."""
         if len(shape) != 4:
-            raise ValueError("image input: a uint8 batch is 4-d (%s), got shape %s" % (self.layout, tuple(shape)))
+            raise ValueError("image input: an image batch is 4-d (%s), got shape %s" % (self.layout, tuple(shape)))
         n, h, w, c = shape if self.layout == "nhwc" else (shape[0], shape[2], shape[3], shape[1])
+        if self.normalise is not None and h * w >= 1 << 31:
+            raise NotImplementedError("image input: a plane of %d x %d = %d samples, and the per-plane rank counters of the "
+                                      "percentile selection are 32-bit (fewer than 2^31 samples)" % (h, w, h * w))
         if not 1 <= c <= 4:
             raise NotImplementedError("image input: 1 to 4 source channels, got %d in shape %s (%s)" % (c, tuple(shape), self.layout))
         if self.order is None and self.channels != c:
@@ -160,16 +175,25 @@ class ImageSpec:
 
 
 class ImageFeed:
-    """A uint8 device batch standing for the float32 tensor it decodes to: `shape` / `dtype` are the decoded tensor's (a plan
-    is looked up by them), `decode_into` writes that tensor wherever the caller wants it, on the stream the caller names."""
+    """A uint8 or uint16 device batch standing for the float32 tensor it decodes to: `shape` / `dtype` are the decoded tensor's (a
+    plan is looked up by them), `decode_into` writes that tensor wherever the caller wants it, on the stream the caller names.
+    The counters of a percentile scaling are taken from the batch's pool here, when the feed is bound; the decode clears them."""
 
     def __init__(self, spec, x):
-        if not isinstance(x, DeviceArray) or x.dtype != numpy.uint8:
-            raise TypeError("image input: expected a uint8 DeviceArray, got %r" % (x,))
+        if isinstance(x, DeviceArray) and x.dtype == numpy.int16:
+            raise TypeError("image input: int16 batches are not taken (signed samples and their rescale slopes are not built); "
+                            "uint8 or uint16, got %r" % (x,))
+        if not isinstance(x, DeviceArray) or x.dtype not in IMAGE_DTYPES:
+            raise TypeError("image input: expected a uint8 DeviceArray or a uint16 one, got %r" % (x,))
         self.spec, self.u8, self.ctx = spec, x, x.ctx
         self.src, self.shape = spec.geometry(x.shape)
         self.dtype, self.ndim = numpy.dtype(numpy.float32), 4
         self.tabs = spec.tables(x.ctx, self.src, self.shape)
+        self.scratch = None
+        if spec.normalise is not None and self.src[0]:
+            size = _lib.c_size_t()
+            _lib.call("pl_image_norm_scratch_bytes", self.src[0], self.src[3], _lib.byref(size))
+            self.scratch = hip.empty(((size.value + 7) // 8,), numpy.int64, ctx=x.ctx)
 
     @property
     def nbytes(self):
@@ -178,8 +202,14 @@ class ImageFeed:
     def decode_into(self, ptr, ctx=None):
         n, h, w, c = self.src
         sp, t = self.spec, self.tabs
-        _lib.call("pl_image_u8_nchw_f32", (ctx or self.ctx).handle, self.u8.ptr, ptr, n, h, w, c, int(sp.layout == "nhwc"),
-                  sp.channels, sp._order, self.shape[2], self.shape[3], *([a.ptr for a in t] if t else [None] * 4), sp._k, sp._b)
+        args = (ptr, n, h, w, c, int(sp.layout == "nhwc"), sp.channels, sp._order, self.shape[2], self.shape[3],
+                *([a.ptr for a in t] if t else [None] * 4), sp._k, sp._b)
+        handle = (ctx or self.ctx).handle
+        if sp.normalise is None:
+            _lib.call("pl_image_u8_nchw_f32" if self.u8.dtype == numpy.uint8 else "pl_image_u16_nchw_f32", handle, self.u8.ptr, *args)
+        elif n:
+            _lib.call("pl_image_norm_nchw_f32", handle, self.u8.ptr, 8 * self.u8.dtype.itemsize, *args, sp.normalise[1],
+                      sp.normalise[2], self.scratch.ptr)
 
     def materialise(self):
         y = hip.empty(self.shape, ctx=self.ctx)
@@ -190,11 +220,13 @@ class ImageFeed:
         return ImageFeed(self.spec, self.u8.rows(lo, hi))
 
 
-def decode_images(x, k, b, layout="nhwc", size=None, order=None):
-    """A uint8 DeviceArray batch, (N, H, W, C) or (N, C, H, W), as the float32 (N, Co, OH, OW) DeviceArray
-    fl(fl(r * k[c]) + b[c]) (pl_image_u8_nchw_f32): r is the byte of source channel order[c] (default: c), bilinearly resampled
-    to `size` as util.resize does where that differs from H x W.  (k, b) from `image_affine`.  Asynchronous on x's stream."""
-    return ImageFeed(ImageSpec(k, b, layout, size, order), x).materialise()
+def decode_images(x, k, b, layout="nhwc", size=None, order=None, normalise=None):
+    """A uint8 or uint16 DeviceArray batch, (N, H, W, C) or (N, C, H, W), as the float32 (N, Co, OH, OW) DeviceArray
+    fl(fl(r * k[c]) + b[c]) (pl_image_u8_nchw_f32, pl_image_u16_nchw_f32): r is the sample of source channel order[c] (default:
+    c), bilinearly resampled to `size` as util.resize does where that differs from H x W.  (k, b) from `image_affine` (scale=65535
+    for 16-bit samples).  normalise=("percentile", lo, hi): scaled per image and source plane first (`ImageSpec`;
+    pl_image_norm_nchw_f32).  Asynchronous on x's stream."""
+    return ImageFeed(ImageSpec(k, b, layout, size, order, normalise), x).materialise()
 
 
 # ---- uint8 images and label maps as net output (DESIGN 4.23) -------------------------------------------------------------

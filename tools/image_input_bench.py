@@ -11,6 +11,11 @@ summary line; `b_not_slower_than_a` is the check: the median of b is not below t
 between same-arm rounds.
     python tools/image_input_bench.py [--batch 32] [--rounds 3] [--passes 100] [--arms abc] [--root DIR]
 --arms a with --root DIR times arm a alone on the package found in DIR (another checkout: the parent commit's figure).
+--dtype uint16 [--normalise lo,hi] times the 16-bit decode instead, kernels alone, ALTERNATING --rounds times: the
+uint8 kernel and the uint16 kernel on the same pixel count (bytes moved per microsecond each), and with --normalise the
+five-launch percentile-scaled decode on (batch, size, size, 3) and on (1, 4096, 4096, 1); one JSON line per timing.  Per-pass
+times come from a kernel trace of the same command (rocprofv3 --kernel-trace --stats -- python tools/image_input_bench.py
+--child --dtype uint16 --normalise 1,99).
 The device work runs in a child process under a timeout of its own; the parent never opens the GPU."""
 import argparse
 import collections
@@ -133,6 +138,46 @@ def device(args):
                               "launch_floor_us": round(floor * 1e6, 1)}), flush=True)
 
 
+def device16(args):
+    """uint8 decode | uint16 decode [| uint16 percentile-scaled decode], kernels alone, in alternating rounds."""
+    sys.path.insert(0, args.root)
+    import planer_amd
+    from planer_amd import hip
+    from planer_amd.util import ImageFeed, ImageSpec
+    ctx = hip.context()
+    rng = np.random.default_rng(3)
+    norm = ("percentile",) + tuple(float(q) for q in args.normalise.split(",")) if args.normalise else None
+
+    def timed(fn, bursts=5, reps=20):
+        for _ in range(3):
+            fn()
+        best = None
+        for _ in range(bursts):
+            e0 = hip.Event(ctx).record()
+            for _ in range(reps):
+                fn()
+            e1 = hip.Event(ctx).record()
+            t = e0.elapsed_ms(e1) / reps
+            best = t if best is None else min(best, t)
+        return best * 1e-3
+    for shape in [(args.batch, args.size, args.size, 3)] + ([(1, 4096, 4096, 1)] if norm else []):
+        c = shape[3]
+        k, b = np.ones(c, np.float32), np.zeros(c, np.float32)
+        y = hip.empty((shape[0], c, shape[1], shape[2]), ctx=ctx)
+        x8 = planer_amd.asarray(rng.integers(0, 256, shape, dtype=np.uint8))
+        x16 = planer_amd.asarray(rng.integers(0, 65536, shape, dtype=np.uint16))
+        # (bytes the algorithm moves: the source once per pass that reads it, the output once)
+        arms = [("uint8", ImageFeed(ImageSpec(k, b), x8), x8.nbytes + y.nbytes), ("uint16", ImageFeed(ImageSpec(k, b), x16), x16.nbytes + y.nbytes)]
+        if norm:
+            arms.append(("uint16 normalised", ImageFeed(ImageSpec(k, b, normalise=norm), x16), 3 * x16.nbytes + y.nbytes))
+        for rnd in range(args.rounds):
+            for label, feed, nbytes in arms:
+                t = timed(lambda: feed.decode_into(y.ptr))
+                print(json.dumps({"kernel": label, "shape": shape, "round": rnd, "us": round(t * 1e6, 1), "bytes": nbytes,
+                                  "bytes_per_us": round(nbytes / t / 1e6, 1), "output_bytes_per_us": round(y.nbytes / t / 1e6, 1)}),
+                      flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=32)
@@ -146,9 +191,20 @@ def main():
     ap.add_argument("--root", default=HERE, help="directory that holds the planer_amd package to time")
     ap.add_argument("--timeout", type=int, default=500, help="seconds the device child may take")
     ap.add_argument("--child", action="store_true")
+    ap.add_argument("--dtype", default="uint8", choices=["uint8", "uint16"], help="uint16: the 16-bit decode kernels alone")
+    ap.add_argument("--normalise", default=None, help="lo,hi: with --dtype uint16, also the percentile-scaled decode")
     args = ap.parse_args()
+    if args.normalise and args.dtype != "uint16":
+        ap.error("--normalise goes with --dtype uint16")
     if args.child:
-        return device(args)
+        return device16(args) if args.dtype == "uint16" else device(args)
+    if args.dtype == "uint16":
+        cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, os.path.abspath(__file__), "--child"] + sys.argv[1:]
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        if r.returncode != 0:
+            sys.exit("device child failed (exit %d):\n%s\n%s" % (r.returncode, r.stdout[-2000:], r.stderr[-3000:]))
+        print(r.stdout, end="")
+        return
     out = {"workload": "resnet18", "batch": args.batch, "size": args.size, "dtype": "fp32", "passes": args.passes,
            "rounds": args.rounds, "root": os.path.relpath(args.root, HERE)}
     if "f" in args.also:
